@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: discriminator-step images/sec (ContraD, SimCLR aug) on synthetic batches, random-init weights.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c10_b512|sg2_32|sg2_512|all]
+    python bench.py [--gpus N --steps K --warmup W] [--config c10_b512|sg2_32|sg2_512|all] [--dump-outputs DIR]
 
 ``--gpus N`` (N > 1) spawns one process per GPU itself (re-exec under ``torch.distributed.run`` on 127.0.0.1, as the
 reference's ``mp.spawn`` does, train_gan.py:331) unless it already runs inside such a launch (WORLD_SIZE set).  With N > 1
@@ -21,6 +21,11 @@ One "step" = one full D-step of the reference loop (train_gan.py:153-163): no-gr
 SimCLR-augment 3N images -> D forward -> NT-Xent + SupCon + non-saturating GAN loss [+ R1] -> backward -> [embedding
 all-gather / gradient all-reduce over RCCL] -> Adam on D.  Inputs are resident in HBM before the timed region.
 Prints ONE JSON line on rank 0.
+
+``--dump-outputs DIR`` writes what the LAST timed step of each workload returned to its caller -- the losses and the aux
+tensors of the step, and the discriminator's state_dict after its Adam update -- as ``DIR/<workload>.<name>.npy`` (float32;
+a fixed, seeded sample of the elements of every tensor larger than DUMP_MAX_ELEMS).  Weights, batch, latents and
+augmentation parameters are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -315,6 +320,35 @@ def _write_shape_table(path, name, cfg, warm_prof, marks, n_local):
         json.dump(out, f, indent=1)
 
 
+DUMP_MAX_ELEMS = 131072          # per tensor; the largest discriminator (sg2_512) comes to ~11 MB of dumps
+DUMP_MAX_BYTES = 64 << 20        # all workloads together
+
+
+def _dump_arrays(name, d_loss, aux, D):
+    """{file stem: float32 array} of one workload's last timed step (--dump-outputs), copied to the host."""
+    out = {'%s.d_loss' % name: d_loss}
+    out.update(('%s.aux.%s' % (name, k), v) for k, v in sorted(aux.items()))
+    out.update(('%s.D.%s' % (name, k), v) for k, v in D.state_dict().items())
+    arrays = {}
+    for stem, t in out.items():
+        a = t.detach().float().cpu()
+        if a.numel() > DUMP_MAX_ELEMS:           # flat sample, the same element indices in every run
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            a = a.reshape(-1)[idx]
+        arrays[stem] = a.numpy()
+    return arrays
+
+
+def _write_dumps(path, dumps):
+    arrays = {k: v for d in dumps.values() for k, v in d.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit('bench.py: --dump-outputs would write %d bytes (limit %d)' % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for stem, a in sorted(arrays.items()):
+        np.save(os.path.join(path, stem + '.npy'), a)
+
+
 def _csrc_fingerprint():
     """sha256 over the kernel sources: a committed PMC summary names the fingerprint it was collected with, so a summary
     that predates a kernel change is recognised as stale instead of being quoted."""
@@ -329,7 +363,7 @@ def _csrc_fingerprint():
 
 
 def run_config(name, args, world, rank, dev, multi, keep=None, arm=None, disarm=None, graph=None, eager_line=None,
-               overlap=None):
+               overlap=None, dump=None):
     from contrad_amd import config, ops
     from contrad_amd.augment import get_augment
     from contrad_amd.engine import (GradAllReducer, OverlappedGradReducer, d_step, d_step_stylegan2,
@@ -341,10 +375,8 @@ def run_config(name, args, world, rank, dev, multi, keep=None, arm=None, disarm=
     cfg = CONFIGS[name]
     steps = args.steps if args.steps is not None else cfg['steps']
     warmup = args.warmup if args.warmup is not None else cfg['warmup']
-    if cfg['d_reg_every'] > 1 and steps % cfg['d_reg_every']:
-        # lazy R1 (a side workload, never the top-level line): a window that is not a multiple of the period holds the wrong
-        # share of R1 steps (20 steps: 1 / 20 instead of 1 / 16, 0.7 % optimistic -- VERDICT r5): round the window UP
-        steps = -(-steps // cfg['d_reg_every']) * cfg['d_reg_every']
+    # lazy R1: the window holds steps // d_reg_every R1 steps and make_out prices exactly those; the default windows are
+    # whole periods
     batch = args.dev_local_batch or cfg['batch']
     if cfg['batch_is_global']:
         assert batch % world == 0
@@ -454,7 +486,7 @@ def run_config(name, args, world, rank, dev, multi, keep=None, arm=None, disarm=
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = t.item()
         finite = bool(torch.isfinite(d_loss).item() and torch.isfinite(aux['penalty']).item())
-        return dt, finite
+        return dt, finite, (d_loss, aux)
 
     def make_out(dt, finite, prof, nprof_steps, launch, dom, wagg_, wsteps_):
         """This workload's JSON object from one timed region (rank 0 only)."""
@@ -623,7 +655,10 @@ def run_config(name, args, world, rank, dev, multi, keep=None, arm=None, disarm=
             out = json.loads(json.dumps(eager_line))
             out["config"]["launch"] = launch
         return out, False
-    dt, finite = timed_region()
+    dt, finite, (d_loss, aux) = timed_region()
+    if dump is not None and rank == 0:      # before anything else runs the step again
+        dump.update(_dump_arrays(name, d_loss, aux, D))
+    del d_loss, aux
     if use_graph:                           # same kernels, same shapes, eager launches with the dominant kernel bracketed
         graphed[0] = None
         ops.PROFILE = []
@@ -738,6 +773,8 @@ def main():
     ap.add_argument('--dev-backend', default='nccl', choices=['nccl', 'gloo'],
                     help="dev: process-group backend.  'gloo' lets several ranks share ONE GPU (RCCL refuses that), so the "
                          "self-launch, the barriers, the MAX over ranks and the fallback order can be exercised on a 1-GPU box")
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="write the last timed step's outputs of every workload to DIR/<workload>.<name>.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -785,6 +822,14 @@ def main():
     if args.dev_local_batch:
         names = names[:1]
     results = {}
+    dumps = {}                               # workload -> arrays of the run whose line is reported (--dump-outputs)
+
+    def sink():
+        return {} if args.dump_outputs else None
+
+    def keep_dump(name, d):
+        if d:
+            dumps[name] = d
 
     def emit():
         out = results[names[0]]
@@ -803,6 +848,8 @@ def main():
                            "step_frac": r["roofline"]["step_level"]["frac"],
                            "g_step_ms": (r.get("g_step") or {}).get("ms_per_step")}
         out["summary"] = summ
+        if args.dump_outputs:
+            _write_dumps(args.dump_outputs, dumps)
         print(json.dumps(out), flush=True)
 
     # Order with more than one rank: (1) EVERY workload is run and timed with eager launches and its
@@ -824,12 +871,15 @@ def main():
     chosen = {}                                  # workload -> gradient exchange overlapped with the backward?
     fixed = {'overlap': True, 'serial': False}.get(args.exchange) if world > 1 else None
     for i, name in enumerate(names):
-        results[name], _ok = guarded(name, i == 0, graph='off' if two_phase else None, overlap=fixed)
+        d = sink()
+        results[name], _ok = guarded(name, i == 0, graph='off' if two_phase else None, overlap=fixed, dump=d)
+        keep_dump(name, d)
         chosen[name] = fixed
         if world > 1 and args.exchange == 'auto':
             # the same workload once more, eagerly, with the exchange after the backward: keep the faster of the two lines
             # (every rank must take the same decision: rank 0 decides, the others are told)
-            alt, _ok2 = guarded(name, False, graph='off', overlap=False)
+            d_alt = sink()
+            alt, _ok2 = guarded(name, False, graph='off', overlap=False, dump=d_alt)
             pick = torch.zeros(1, device=dev)
             if rank == 0:
                 a, b = results[name] or {}, alt or {}
@@ -841,20 +891,23 @@ def main():
                 both = {"overlapped": results[name]['ms_per_step'], "after_the_backward": alt['ms_per_step']}
                 if serial:
                     results[name] = alt
+                    keep_dump(name, d_alt)
                 results[name]["config"]["eager_ms_per_step_by_exchange"] = both
             chosen[name] = (not serial)
     if two_phase:
         for i, name in enumerate(names):
             if rank == 0 and "error" in (results[name] or {}):
                 continue
+            d = sink()
             try:
                 out, ok = run_config(name, args, world, rank, dev, multi, wd.keep, wd.arm, wd.disarm, graph='on',
-                                     eager_line=results[name], overlap=chosen.get(name))
+                                     eager_line=results[name], overlap=chosen.get(name), dump=d)
             except Exception as e:               # (anything else that goes wrong in the graph phase: keep the eager lines)
                 sys.stderr.write('bench.py: graph phase of %s failed (%r); keeping the eager lines\n' % (name, e))
                 break
             if rank == 0 and out is not None:
                 results[name] = out
+                keep_dump(name, d)
             if not ok:
                 break
     if multi:
