@@ -2071,8 +2071,10 @@ extern "C" int contrad_conv2d_fwd_add(const contrad_conv_desc* d, const float* x
     CONTRAD_ARG(aligned16(x, wp, workspace));
     return launch_wino23(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream);
   }
-  if (conv_c32_ok(d))   // weight-stationary kernel (conv_c32.h); (alignment is an argument error above, so the dispatch is
-                        // exactly what contrad_conv2d_path / _grid_blocks report)
+  // (without a workspace of contrad_conv2d_fwd_workspace_bytes the Winograd plans above fall through to the direct kernels
+  // below; contrad_conv2d_path / _executed_fraction describe the plan WITH that workspace, _grid_blocks either one)
+  if (conv_c32_ok(d))   // weight-stationary kernel (conv_c32.h); (alignment is an argument error above, so with the workspace
+                        // the dispatch is exactly what contrad_conv2d_path / _grid_blocks report)
     return launch_conv_c32<MODE_FWD>(d, x, wp, y, bias, addend, nullptr, slope, gain, (hipStream_t)stream);
   if (fwd_k1_ok(d)) {
     hipLaunchKernelGGL(fwd_k1_kernel, dim3((unsigned)cdivll(M, 4)), dim3(256), 0, (hipStream_t)stream, x, wp, M, d->C,
@@ -2253,7 +2255,9 @@ extern "C" int contrad_conv2d_wino_ok(const contrad_conv_desc* d, int mode) {
 extern "C" long long contrad_conv2d_wino_workspace_bytes(const contrad_conv_desc* d, int mode) {
   if (check_desc(d) || mode < 0 || mode > 2) return -22;
   if (mode == MODE_WGRAD) return wino_wgrad_ok(d) ? wino_wgrad_workspace_bytes(d) : wino22_wgrad_ok(d) ? wino22_wgrad_workspace_bytes(d) : -22;
-  return d->KH == 4 ? wino22_workspace_bytes(d) : d->stride == 2 ? wino23_workspace_bytes(d) : wino_workspace_bytes(d);
+  if (wino22_ok(d, mode)) return wino22_workspace_bytes(d);     // (the dispatch order of contrad_conv2d_wino)
+  if (wino23_ok(d, mode)) return wino23_workspace_bytes(d);
+  return wino_ok(d, mode) ? wino_workspace_bytes(d) : -22;      // -22 exactly when contrad_conv2d_wino_ok says 0
 }
 
 extern "C" int contrad_conv2d_wino_wgrad(const contrad_conv_desc* d, const float* x, const float* gy, float* dwp,
@@ -2299,6 +2303,7 @@ extern "C" int contrad_conv2d_wino44_ok(const contrad_conv_desc* d, int mode) {
 
 extern "C" long long contrad_conv2d_wino44_workspace_bytes(const contrad_conv_desc* d) {
   if (check_desc(d)) return -22;
+  if (!wino44_ok(d, MODE_FWD) && !wino44_ok(d, MODE_DGRAD)) return -22;     // (neither mode runs: no workspace to size)
   return wino44_workspace_bytes(d);
 }
 

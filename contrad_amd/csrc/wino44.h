@@ -1,5 +1,7 @@
-// Winograd F(4x4, 3x3) in fp32 on v_mfma_f32_32x32x2_f32 for the 3x3 stride-1 pad-1 layers with maps >= 8x8 (included by
-// igemm.hip after wino.h).
+// Winograd F(4x4, 3x3) in fp32 on v_mfma_f32_32x32x2_f32 for the 3x3 stride-1 pad-1 layers (included by igemm.hip after wino.h).
+// Supported shapes (wino44_ok; the statement of include/contrad_hip.h and ops.conv2d_wino): H and W powers of two, either square
+// 4x4 / 8x8 / 16x16, or W >= 32 and H >= 16; input and output channels multiples of 32 (the 4x4 maps and odd numbers of 32-wide
+// cout blocks: wino44n.h); input and filter leading dimensions multiples of 4.
 //
 // Same layers as wino.h (reference: models/gan/sndcgan.py:91-109, models/gan/stylegan2/layers.py:95-123,
 // discriminator.py:60-76; forward and input gradient of F.conv2d), one step further down the multiply-add count:

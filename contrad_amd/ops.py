@@ -190,11 +190,18 @@ def conv2d_dgrad(gy, wp, x_shape, KH, KW, stride, pad, act_ref=None, slope=1.0, 
 
 def conv2d_wino(mode, inp, wp, C, K, bias=None, ref=None, slope=1.0, gain=1.0, out=None, k4s2=False, f44=False, k3s2=False):
     """Winograd kernels on ANY shape ``contrad_conv2d_wino_ok`` accepts (conv2d_fwd / conv2d_dgrad pick them by themselves for
-    launches that fill the chip).  3x3 stride 1 pad 1 (F(2x2,3x3), csrc/wino.h; ``f44``: F(4x4,3x3), csrc/wino44.h, maps of
-    16x16 and larger) -- mode 0: inp = x (N,H,W,C) -> y (N,H,W,K);
+    launches that fill the chip).  3x3 stride 1 pad 1 (F(2x2,3x3), csrc/wino.h; ``f44``: F(4x4,3x3), csrc/wino44.h) -- mode 0:
+    inp = x (N,H,W,C) -> y (N,H,W,K);
     mode 1: inp = gy (N,H,W,K) -> dx (N,H,W,C) -- or, ``k4s2``, 4x4 stride 2 pad 1 (F(2x2,2x2) on the four phases,
     csrc/wino22.h): mode 0: x (N,H,W,C) -> y (N,H/2,W/2,K); mode 1: gy (N,Ho,Wo,K) -> dx (N,2Ho,2Wo,C) -- or, ``k3s2``, 3x3 stride 2
-    pad 0 on an odd map (F(2x2,2x2) on the phases, zero planes skipped, csrc/wino23.h): mode 0 only, x (N,2G+1,2G+1,C) -> y (N,G,G,K)."""
+    pad 0 on an odd map (F(2x2,2x2) on the phases, zero planes skipped, csrc/wino23.h): mode 0 only, x (N,2G+1,2G+1,C) -> y (N,G,G,K).
+
+    Supported 3x3 stride-1 pad-1 shapes (the statement of include/contrad_hip.h and csrc/wino44.h):
+      F(2x2,3x3): H and W powers of two >= 4, any aspect ratio; input channels a multiple of 16, output channels of 64.
+      F(4x4,3x3): H and W powers of two, either square 4x4 / 8x8 / 16x16, or W >= 32 and H >= 16; input and output channels
+                  multiples of 32.
+      (Both: input and filter leading dimensions multiples of 4, block-relative offsets below 2^31 bytes.)  ``in`` / ``out``
+      are "input" / "output" of the call: x / y in mode 0, gy / dx in mode 1.  Other shapes raise RuntimeError."""
     _chk(inp, 'inp'); _chk(wp, 'wp'); _chk(bias, 'bias'); _chk(ref, 'ref')
     N, Hi, Wi, _ = inp.shape
     co = K if mode == 0 else C
@@ -227,6 +234,8 @@ def conv2d_wino(mode, inp, wp, C, K, bias=None, ref=None, slope=1.0, gain=1.0, o
         if lib().raw('contrad_conv2d_wino_ok')(ctypes.byref(d), mode) != 1:
             raise RuntimeError('contrad_hip: shape not supported by the Winograd kernels')
         nbytes = lib().raw('contrad_conv2d_wino_workspace_bytes')(ctypes.byref(d), mode)
+    if nbytes < 0:
+        raise RuntimeError('contrad_hip: the Winograd workspace query rejected the shape (%d)' % nbytes)
     ws = _workspace(nbytes, inp.device)
     lib().call('contrad_conv2d_wino44' if f44 else 'contrad_conv2d_wino', ctypes.byref(d), mode, _p(inp), _p(wp), _p(bias), _p(ref), _p(out),
                float(slope), float(gain), _p(ws), ctypes.c_longlong(nbytes), _stream())
@@ -248,6 +257,8 @@ def conv2d_wino_wgrad(x, gy, ldw=None, out=None, dbias=None):
     if lib().raw('contrad_conv2d_wino_ok')(ctypes.byref(d), 2) != 1:
         raise RuntimeError('contrad_hip: shape not supported by the Winograd weight-gradient kernel')
     nbytes = lib().raw('contrad_conv2d_wino_workspace_bytes')(ctypes.byref(d), 2)
+    if nbytes < 0:
+        raise RuntimeError('contrad_hip: the Winograd workspace query rejected the shape (%d)' % nbytes)
     ws = _workspace(nbytes, x.device)
     lib().call('contrad_conv2d_wino_wgrad', ctypes.byref(d), _p(x), _p(gy), _p(out), _p(dbias), _p(ws),
                ctypes.c_longlong(ws.numel() * 4), _stream())

@@ -76,8 +76,16 @@ int contrad_conv2d_dgrad_ws(const contrad_conv_desc* d, const float* gy, const f
                             const float* act_ref, float slope, float gain, float* workspace,
                             long long workspace_bytes, contrad_stream_t stream);
 
-/* Winograd F(2x2, 3x3) in exact fp32 (csrc/wino.h) for 3x3 stride-1 pad-1 layers on power-of-two maps >= 4x4 whose input
- * channels are a multiple of 16 and output channels a multiple of 64: 2.25x fewer multiply-adds than the direct kernels,
+/* Supported shapes of the 3x3 stride-1 pad-1 Winograd kernels (contrad_conv2d_wino_ok / contrad_conv2d_wino44_ok; the same
+ * statement stands in ops.conv2d_wino and csrc/wino44.h):
+ *   F(2x2, 3x3): H and W powers of two >= 4, any aspect ratio; input channels a multiple of 16, output channels of 64;
+ *   F(4x4, 3x3): H and W powers of two, either square 4x4 / 8x8 / 16x16, or W >= 32 and H >= 16; input and output channels
+ *                multiples of 32;
+ *   both: input and filter leading dimensions multiples of 4, block-relative offsets below 2^31 bytes.  "Input" / "output" are
+ *   those of the call: x / y in mode 0, gy / dx in mode 1.  contrad_conv2d_wino_workspace_bytes (every mode) and
+ *   contrad_conv2d_wino44_workspace_bytes (when neither mode is accepted) return -22 exactly where the *_ok query says 0.
+ *
+ * Winograd F(2x2, 3x3) in exact fp32 (csrc/wino.h) for 3x3 stride-1 pad-1 layers on the maps above: 2.25x fewer multiply-adds than the direct kernels,
  * fp32 round-off class results (rel-L2 3 - 6e-7 against fp64; F.conv2d of the reference reaches cuDNN's Winograd-class
  * kernels the same way: models/gan/sndcgan.py:91-109, models/gan/stylegan2/layers.py:115-121).  contrad_conv2d_fwd_add /
  * contrad_conv2d_dgrad_ws choose it by themselves for launches of about one item (64 tiles x 64 output channels) per CU or
@@ -100,9 +108,9 @@ int contrad_conv2d_wino(const contrad_conv_desc* d, int mode, const float* in, c
                         const float* ref, float* out, float slope, float gain, float* workspace,
                         long long workspace_bytes, contrad_stream_t stream);
 
-/* Winograd F(4x4, 3x3) in fp32 (csrc/wino44.h) for the same 3x3 stride-1 pad-1 layers on power-of-two maps >= 16x16 whose
- * input channels and output channels are multiples of 32 (output channels in whole 64-wide blocks: wino44_kernel; an odd number
- * of 32-wide blocks -- StyleGAN2_512's 32 -> 32 channel layers -- csrc/wino44n.h): 2.25 multiply-adds per output instead of 4
+/* Winograd F(4x4, 3x3) in fp32 (csrc/wino44.h) for the same 3x3 stride-1 pad-1 layers on the maps stated above (output
+ * channels in whole 64-wide blocks: wino44_kernel; an odd number of 32-wide blocks -- StyleGAN2_512's 32 -> 32 channel
+ * layers -- and the 4x4 maps: csrc/wino44n.h): 2.25 multiply-adds per output instead of 4
  * (F(2x2, 3x3)) or 9 (direct); standard interpolation points (0, +-1, +-2, inf), round-off rel-L2 1 - 5e-6 against fp64 (the
  * contract of this path is 1e-3; reference as above: F.conv2d of models/gan/sndcgan.py:91-109, stylegan2/layers.py:115-121).
  * contrad_conv2d_fwd_add / contrad_conv2d_dgrad_ws choose it ahead of F(2x2, 3x3) for launches of a full round of its items
@@ -133,7 +141,10 @@ int contrad_conv2d_tile(const contrad_conv_desc* d, int mode, int* bm, int* bn);
  * 8 = F(2x2, 2x2) on the phases of the 4x4 stride-2 layers (wino22_kernel<mode> / wino22_wgrad_kernel), 9 = Winograd F(4x4, 3x3)
  * (wino44_kernel<mode>, modes 0 and 1; with a workspace), 10 = F(2x2, 2x2) on the phases of a 3x3 stride-2 pad-0 layer with the zero
  * planes skipped (wino23_kernel, mode 0; with a workspace), 11 = F(4x4, 3x3) with 32-wide output-channel blocks (wino44n_kernel<mode>:
- * output channels not a multiple of 64, and the 4x4 maps; with a workspace);  negative = bad descriptor.  Profiling aid. */
+ * output channels not a multiple of 64, and the 4x4 maps; with a workspace);  negative = bad descriptor.  Profiling aid.
+ * Workspace assumption: this and contrad_conv2d_executed_fraction describe the plan of a call that passes a workspace of
+ * contrad_conv2d_{fwd,dgrad,wgrad}_workspace_bytes.  contrad_conv2d_fwd_add / contrad_conv2d_dgrad_ws with a NULL (or
+ * smaller) workspace skip paths 7 - 11 and run the direct kernels instead (contrad_conv2d_dgrad: never split-K either). */
 int contrad_conv2d_path(const contrad_conv_desc* d, int mode);
 /* Share of the layer's nominal multiply-adds (2*N*Ho*Wo*K*C*KH*KW, the count every roofline here is quoted on, padding
  * taps included as in the reference's dense layer) that the kernel actually issues: 1 except on pixel-major tiles (path

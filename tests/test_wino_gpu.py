@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_ref64 as R
 from contrad_amd import ops
 from contrad_amd._lib import lib
 
@@ -433,7 +434,7 @@ PLANNED = [(1536, 16, 128), (1536, 8, 256), (1536, 4, 512), (48, 128, 128), (48,
 
 
 @pytest.mark.parametrize('shape', PLANNED)
-def test_the_plan_takes_winograd_at_the_baseline_shapes_and_matches_torch(shape):
+def test_the_plan_takes_winograd_at_the_baseline_shapes_and_matches_torch(shape, margin):
     """conv2d_fwd / conv2d_dgrad (the calls the models make) at full size: the path query says Winograd, and the first and
     last images match PyTorch-CPU."""
     N, H, C = shape
@@ -478,9 +479,29 @@ def test_the_plan_takes_winograd_at_the_baseline_shapes_and_matches_torch(shape)
     F.conv2d(xs2.permute(0, 3, 1, 2), w0, None, padding=1).backward(ys2.permute(0, 3, 1, 2))
     dws = ops.unpack_weight(ops.conv2d_wino_wgrad(xd[:nb], y[:nb]), K, C, 3, 3).cpu()
     assert rel(dws, w0.grad) < TIGHT
+    # every image of the full launch against float64 (tests/conv_ref64.py): forward, data gradient, weight and bias gradient
+    wd = w.to(dev)
+    _whole_batch(margin, 'planned F(4x4,3x3) fwd', y, R.fwd(xd, wd, b.to(dev), 1, 1, 0.1, 1.0), TIGHT44, TIGHT44_L2)
+    _whole_batch(margin, 'planned F(4x4,3x3) dgrad', dx, R.dgrad(y, wd, (H, H), 1, 1, xd, 0.1, 1.0), TIGHT44, TIGHT44_L2)
+    refw, refb = R.wgrad(xd, y, 3, 3, 1, 1)
+    _whole_batch(margin, 'planned F(3x3,2x2) wgrad', ops.unpack_weight(dwp, K, C, 3, 3), refw, TIGHT, TIGHT_L2)
+    _whole_batch(margin, 'planned F(3x3,2x2) dbias', dbias, refb, TIGHT, TIGHT_L2)
 
 
-def test_the_plan_takes_winograd_for_the_32_channel_layers_at_512():
+# rel-L2 bounds of the whole-batch comparisons against float64 (observed worst on an MI355X: 9.0e-7 -- the strided 3x3
+# forward --; 4.9e-6 -- the F(4x4, 3x3) forward at 1536 x 16^2 x 128 and kin)
+TIGHT_L2 = 4e-6
+TIGHT44_L2 = 2e-5
+
+
+def _whole_batch(margin, name, out, ref, tmax, tl2):
+    emax, el2 = R.errors(out, ref)
+    assert emax < TOL, (name, emax)
+    margin(name + ' max-norm', emax, tmax)
+    margin(name + ' rel-L2', el2, tl2)
+
+
+def test_the_plan_takes_winograd_for_the_32_channel_layers_at_512(margin):
     """StyleGAN2_512's 32 -> 32 channel 3x3 layers (3N = 48 images at 512^2): forward and data gradient on F(4x4, 3x3) with 32-wide
     cout blocks (csrc/wino44n.h), the weight gradient on its dedicated direct kernel; computed here on 4 images."""
     N, H, C, K = 4, 512, 32, 32
@@ -504,6 +525,15 @@ def test_the_plan_takes_winograd_for_the_32_channel_layers_at_512():
     dx = ops.conv2d_dgrad(y, wp, (N, H, H, C), 3, 3, 1, 1, act_ref=xd, slope=0.2, gain=1.0)
     refd = F.conv_transpose2d(y[sel].cpu().permute(0, 3, 1, 2), w, padding=1).permute(0, 2, 3, 1) * torch.where(x[sel] > 0, 1.0, 0.2)
     assert rel(dx[sel].cpu(), refd) < TIGHT44
+    # every image against float64; the weight gradient (direct engine) too
+    wd = w.to(dev)
+    _whole_batch(margin, 'planned F(4x4,3x3) 32-wide fwd', y, R.fwd(xd, wd, b.to(dev), 1, 1, 0.2, 1.0), TIGHT44, TIGHT44_L2)
+    _whole_batch(margin, 'planned F(4x4,3x3) 32-wide dgrad', dx, R.dgrad(y, wd, (H, H), 1, 1, xd, 0.2, 1.0), TIGHT44, TIGHT44_L2)
+    dbias = torch.empty(K, device=dev)
+    dwp = ops.conv2d_wgrad(xd, y, 3, 3, 1, 1, dbias=dbias)
+    refw, refb = R.wgrad(xd, y, 3, 3, 1, 1)
+    _whole_batch(margin, 'planned 32-channel direct wgrad', ops.unpack_weight(dwp, K, C, 3, 3), refw, TIGHT, TIGHT_L2)
+    _whole_batch(margin, 'planned 32-channel direct dbias', dbias, refb, TIGHT, TIGHT_L2)
 
 
 # the blurred 3x3 stride-2 layers of StyleGAN2_512 at 3N = 48 that the plan gives to csrc/wino23.h: (N, G, C, K)
@@ -511,7 +541,7 @@ PLANNED23 = [(48, 256, 32, 64), (48, 128, 64, 128), (48, 64, 128, 256), (48, 32,
 
 
 @pytest.mark.parametrize('shape', PLANNED23)
-def test_the_plan_takes_the_strided_3x3_winograd_forward_at_the_baseline_shapes(shape):
+def test_the_plan_takes_the_strided_3x3_winograd_forward_at_the_baseline_shapes(shape, margin):
     """conv2d_fwd (the call ResBlock.conv2 makes, with the skip path's addend) at full size: path 10, 25 / 36 of the dense
     products, first and last image against PyTorch-CPU; data and weight gradient of the same layer stay on the direct engine."""
     N, G, C, K = shape
@@ -532,3 +562,13 @@ def test_the_plan_takes_the_strided_3x3_winograd_forward_at_the_baseline_shapes(
     sel = [0, N - 1]
     ref = F.leaky_relu(F.conv2d(x[sel].permute(0, 3, 1, 2), w, b, stride=2), 0.2).permute(0, 2, 3, 1) + add[sel]
     assert rel(y[sel].cpu(), ref) < TIGHT
+    # every image against float64; the data and weight gradient of the same layer (direct engine) too
+    xd, wd, gy = x.to(dev), w.to(dev), y.clone()
+    _whole_batch(margin, 'planned strided 3x3 fwd', y, R.fwd(xd, wd, b.to(dev), 2, 0, 0.2, 1.0, add.to(dev)), TIGHT, TIGHT_L2)
+    dx = ops.conv2d_dgrad(gy, wp, (N, H, H, C), 3, 3, 2, 0, act_ref=xd, slope=0.2, gain=1.0)
+    _whole_batch(margin, 'planned strided 3x3 direct dgrad', dx, R.dgrad(gy, wd, (H, H), 2, 0, xd, 0.2, 1.0), TIGHT, TIGHT_L2)
+    dbias = torch.empty(K, device=dev)
+    dwp = ops.conv2d_wgrad(xd, gy, 3, 3, 2, 0, dbias=dbias)
+    refw, refb = R.wgrad(xd, gy, 3, 3, 2, 0)
+    _whole_batch(margin, 'planned strided 3x3 direct wgrad', ops.unpack_weight(dwp, K, C, 3, 3), refw, TIGHT, TIGHT_L2)
+    _whole_batch(margin, 'planned strided 3x3 direct dbias', dbias, refb, TIGHT, TIGHT_L2)
