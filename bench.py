@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """Headline benchmark: discriminator-step images/sec (ContraD, SimCLR aug) on synthetic batches, random-init weights.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c10_b512|sg2_32|sg2_512|all] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--config c10_b512|sg2_32|sg2_512|all] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the K timed steps of the headline
+workload and its JSON line.  ``--full`` adds every side measurement, each of which costs runs of its own: the two
+StyleGAN2 workloads (``--config`` then defaults to ``all``), the dominant conv kernel's ``roofline`` (eager steps bracketed
+by HIP events after a replayed window, PMC figures from ``profiles/``), the generator step (``g_step``) and, at N = 1, the
+CPU baselines (``cpu_baseline``).  ``--dump-outputs`` also defaults ``--config`` to ``all``: the dump is the record two
+builds are compared on, so it holds every workload's outputs (the timing side measurements still need ``--full``).
 
 ``--gpus N`` (N > 1) spawns one process per GPU itself (re-exec under ``torch.distributed.run`` on 127.0.0.1, as the
 reference's ``mp.spawn`` does, train_gan.py:331) unless it already runs inside such a launch (WORLD_SIZE set).  With N > 1
@@ -14,8 +21,9 @@ Workloads (BASELINE.json configs):
   sg2_32    StyleGAN2 small32 + ContraD, 32x32, batch 64 per GPU, R1 every step (train_stylegan2.py --no_lazy) (configs[3])
   sg2_512   StyleGAN2_512 + ContraD, 512x512, batch 16 per GPU, simclr_hq aug, lazy R1 every 16th step
             (train_stylegan2_contraD.py semantics: separate N and 2N discriminator calls) (configs[4])
-With ``--config all`` (the default) the two StyleGAN2 workloads run after the headline one and are reported under
-``"other_configs"`` of the same single JSON line, each with its own ``roofline`` (and ``cpu_baseline`` at N=1).
+With ``--config all`` (the default under ``--full`` or ``--dump-outputs``) the two StyleGAN2 workloads run after the
+headline one and are reported under ``"other_configs"`` of the same single JSON line; with ``--full`` each has its own
+``roofline`` (and ``cpu_baseline`` at N=1).
 
 One "step" = one full D-step of the reference loop (train_gan.py:153-163): no-grad G forward for N fakes ->
 SimCLR-augment 3N images -> D forward -> NT-Xent + SupCon + non-saturating GAN loss [+ R1] -> backward -> [embedding
@@ -461,7 +469,7 @@ def run_config(name, args, world, rank, dev, multi, keep=None, arm=None, disarm=
         _write_shape_table(args.shape_table, name, cfg, warm_prof, marks, n_local)
     del warm_prof
     dom_name = max(wagg.items(), key=lambda kv: kv[1][0])[0] if wagg else None
-    ops.PROFILE_ONLY = dom_name
+    ops.PROFILE_ONLY = dom_name           # (also without --full: an eager timed region is the same with and without it)
     peak_box = [None]                     # peak HBM of the D-step (read before the generator-step side measurement)
 
     def timed_region():
@@ -488,11 +496,8 @@ def run_config(name, args, world, rank, dev, multi, keep=None, arm=None, disarm=
         finite = bool(torch.isfinite(d_loss).item() and torch.isfinite(aux['penalty']).item())
         return dt, finite, (d_loss, aux)
 
-    def make_out(dt, finite, prof, nprof_steps, launch, dom, wagg_, wsteps_):
-        """This workload's JSON object from one timed region (rank 0 only)."""
-        ms = dt / steps * 1e3
-        value = global_batch * steps / dt
-        graph_run = launch == 'hipGraph replay'
+    def make_roofline(dt, value, prof, nprof_steps, graph_run, dom, wagg_, wsteps_):
+        """The dominant kernel's roofline and the step-level pricing of one timed region (--full, rank 0 only)."""
         # dominant kernel = the conv-engine instance with the largest summed device time (chosen on the warm-up
         # steps); its launches in the timed region are the `achieved` figure
         if dom is None:                                             # --warmup 0: everything was bracketed
@@ -563,6 +568,12 @@ def run_config(name, args, world, rank, dev, multi, keep=None, arm=None, disarm=
                                    "flop_per_image": fpi,
                                    "note": "whole step (every kernel, every gap) priced at SURVEY's nominal FLOPs per "
                                            "image; frac scales it by the issued / nominal share of the conv launches"}}
+        return roofline
+
+    def make_out(dt, finite, prof, nprof_steps, launch, dom, wagg_, wsteps_):
+        """This workload's JSON object from one timed region (rank 0 only)."""
+        ms = dt / steps * 1e3
+        value = global_batch * steps / dt
         out = {"metric": "discriminator-step images/sec (ContraD, SimCLR aug)", "value": round(value, 1),
                "unit": "images/sec", "n_gpus": world, "steps": steps, "warmup": warmup,
                "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
@@ -575,8 +586,9 @@ def run_config(name, args, world, rank, dev, multi, keep=None, arm=None, disarm=
                                                                    else "after the backward (flat collectives)"),
                           "rccl_ranks": dist.get_world_size() if multi else 1,
                           "backend": dist.get_backend() if multi else None,
-                          "peak_hbm_gib": round((peak_box[0] or torch.cuda.max_memory_allocated(dev)) / 2 ** 30, 2)},
-               "roofline": roofline}
+                          "peak_hbm_gib": round((peak_box[0] or torch.cuda.max_memory_allocated(dev)) / 2 ** 30, 2)}}
+        if args.full:
+            out["roofline"] = make_roofline(dt, value, prof, nprof_steps, launch == 'hipGraph replay', dom, wagg_, wsteps_)
         if cfg['d_reg_every'] > 1:
             out["config"]["r1_steps_in_window"] = steps // cfg['d_reg_every']
         return out
@@ -659,7 +671,7 @@ def run_config(name, args, world, rank, dev, multi, keep=None, arm=None, disarm=
     if dump is not None and rank == 0:      # before anything else runs the step again
         dump.update(_dump_arrays(name, d_loss, aux, D))
     del d_loss, aux
-    if use_graph:                           # same kernels, same shapes, eager launches with the dominant kernel bracketed
+    if use_graph and args.full:             # same kernels, same shapes, eager launches with the dominant kernel bracketed
         graphed[0] = None
         ops.PROFILE = []
         for _ in range(max(3, steps // 4)):
@@ -674,7 +686,7 @@ def run_config(name, args, world, rank, dev, multi, keep=None, arm=None, disarm=
 
     # ---- generator step, reported separately -- never part of `value` ----
     g_step = None
-    if not args.no_g_step and not multi:
+    if args.full and not args.no_g_step and not multi:
         try:
             from contrad_amd.training.gan.contrad import loss_G_fn
             opt_G = FusedAdam(G.parameters(), lr=opt['lr'], betas=tuple(opt['beta']))
@@ -750,9 +762,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=None, help='timed steps (default: 20 / 10 / 16 for c10_b512 / sg2_32 / sg2_512)')
     ap.add_argument('--warmup', type=int, default=None, help='untimed warm-up steps (default: 5 / 3 / 3)')
-    ap.add_argument('--config', default='all', choices=sorted(CONFIGS) + ['all'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-g-step', action='store_true', help='skip the separately reported generator-step timing')
+    ap.add_argument('--config', default=None, choices=sorted(CONFIGS) + ['all'],
+                    help='workload(s) to time (default: c10_b512, the headline; all with --full or --dump-outputs)')
+    ap.add_argument('--full', action='store_true',
+                    help='add every side measurement: the StyleGAN2 workloads (unless --config says otherwise), the '
+                         'roofline of each, the generator step and, at N = 1, the CPU baselines')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baselines')
+    ap.add_argument('--no-g-step', action='store_true', help='--full: skip the separately reported generator-step timing')
     ap.add_argument('--shape-table', default=None,
                     help='write the per-(kernel, layer shape) table of the conv engine (from the bracketed warm-up) here')
     ap.add_argument('--graph', default='on', choices=['on', 'off'],
@@ -818,7 +834,8 @@ def main():
             import contrad_amd.engine as _eng
             _eng.FORCE_DIST = True
 
-    names = ['c10_b512', 'sg2_32', 'sg2_512'] if args.config == 'all' else [args.config]
+    config = args.config or ('all' if args.full or args.dump_outputs else 'c10_b512')
+    names = ['c10_b512', 'sg2_32', 'sg2_512'] if config == 'all' else [config]
     if args.dev_local_batch:
         names = names[:1]
     results = {}
@@ -843,10 +860,11 @@ def main():
         for n in names:
             r = results.get(n)
             if r and "error" not in r:
-                summ[n] = {"value": r["value"], "ms_per_step": r["ms_per_step"], "steps": r["steps"],
-                           "dominant_kernel": r["roofline"]["kernel"], "frac": r["roofline"]["frac"],
-                           "step_frac": r["roofline"]["step_level"]["frac"],
-                           "g_step_ms": (r.get("g_step") or {}).get("ms_per_step")}
+                summ[n] = {"value": r["value"], "ms_per_step": r["ms_per_step"], "steps": r["steps"]}
+                if "roofline" in r:              # --full
+                    summ[n].update(dominant_kernel=r["roofline"]["kernel"], frac=r["roofline"]["frac"],
+                                   step_frac=r["roofline"]["step_level"]["frac"],
+                                   g_step_ms=(r.get("g_step") or {}).get("ms_per_step"))
         out["summary"] = summ
         if args.dump_outputs:
             _write_dumps(args.dump_outputs, dumps)
@@ -917,7 +935,7 @@ def main():
         except Exception as e:                   # (after a failed capture the process group may be unusable: still print)
             sys.stderr.write('bench.py: process-group shutdown failed (%r)\n' % (e,))
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             for name in names:
                 if "error" in results[name]:
                     continue

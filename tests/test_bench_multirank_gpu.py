@@ -24,7 +24,7 @@ def _run(extra, env_extra=None, timeout=600, config='c10_b512', exchange='overla
 
 
 def test_two_gloo_ranks_eager_line():
-    r, lines = _run(['--graph', 'off'])
+    r, lines = _run(['--graph', 'off', '--full'])
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1, r.stdout[-2000:]
     out = json.loads(lines[0])

@@ -1,14 +1,14 @@
-# Round-2 evidence run: default bench (all configs + CPU baselines), kernel traces and PMC passes per config.
+# Round-2 evidence run: `bench.py --full` (all configs + CPU baselines), kernel traces and PMC passes per config.
 # Each profiler run sits under its own timeout; PMC passes carry --kernel-trace only.
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r02p
 rm -rf $O; mkdir -p $O
 cd $R
-timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp
 for c in c10_b512 sg2_32 sg2_512; do
   case $c in c10_b512) S="--steps 5 --warmup 3";; sg2_32) S="--steps 5 --warmup 3";; sg2_512) S="--steps 16 --warmup 2";; esac
-  timeout 300 rocprofv3 --kernel-trace -d $O -o ${c}_kt -- python $R/bench.py --config $c $S --no-cpu-baseline > $O/${c}_kt.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace -d $O -o ${c}_kt -- python $R/bench.py --config $c $S --full --no-cpu-baseline > $O/${c}_kt.log 2>&1
   python $R/tools/rocpd_summary.py $O/${c}_kt_results.db > $O/${c}_kernel_trace.txt 2>&1
   grep -h '^{' $O/${c}_kt.log > $O/${c}_under_rocprof.json
   rm -f $O/${c}_kt_results.db

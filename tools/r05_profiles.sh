@@ -2,7 +2,7 @@
 # rocprofv3 kernel trace of `bench.py --config <c> --no-g-step` (D-step launches only: the generator-step side
 # measurement would mix other shapes into the same kernel names) joined with the bench's own shape table
 # (tools/rocpd_rows.py -> one row per (kernel, layer shape) with GFLOP per launch), and the PMC passes (own runs,
-# --kernel-trace only beside the counters), then the default bench (all configs + CPU baselines).  Usage: PMC_CONFIGS="c10_b512 sg2_32 sg2_512" bash tools/r05_profiles.sh [tag]
+# --kernel-trace only beside the counters), then `bench.py --full` (all configs + CPU baselines).  Usage: PMC_CONFIGS="c10_b512 sg2_32 sg2_512" bash tools/r05_profiles.sh [tag]
 R=$GRAFT_REPO_ROOT
 TAG=${1:-r05}
 O=$R/gpurun_out/${TAG}p
@@ -14,7 +14,7 @@ fi
 cd /tmp && export TMPDIR=/tmp
 for c in ${KT_CONFIGS-c10_b512 sg2_32 sg2_512}; do
   case $c in c10_b512) S="--steps 5 --warmup 3";; sg2_32) S="--steps 5 --warmup 3";; sg2_512) S="--steps 16 --warmup 2";; esac
-  timeout 400 rocprofv3 --kernel-trace -d $O -o ${c}_kt -- python $R/bench.py --config $c $S --no-cpu-baseline --no-g-step --shape-table $O/${c}_shapes.json > $O/${c}_kt.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace -d $O -o ${c}_kt -- python $R/bench.py --config $c $S --full --no-cpu-baseline --no-g-step --shape-table $O/${c}_shapes.json > $O/${c}_kt.log 2>&1
   python $R/tools/rocpd_summary.py $O/${c}_kt_results.db > $O/${c}_kernel_trace.txt 2>&1
   python $R/tools/rocpd_rows.py $O/${c}_kt_results.db $O/${c}_shapes.json > $O/${c}_rows.txt 2>&1
   grep -h '^{' $O/${c}_kt.log > $O/${c}_under_rocprof.json
@@ -35,7 +35,7 @@ done
 # one rank of the 2- / 4- / 8-GPU headline config on one GPU (per-rank batch 256 / 128 / 64; every collective on a 1-rank RCCL
 # group): kernel trace + per-shape rows, then the un-profiled step time
 for B in ${RANK_BATCHES-256 128 64}; do
-  timeout 300 rocprofv3 --kernel-trace -d $O -o b${B}_kt -- python $R/bench.py --config c10_b512 --dev-local-batch $B --force-dist --steps 20 --warmup 3 --no-cpu-baseline --no-g-step --shape-table $O/b${B}_shapes.json > $O/b${B}_kt.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace -d $O -o b${B}_kt -- python $R/bench.py --config c10_b512 --dev-local-batch $B --force-dist --steps 20 --warmup 3 --full --no-cpu-baseline --no-g-step --shape-table $O/b${B}_shapes.json > $O/b${B}_kt.log 2>&1
   python $R/tools/rocpd_summary.py $O/b${B}_kt_results.db > $O/b${B}_kernel_trace.txt 2>&1
   python $R/tools/rocpd_rows.py $O/b${B}_kt_results.db $O/b${B}_shapes.json > $O/b${B}_rows.txt 2>&1
   rm -f $O/b${B}_kt_results.db
@@ -43,7 +43,7 @@ for B in ${RANK_BATCHES-256 128 64}; do
 done
 cd $R
 if [ -z "$SKIP_BENCH" ]; then     # after the counter passes: its roofline.traffic then comes from THIS run's PMC summaries
-  timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
+  timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
 fi
 mkdir -p $O/profiles
 for c in ${KT_CONFIGS-c10_b512 sg2_32 sg2_512}; do
