@@ -342,6 +342,7 @@ int check(int R, int D, int N, int mode) {
   CONTRAD_ARG(R > 0 && D > 0 && D <= 256 && N > 0);
   CONTRAD_ARG(mode == 0 || mode == 1);
   CONTRAD_ARG(mode == 0 ? (R == 2 * N) : (R == 3 * N));
+  CONTRAD_ARG(mode == 0 || N >= 2);  // SupCon: an anchor's positives are the N - 1 other fakes (N = 1: 0 / 0 in the reference)
   return 0;
 }
 float anchor_coef(int N, int mode) { return mode == 0 ? 1.f / (2.f * N) : 1.f / (float)N; }

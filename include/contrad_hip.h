@@ -175,7 +175,8 @@ int contrad_conv2d_wgrad(const contrad_conv_desc* d, const float* x, const float
 /* Scratch for the column-split partials of either call (the R x R work is spread over ~256 blocks; the
  * per-split (max, sum, target) triples / dZ slabs are merged in a fixed order -> deterministic). */
 long long contrad_contrast_workspace_bytes(int R, int D);
-/* z[R,D] row-normalised. Writes lse[R], rowloss[R] (scratch) and loss[0] = mean anchor loss. */
+/* z[R,D] row-normalised, D <= 256. Writes lse[R], rowloss[R] (scratch) and loss[0] = mean anchor loss.
+ * Mode 1 needs N >= 2 (with one fake an anchor has no positive); both calls return -22 otherwise. */
 int contrad_contrast_fwd(const float* z, int R, int D, int N, int mode, float inv_temp, float* lse,
                          float* rowloss, float* loss, float* workspace, long long workspace_bytes,
                          contrad_stream_t stream);
