@@ -9,7 +9,7 @@
 //   params[n][10]    = gray mask, [11] = blur mask (used by the blur kernels only)
 //   params[n][12..14]= cutout mask, cutout row centre, cutout column centre (used by the cutout kernel only)
 //
-// Small images (3*H*W*4 B <= 64 KiB: CIFAR 32x32, up to 64x64): one block per image, the image lives in LDS
+// Small images (3*H*W*4 B <= 64 KiB: CIFAR 32x32, square up to 73x73): one block per image, the image lives in LDS
 // between stages so the per-channel contrast mean costs no extra HBM pass.
 // Large images (AFHQ 512x512): a statistics pass (gather [+HSV] -> channel sums, the source stays hot in the
 // 256 MiB Infinity Cache) followed by an apply pass that recomputes the gather; optional separable Gaussian
@@ -413,10 +413,13 @@ __device__ __forceinline__ Axis axis_sample(float scale, float bias, int idx, in
   a.v0 = (unsigned)a.p0 < (unsigned)size; a.v1 = (unsigned)a.p1 < (unsigned)size;
   return a;
 }
-// candidate output indices whose (unclamped) source coordinate lies within (src-1, src+1), widened by 2
+// candidate output indices whose (unclamped) source coordinate lies within (src-1, src+1), widened by 2.  Every index
+// when the map is not increasing, or when its unclamped coordinates leave [-0.5, size-0.5] (a crop reaching past the
+// border, e.g. a zoom-out): reflected coordinates then land far from the run of their unreflected ones.  The sampler's
+// crops stay inside the image (their end coordinates are s/2 inside the border) and keep the short run.
 __device__ __forceinline__ void axis_inverse_range(float scale, float bias, int src, int size, int& lo, int& hi) {
-  if (!(scale > 1e-6f)) { lo = 0; hi = size - 1; return; }
   const float c0 = scale * 0.5f + (float)size * (bias + 1.f - scale) * 0.5f - 0.5f;
+  if (!(scale > 1e-6f) || c0 < -0.5f || scale * (float)(size - 1) + c0 > (float)size - 0.5f) { lo = 0; hi = size - 1; return; }
   lo = (int)floorf(((float)src - 1.f - c0) / scale) - 2;
   hi = (int)ceilf(((float)src + 1.f - c0) / scale) + 2;
   lo = lo < 0 ? 0 : lo;
@@ -625,7 +628,7 @@ extern "C" int contrad_simclr_augment_bwd(const float* x, const float* params, c
   hipStream_t s = (hipStream_t)stream;
   const size_t smem = (size_t)(7 * H * W + H * H + W * W) * sizeof(float);
   AugArgs a{x, nullptr, params, B, H, W, contrast_first, has_contrast};
-  if (smem <= 64 * 1024) {   // small-image path (<= 44x44): one block per image, everything in LDS
+  if (smem <= 64 * 1024) {   // small-image path (square: <= 42x42): one block per image, everything in LDS
     hipLaunchKernelGGL(simclr_small_bwd_kernel, dim3(B), dim3(256), smem, s, a, grad_out, grad_in);
     CONTRAD_CHECK_LAUNCH();
     return 0;
