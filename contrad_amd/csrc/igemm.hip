@@ -2029,7 +2029,7 @@ int launch_wino_wgrad(const contrad_conv_desc* d, const float* x, const float* g
 
 }  // namespace
 
-extern "C" int contrad_abi_version(void) { return 2; }
+extern "C" int contrad_abi_version(void) { return 3; }
 
 extern "C" long long contrad_conv2d_fwd_workspace_bytes(const contrad_conv_desc* d) {
   if (check_desc(d)) return -22;

@@ -77,6 +77,48 @@ class TinyHead(nn.Module):
         self.l2 = mk((1, d_hidden))
 
 
+class _LinHeadFn(torch.autograd.Function):
+    """logits = feats @ weight.T + bias on the lin-eval head kernels (csrc/linhead.hip: launches 1 + 2, logits only);
+    the backward takes the weight / bias gradients from launch 3 in its no-update form."""
+
+    @staticmethod
+    def forward(ctx, feats, weight, bias):
+        from ... import ops
+        ctx.save_for_backward(feats, weight)
+        ctx.has_bias = bias is not None
+        return ops.linhead_fwd(feats, weight, bias)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        from ... import ops
+        feats, weight = ctx.saved_tensors
+        g = g.contiguous()
+        gw = gb = gf = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gw, gb = torch.empty_like(weight), g.new_empty(weight.shape[0])
+            ops.linhead_wgrad_sgd(feats, g, grad_weight=gw, grad_bias=gb)
+        if ctx.needs_input_grad[0]:
+            gf = g @ weight                 # off the lin-eval path (the features are detached there)
+        return gf, gw, (gb if ctx.has_bias else None)
+
+
+class LinearWrapper(nn.Linear):
+    """The reference's ``LinearWrapper`` (base.py:56-61): an ``nn.Linear`` (state-dict keys ``weight``, ``bias``; default
+    init drawn on the host) whose forward takes and ignores ``y``.  Installed as ``D.linear`` for linear evaluation."""
+
+    def __init__(self, in_features, out_features, bias=True):
+        super().__init__(in_features, out_features, bias)
+
+    def forward(self, inputs, y=None):
+        if not inputs.is_cuda:
+            return F.linear(inputs, self.weight, self.bias)
+        lead = inputs.shape[:-1]
+        flat = inputs.reshape(-1, inputs.shape[-1]).float()
+        if flat.stride(-1) != 1:
+            flat = flat.contiguous()
+        return _LinHeadFn.apply(flat, self.weight, self.bias).view(*lead, self.out_features)
+
+
 def make_projection(n_features, d_hidden, d_project, spectral):
     """nn.Sequential(Linear, LeakyReLU(0.1), Linear) parameter layout (base.py:92-101): entries '0' and '2'."""
     mk = SNParams if spectral else PlainParams
@@ -89,6 +131,25 @@ class BaseDiscriminator(nn.Module):
 
     d_penul = None
 
+    # A ``LinearWrapper`` assigned to ``D.linear`` (test_lineval.py:142 of the reference) replaces the logit head in the
+    # module tree and the state dict.  The trunk's merged head launches still consume the stock ``TinyHead``, so it is
+    # kept beside the tree (moved with the module, never saved, never trained).
+    def __setattr__(self, name, value):
+        if name == 'linear' and isinstance(value, LinearWrapper) and isinstance(self._modules.get('linear'), TinyHead):
+            self.__dict__['_stock_head'] = self._modules['linear']
+        super().__setattr__(name, value)
+
+    def _head(self):
+        """The TinyHead the trunk launches read: ``self.linear`` unless a LinearWrapper took its place."""
+        lin = self._modules['linear']
+        return self.__dict__['_stock_head'] if isinstance(lin, LinearWrapper) else lin
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        if '_stock_head' in self.__dict__:
+            self.__dict__['_stock_head']._apply(fn, *args, **kwargs)
+        return out
+
     def _run(self, inputs, sg_linear, finetuning, want_features):
         raise NotImplementedError
 
@@ -96,11 +157,16 @@ class BaseDiscriminator(nn.Module):
                 finetuning=False, sg_linear=False):
         if y is not None:
             raise NotImplementedError('class-conditional heads (n_classes > 1) are not used by get_architecture')
+        lin = self._modules.get('linear')
+        replaced = isinstance(lin, LinearWrapper)           # linear evaluation: D(x) = linear(penultimate(x)), base.py:128
+        want_features = penultimate or replaced
         if getattr(self, '_lazy_projections', False):       # (networks whose heads are separate launches)
-            output, project, project2, features = self._run(inputs, sg_linear, finetuning, penultimate,
+            output, project, project2, features = self._run(inputs, sg_linear, finetuning, want_features,
                                                             want_proj=(projection or projection2))
         else:
-            output, project, project2, features = self._run(inputs, sg_linear, finetuning, penultimate)
+            output, project, project2, features = self._run(inputs, sg_linear, finetuning, want_features)
+        if replaced:
+            output = lin(features.detach() if (sg_linear or finetuning) else features)
         aux = {}
         if penultimate:
             aux['penultimate'] = features

@@ -44,8 +44,8 @@ class _DPlan(object):
         dh, dp = D.d_hidden, D.d_project
         self.dh, self.dp = dh, dp
         convs = [D.main[2 * i] for i in range(7)]
-        heads1 = [D.linear.l1, D.projection[0], D.projection2[0]]
-        heads2 = [D.linear.l2, D.projection[2], D.projection2[2]]
+        heads1 = [D._head().l1, D.projection[0], D.projection2[0]]
+        heads2 = [D._head().l2, D.projection[2], D.projection2[2]]
         self.layers = convs + heads1 + heads2
         T_head = self.hb * self.wb
         self.specs = []
@@ -275,8 +275,8 @@ class D_SNDCGAN(BaseDiscriminator):
     def _ordered_params(self):
         out = []
         for m in ([self.main[2 * i] for i in range(7)] +
-                  [self.linear.l1, self.projection[0], self.projection2[0],
-                   self.linear.l2, self.projection[2], self.projection2[2]]):
+                  [self._head().l1, self.projection[0], self.projection2[0],
+                   self._head().l2, self.projection[2], self.projection2[2]]):
             out += [m.weight_orig, m.bias]
         return out
 

@@ -66,7 +66,7 @@ class D_SNResNet18(BaseDiscriminator):
         for li in range(1, 5):
             for blk in getattr(self, 'layer%d' % li):
                 mods += [blk.conv1, blk.conv2] + list(blk.shortcut)
-        return mods + [self.linear.l1, self.linear.l2, self.projection[0], self.projection[2], self.projection2[0],
+        return mods + [self._head().l1, self._head().l2, self.projection[0], self.projection[2], self.projection2[0],
                        self.projection2[2]]
 
     def _trunk(self, images, wp):
@@ -122,11 +122,11 @@ class D_SNResNet18(BaseDiscriminator):
         def lin(m, t, K, slope):
             return A.ConvBiasActFn.apply(t, wp[m], m.bias, (K, 1, 1, 1, 0), slope, 1.0)
 
-        h_l, h_p, h_p2 = lin(self.linear.l1, fd, dh, _SLOPE), lin(self.projection[0], f4, dh, _SLOPE), \
+        h_l, h_p, h_p2 = lin(self._head().l1, fd, dh, _SLOPE), lin(self.projection[0], f4, dh, _SLOPE), \
             lin(self.projection2[0], f4, dh, _SLOPE)
         if getattr(self, '_record_activations', False):
             self._recorded_heads = tuple(t.detach().reshape(B, dh) for t in (h_l, h_p, h_p2))
-        out = lin(self.linear.l2, h_l, 1, 1.0).view(B, 1)
+        out = lin(self._head().l2, h_l, 1, 1.0).view(B, 1)
         proj = lin(self.projection[2], h_p, dp, 1.0).view(B, dp)
         proj2 = lin(self.projection2[2], h_p2, dp, 1.0).view(B, dp)
         return out, proj, proj2, (feat if want_features else None)

@@ -453,13 +453,13 @@ class ResidualDiscriminatorP(BaseDiscriminator):
         w_last = F.pad(m.weight, (0, 0, 0, 0, 0, cpad - (self.c_last_in + 1)))     # zero rows for the pad channels
         idx['last'] = add(w_last, m.weight.shape[0], cpad, 9, m.scale)
         dh, dp, T = self.d_hidden, self.d_project, 16
-        idx['l1'] = add(self.linear.l1.weight, dh, 512, T, 1.0)
+        idx['l1'] = add(self._head().l1.weight, dh, 512, T, 1.0)
         groups.append((self.n_features, 2 * dh))                                    # projection.0 | projection2.0
         gm = len(groups) - 1
         add(self.projection[0].weight, dh, 512, T, 1.0, gm, 0)
         add(self.projection2[0].weight, dh, 512, T, 1.0, gm, dh)
         idx['p0q0'] = gm
-        idx['l2'] = add(self.linear.l2.weight, 1, dh, 1, 1.0)
+        idx['l2'] = add(self._head().l2.weight, 1, dh, 1, 1.0)
         idx['p2'] = add(self.projection[2].weight, dp, dh, 1, 1.0)
         idx['q2'] = add(self.projection2[2].weight, dp, dh, 1, 1.0)
         meta = A.PackMeta(entries, groups)
@@ -567,9 +567,9 @@ class ResidualDiscriminatorP(BaseDiscriminator):
         g1 = (1, 1, 1, 1, 0)
         # (first-order call: each head weight has exactly one gradient producer -> it may start the data-parallel
         # exchange of its packed gradient itself, _xch)
-        h_l = A.ConvBiasActFn.apply(feat_d, wp[idx['l1']], self.linear.l1.bias, (dh,) + g1[1:], _HEAD_SLOPE, 1.0,
+        h_l = A.ConvBiasActFn.apply(feat_d, wp[idx['l1']], self._head().l1.bias, (dh,) + g1[1:], _HEAD_SLOPE, 1.0,
                                     *self._xch(idx['l1'], fused))
-        out = A.ConvBiasActFn.apply(h_l, wp[idx['l2']], self.linear.l2.bias, (1,) + g1[1:], 1.0, 1.0,
+        out = A.ConvBiasActFn.apply(h_l, wp[idx['l2']], self._head().l2.bias, (1,) + g1[1:], 1.0, 1.0,
                                     *self._xch(idx['l2'], fused)).view(B, 1)
         h_pq = proj = proj2 = None
         if want_proj or rec is not None:

@@ -889,3 +889,83 @@ def bn_relu_bwd(dy2d, x2d, stats, count, gamma, beta, eps, reduce_fn=None):
     lib().call('contrad_bn_relu_bwd_apply', _p(dy2d), _p(x2d), _p(dx), ctypes.c_longlong(M), K, ld, _p(stats),
                float(count), _p(gamma), _p(beta), float(eps), _p(out), _stream())
     return dx, local[1], local[0]
+
+
+# ---- linear-evaluation head (csrc/linhead.hip) ----
+def linhead_plan(N, K, C):
+    """(K-splits, classes per thread of the logits kernel, 64-row tiles) contrad_linhead_fwd takes for (N, K, C)."""
+    s, ct, rt = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    lib().call('contrad_linhead_plan', int(N), int(K), int(C), ctypes.byref(s), ctypes.byref(ct), ctypes.byref(rt))
+    return s.value, ct.value, rt.value
+
+
+def _chk_labels(y, N, C):
+    if y.dtype != torch.int64 or y.dim() != 1 or y.numel() != N or not y.is_contiguous():
+        raise RuntimeError('contrad_hip: labels must be a contiguous int64 vector of %d entries' % N)
+    if not y.is_cuda:           # host labels can be checked before the launch; device labels are handled by the kernel
+        if N and (int(y.min()) < 0 or int(y.max()) >= C):
+            raise RuntimeError('contrad_hip: label outside [0, %d)' % C)
+
+
+def linhead_fwd(feats, weight, bias, y=None, dl_scale=None, logits=None, dlogits=None, meters=None, want_logits=True,
+                want_dlogits=False):
+    """Launches 1 + 2 of the head: logits = feats @ weight.T + bias and, with labels ``y`` (int64; a CPU tensor is
+    range-checked here and uploaded), the cross-entropy meters and ``dlogits = (softmax - onehot) * dl_scale``
+    (default 1 / N).  ``meters`` (4 float64 on the device: loss sum, top-1 hits, top-5 hits, samples) is added to in
+    place.  Returns (logits or None, dlogits or None)."""
+    _chk(feats, 'feats'); _chk(weight, 'weight'); _chk(bias, 'bias')
+    N, K = feats.shape
+    C = weight.shape[0]
+    if weight.dim() != 2 or weight.shape[1] != K or not weight.is_contiguous() or not 1 <= C <= 128:
+        raise RuntimeError('contrad_hip: weight must be a contiguous (C, %d) matrix with 1 <= C <= 128' % K)
+    if bias is not None and (bias.numel() != C or not bias.is_contiguous()):
+        raise RuntimeError('contrad_hip: bias must hold %d contiguous floats' % C)
+    if y is not None:
+        _chk_labels(y, N, C)
+        y = y.to(feats.device)
+    elif want_dlogits or dlogits is not None or meters is not None:
+        raise RuntimeError('contrad_hip: loss, meters and dlogits need labels')
+    if meters is not None and (meters.dtype != torch.float64 or not meters.is_cuda or meters.numel() != 4
+                               or not meters.is_contiguous()):
+        raise RuntimeError('contrad_hip: meters must be 4 contiguous CUDA float64 values')
+    if logits is None and want_logits:
+        logits = torch.empty(N, C, device=feats.device, dtype=torch.float32)
+    if dlogits is None and want_dlogits:
+        dlogits = torch.empty(N, C, device=feats.device, dtype=torch.float32)
+    for t, nm in ((logits, 'logits'), (dlogits, 'dlogits')):
+        _chk(t, nm)
+        if t is not None and (tuple(t.shape) != (N, C) or not t.is_contiguous()):
+            raise RuntimeError('contrad_hip: %s must be a contiguous (%d, %d) tensor' % (nm, N, C))
+    ws = _workspace(lib().raw('contrad_linhead_workspace_bytes')(N, K, C), feats.device)
+    lib().call('contrad_linhead_fwd', _p(feats), _ld(feats), _p(weight), _p(bias), _p(y), N, K, C,
+               float(1.0 / N if dl_scale is None else dl_scale), _p(logits), _p(dlogits), _p(meters), _p(ws), _stream())
+    if meters is not None:
+        torch.autograd.graph.increment_version(meters)
+    return logits, dlogits
+
+
+def linhead_wgrad_sgd(feats, dlogits, weight=None, bias=None, lr=None, grad_weight=None, grad_bias=None):
+    """Launch 3: gradW = dlogits.T @ feats, gradb = dlogits.sum(0); with ``lr`` (a 1-element CUDA float tensor)
+    ``weight`` / ``bias`` take the SGD step in place; ``grad_weight`` / ``grad_bias`` (optional) receive the gradients."""
+    _chk(feats, 'feats'); _chk(dlogits, 'dlogits'); _chk(weight, 'weight'); _chk(bias, 'bias'); _chk(lr, 'lr')
+    _chk(grad_weight, 'grad_weight'); _chk(grad_bias, 'grad_bias')
+    N, K = feats.shape
+    C = dlogits.shape[1]
+    if tuple(dlogits.shape) != (N, C) or not dlogits.is_contiguous() or not 1 <= C <= 128:
+        raise RuntimeError('contrad_hip: dlogits must be a contiguous (%d, C) tensor with 1 <= C <= 128' % N)
+    for t, nm, shape in ((weight, 'weight', (C, K)), (grad_weight, 'grad_weight', (C, K)), (bias, 'bias', (C,)),
+                         (grad_bias, 'grad_bias', (C,))):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous()):
+            raise RuntimeError('contrad_hip: %s must be a contiguous %s tensor' % (nm, shape))
+    if lr is not None and weight is None:
+        raise RuntimeError('contrad_hip: the SGD form needs the weight')
+    if lr is None and grad_weight is None and grad_bias is None:
+        raise RuntimeError('contrad_hip: nothing to compute (neither lr nor a gradient output)')
+    upd = lr is not None
+    lib().call('contrad_linhead_wgrad_sgd', _p(feats), _ld(feats), _p(dlogits), N, K, C, _p(lr),
+               _p(weight if upd else None), _p(bias if upd else None), _p(grad_weight), _p(grad_bias), _stream())
+    if upd:
+        torch.autograd.graph.increment_version(weight)
+        if bias is not None:
+            torch.autograd.graph.increment_version(bias)
+    return grad_weight, grad_bias

@@ -469,6 +469,34 @@ long long contrad_nhwc_dot_workspace_bytes(int N, long long HW, int C);
 int contrad_nhwc_dot(const float* a, const float* b, float* out, int N, long long HW, int C, int b_per_channel,
                      float* workspace, long long workspace_bytes, contrad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Linear evaluation head (csrc/linhead.hip): softmax regression on penultimate features F[N,K] (row stride ldf),
+ * weights W[C,K] (dense), bias b[C], labels y[N] (int64), 1 <= C <= 128.  Replaces, per iteration of the reference's
+ * lin-eval loop (test_lineval.py:79-94: model.linear, CrossEntropyLoss, accuracy(topk=(1,5)), three .item() reads,
+ * zero_grad, backward, SGD step; evaluate/classifier.py:11-25,47-67 for the test pass), about twenty launches and
+ * three pipeline drains by three launches (two for evaluation) and no host synchronisation.  No float atomics: every
+ * sum has a fixed order, results are bitwise repeatable.
+ * ---------------------------------------------------------------------------------------------- */
+/* Bytes of the workspace of contrad_linhead_fwd (16-byte aligned, caller-allocated); < 0 on bad arguments. */
+long long contrad_linhead_workspace_bytes(int N, int K, int C);
+/* The launch form of contrad_linhead_fwd for (N, K, C), a pure function of them: number of K-splits whose partial
+ * sums are added in order, classes per thread of the logits kernel (ceil(C / 16)), 64-row tiles.  Any output may be NULL. */
+int contrad_linhead_plan(int N, int K, int C, int* splits, int* classes_per_thread, int* row_tiles);
+/* Launch 1 + 2.  logits[N,C] = F W^T + b (b, logits may be NULL).  With labels: per row the max-subtracted
+ * log-sum-exp, loss_n = lse_n - logits[n,y_n], dlogits[N,C] = (softmax - onehot) * dl_scale (NULL: skipped, the
+ * evaluation form), and meters4 (device float64, NULL ok) += {sum_n loss_n, top-1 hits, top-5 hits, N}; the label is
+ * a top-k hit when fewer than k logits are strictly greater than its logit.  A row whose label is outside [0, C)
+ * counts as loss 0, no hit, zero gradient (and still as a sample).  y == NULL: logits only. */
+int contrad_linhead_fwd(const float* F, int ldf, const float* W, const float* b, const long long* y, int N, int K,
+                        int C, float dl_scale, float* logits, float* dlogits, double* meters4, void* ws,
+                        contrad_stream_t stream);
+/* Launch 3.  gW[c,k] = sum_n dlogits[n,c] F[n,k], gb[c] = sum_n dlogits[n,c] (n ascending); lr_dev != NULL:
+ * W -= lr_dev[0] * gW, b -= lr_dev[0] * gb in place (b may be NULL), the learning rate read from DEVICE memory so that
+ * a captured graph follows the MultiStepLR milestones; gradW / gradb != NULL: the gradients are written out. */
+int contrad_linhead_wgrad_sgd(const float* F, int ldf, const float* dlogits, int N, int K, int C,
+                              const float* lr_dev, float* W, float* b, float* gradW, float* gradb,
+                              contrad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
