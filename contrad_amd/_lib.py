@@ -72,6 +72,36 @@ class DemodBatch(ctypes.Structure):
     _fields_ = [('n', ctypes.c_int), ('B', ctypes.c_int), ('layers', DemodLayer * MODCONV_MAX_LAYERS)]
 
 
+class ContrastProblem(ctypes.Structure):
+    """contrad_contrast_problem."""
+    _fields_ = [('z', ctypes.c_void_p), ('R', ctypes.c_int), ('D', ctypes.c_int), ('N', ctypes.c_int),
+                ('mode', ctypes.c_int), ('inv_temp', ctypes.c_float), ('lse', ctypes.c_void_p),
+                ('rowloss', ctypes.c_void_p), ('loss', ctypes.c_void_p), ('grad_scale', ctypes.c_void_p),
+                ('dz', ctypes.c_void_p), ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_longlong)]
+
+
+class L2normProblem(ctypes.Structure):
+    """contrad_l2norm_problem."""
+    _fields_ = [('u', ctypes.c_void_p), ('z', ctypes.c_void_p), ('inv_norm', ctypes.c_void_p), ('dz', ctypes.c_void_p),
+                ('du', ctypes.c_void_p), ('ldu', ctypes.c_int), ('R', ctypes.c_int), ('D', ctypes.c_int),
+                ('accumulate', ctypes.c_int), ('zero_rows', ctypes.c_int)]
+
+
+FILTER_MAX_JOBS = 16
+
+
+class FilterJob(ctypes.Structure):
+    """contrad_filter_job."""
+    _fields_ = [('wp', ctypes.c_void_p), ('U', ctypes.c_void_p), ('kind', ctypes.c_int), ('mode', ctypes.c_int),
+                ('C', ctypes.c_int), ('K', ctypes.c_int), ('ldw', ctypes.c_int)]
+
+
+class FilterBatch(ctypes.Structure):
+    """contrad_filter_batch."""
+    _fields_ = [('n', ctypes.c_int), ('jobs', FilterJob * FILTER_MAX_JOBS),
+                ('block_start', ctypes.c_int * (FILTER_MAX_JOBS + 1))]
+
+
 _CTYPES = {
     'int': ctypes.c_int,
     'float': ctypes.c_float,

@@ -229,6 +229,18 @@ __global__ void bn_relu_bwd_apply_kernel(const float* __restrict__ dy, const flo
   }
 }
 
+// running statistics of channel c from its batch sums (shared by the two kernels below: one arithmetic)
+__device__ __forceinline__ void bn_running_update_channel(float sum, float sumsq, float count, int c,
+                                                          const float* __restrict__ conv_bias, float momentum,
+                                                          float* __restrict__ running_mean, float* __restrict__ running_var) {
+  const float mean = sum / count;
+  const float var = fmaxf(sumsq / count - mean * mean, 0.f);
+  const float unbiased = (count > 1.f) ? var * (count / (count - 1.f)) : var;
+  const float m = mean + (conv_bias ? conv_bias[c] : 0.f);
+  running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
+  running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+}
+
 __global__ void bn_running_update_kernel(const float* __restrict__ stats, float count, int K,
                                          const float* __restrict__ conv_bias, float momentum,
                                          float* __restrict__ running_mean, float* __restrict__ running_var,
@@ -236,12 +248,48 @@ __global__ void bn_running_update_kernel(const float* __restrict__ stats, float 
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;      // (nn.BatchNorm2d's counter: was an ATen launch per layer)
   if (c >= K) return;
-  const float mean = stats[c] / count;
-  const float var = fmaxf(stats[K + c] / count - mean * mean, 0.f);
-  const float unbiased = (count > 1.f) ? var * (count / (count - 1.f)) : var;
-  const float m = mean + (conv_bias ? conv_bias[c] : 0.f);
-  running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-  running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+  bn_running_update_channel(stats[c], stats[K + c], count, c, conv_bias, momentum, running_mean, running_var);
+}
+
+// colstats_reduce_kernel (two statistics) and bn_running_update_kernel in one launch: a block sums {sum, sumsq} of 8
+// channels over the partial rows -- per entry exactly colstats_reduce_kernel's lanes, chains and order, so `stats` has
+// the same bits -- and the threads that hold a channel's sum then update its running statistics from the two totals.
+__global__ __launch_bounds__(256) void bn_stats_reduce_update_kernel(const float* __restrict__ partial, int nblocks, int K,
+                                                                     float* __restrict__ stats, float count,
+                                                                     const float* __restrict__ conv_bias, float momentum,
+                                                                     float* __restrict__ running_mean,
+                                                                     float* __restrict__ running_var,
+                                                                     long long* __restrict__ num_batches_tracked) {
+  __shared__ float red[CSR_P][CSR_E + 1];
+  __shared__ float tot[CSR_E];
+  const int ex = threadIdx.x % CSR_E, py = threadIdx.x / CSR_E;
+  const int c = blockIdx.x * (CSR_E / 2) + (ex & (CSR_E / 2 - 1));
+  const int e = (ex / (CSR_E / 2)) * K + c;      // entry of the [2][K] statistics
+  const int E = 2 * K;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  if (c < K) {
+    int b = py;
+    for (; b + 3 * CSR_P < nblocks; b += 4 * CSR_P) {
+      s0 += partial[(size_t)b * E + e];
+      s1 += partial[(size_t)(b + CSR_P) * E + e];
+      s2 += partial[(size_t)(b + 2 * CSR_P) * E + e];
+      s3 += partial[(size_t)(b + 3 * CSR_P) * E + e];
+    }
+    for (; b < nblocks; b += CSR_P) s0 += partial[(size_t)b * E + e];
+  }
+  red[py][ex] = (s0 + s1) + (s2 + s3);
+  __syncthreads();
+  if (py == 0 && c < K) {
+    float s = 0.f;
+#pragma unroll
+    for (int r = 0; r < CSR_P; ++r) s += red[r][ex];
+    stats[e] = s;
+    tot[ex] = s;
+  }
+  __syncthreads();
+  if (blockIdx.x == 0 && threadIdx.x == 0 && num_batches_tracked) *num_batches_tracked += 1;
+  if (py == 0 && ex < CSR_E / 2 && c < K)
+    bn_running_update_channel(tot[ex], tot[ex + CSR_E / 2], count, c, conv_bias, momentum, running_mean, running_var);
 }
 
 // ---- discriminator GAN losses on the logits d[3N] (rows [0,N) real view 1, [2N,3N) fakes) ----
@@ -345,6 +393,9 @@ int colstats_plan(long long M, int* rows_per_block, int* nblocks) {
 
 }  // namespace
 
+static int colstats_partials(const float* x, long long M, int K, int ld, int with_sq, float* workspace, int* nb_out,
+                             hipStream_t s);
+
 extern "C" long long contrad_colstats_workspace_bytes(long long M, int K, int with_sq) {
   int rpb, nb;
   colstats_plan(M, &rpb, &nb);
@@ -356,10 +407,24 @@ extern "C" int contrad_colstats(const float* x, long long M, int K, int ld, int 
                                 contrad_stream_t stream) {
   CONTRAD_ARG(x && out && workspace && M > 0 && K > 0 && ld >= K);
   CONTRAD_ARG(workspace_bytes >= contrad_colstats_workspace_bytes(M, K, with_sq));
+  hipStream_t s = (hipStream_t)stream;
+  int nb = 0;
+  const int rc = colstats_partials(x, M, K, ld, with_sq, workspace, &nb, s);
+  if (rc) return rc;
+  const int nstat = with_sq ? 2 : 1;
+  hipLaunchKernelGGL(colstats_reduce_kernel, dim3(cdiv(nstat * K, CSR_E)), dim3(256), 0, s, workspace, nb, nstat, K,
+                     out, accumulate);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+// the per-block partial sums of contrad_colstats (shared by it and contrad_bn_batch_stats)
+static int colstats_partials(const float* x, long long M, int K, int ld, int with_sq, float* workspace, int* nb_out,
+                             hipStream_t s) {
   int rpb, nb;
   colstats_plan(M, &rpb, &nb);
+  *nb_out = nb;
   dim3 grid(nb, cdiv(K, 64 * COLS_PER_THREAD));
-  hipStream_t s = (hipStream_t)stream;
   const bool vec = (K & 3) == 0 && (ld & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)workspace & 15) == 0;
   if (vec) {
     const int cq = K / 4;
@@ -381,9 +446,21 @@ extern "C" int contrad_colstats(const float* x, long long M, int K, int ld, int 
     hipLaunchKernelGGL(colstats_partial_kernel<false>, grid, dim3(256), 0, s, x, M, K, ld, rpb, workspace);
   }
   CONTRAD_CHECK_LAUNCH();
-  const int nstat = with_sq ? 2 : 1;
-  hipLaunchKernelGGL(colstats_reduce_kernel, dim3(cdiv(nstat * K, CSR_E)), dim3(256), 0, s, workspace, nb, nstat, K,
-                     out, accumulate);
+  return 0;
+}
+
+extern "C" int contrad_bn_batch_stats(const float* x, long long M, int K, int ld, float* stats, const float* conv_bias,
+                                      float momentum, float* running_mean, float* running_var,
+                                      long long* num_batches_tracked, float* workspace, long long workspace_bytes,
+                                      contrad_stream_t stream) {
+  CONTRAD_ARG(x && stats && workspace && running_mean && running_var && M > 0 && K > 0 && ld >= K);
+  CONTRAD_ARG(workspace_bytes >= contrad_colstats_workspace_bytes(M, K, 1));
+  hipStream_t s = (hipStream_t)stream;
+  int nb = 0;
+  int rc = colstats_partials(x, M, K, ld, 1, workspace, &nb, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(bn_stats_reduce_update_kernel, dim3(cdiv(K, CSR_E / 2)), dim3(256), 0, s, workspace, nb, K, stats,
+                     (float)M, conv_bias, momentum, running_mean, running_var, num_batches_tracked);
   CONTRAD_CHECK_LAUNCH();
   return 0;
 }

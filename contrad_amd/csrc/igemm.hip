@@ -999,11 +999,11 @@ int launch_wino44n_inst(const wino44::Args& a, hipStream_t stream) {
 
 template <int MODE>
 int launch_wino44(const contrad_conv_desc* d, const float* in, const float* wp, const float* bias, const float* ref,
-                  float* out, float slope, float gain, float* U, hipStream_t stream) {
+                  float* out, float slope, float gain, float* U, hipStream_t stream, const float* Uprep = nullptr) {
   wino44::Args a = wino44_args(d, MODE);
-  a.x = in; a.U = U; a.y = out; a.bias = bias; a.ref = ref; a.slope = slope; a.gain = gain;
+  a.x = in; a.U = Uprep ? Uprep : U; a.y = out; a.bias = bias; a.ref = ref; a.slope = slope; a.gain = gain;
   const int quads = (a.Cin / 4) * a.Cout;
-  hipLaunchKernelGGL(wino44::wino44_filter_kernel<MODE>, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
+  if (!Uprep) hipLaunchKernelGGL(wino44::wino44_filter_kernel<MODE>, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
   CONTRAD_CHECK_LAUNCH();
   if (a.n32)
     return a.BW == 34 ? launch_wino44n_inst<MODE, 34>(a, stream) : a.BW == 18 ? launch_wino44n_inst<MODE, 18>(a, stream)
@@ -1076,11 +1076,11 @@ int launch_wino22_inst(const wino22::Args& a, int blocks, hipStream_t stream) {
 
 template <int MODE>
 int launch_wino22(const contrad_conv_desc* d, const float* in, const float* wp, const float* bias, const float* ref,
-                  float* out, float slope, float gain, float* U, hipStream_t stream) {
+                  float* out, float slope, float gain, float* U, hipStream_t stream, const float* Uprep = nullptr) {
   wino22::Args a = wino22_args(d, MODE);
-  a.x = in; a.U = U; a.y = out; a.bias = bias; a.ref = ref; a.slope = slope; a.gain = gain;
+  a.x = in; a.U = Uprep ? Uprep : U; a.y = out; a.bias = bias; a.ref = ref; a.slope = slope; a.gain = gain;
   const int quads = 4 * (a.Cin / 4) * a.Cout;
-  hipLaunchKernelGGL(wino22::wino22_filter_kernel<MODE>, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
+  if (!Uprep) hipLaunchKernelGGL(wino22::wino22_filter_kernel<MODE>, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
   CONTRAD_CHECK_LAUNCH();
   const int l0 = cdiv(a.NTB, 8) * a.NKB * (MODE == MODE_DGRAD ? 4 : 1);
   const int blocks = 8 * std::min(WINO_CUS / 8, l0);
@@ -1145,11 +1145,11 @@ int launch_wino23_inst(const wino23::Args& a, hipStream_t stream) {
 }
 
 int launch_wino23(const contrad_conv_desc* d, const float* in, const float* wp, const float* bias, const float* ref,
-                  float* out, float slope, float gain, float* U, hipStream_t stream) {
+                  float* out, float slope, float gain, float* U, hipStream_t stream, const float* Uprep = nullptr) {
   wino23::Args a = wino23_args(d);
-  a.x = in; a.U = U; a.y = out; a.bias = bias; a.ref = ref; a.slope = slope; a.gain = gain;
+  a.x = in; a.U = Uprep ? Uprep : U; a.y = out; a.bias = bias; a.ref = ref; a.slope = slope; a.gain = gain;
   const int quads = 4 * (a.Cin / 4) * a.Cout;
-  hipLaunchKernelGGL(wino23::wino23_filter_kernel, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
+  if (!Uprep) hipLaunchKernelGGL(wino23::wino23_filter_kernel, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
   CONTRAD_CHECK_LAUNCH();
   const int nraw = cdiv(2 * a.NIMG * (2 * a.TH + 1) * (2 * a.TW + 1), 256);
   if (nraw <= 5) return launch_wino23_inst<5>(a, stream);
@@ -1246,18 +1246,69 @@ long long wino_wgrad_workspace_bytes(const contrad_conv_desc* d) {
 
 template <int MODE>
 int launch_wino(const contrad_conv_desc* d, const float* in, const float* wp, const float* bias, const float* ref,
-                float* out, float slope, float gain, float* U, hipStream_t stream) {
+                float* out, float slope, float gain, float* U, hipStream_t stream, const float* Uprep = nullptr) {
   static const hipError_t attr = hipFuncSetAttribute((const void*)wino::wino_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                      wino::LDS_DWORDS * 4);
   if (attr != hipSuccess) return (int)attr;
   wino::Args a = wino_args(d, MODE);
-  a.x = in; a.U = U; a.y = out; a.bias = bias; a.ref = ref; a.slope = slope; a.gain = gain;
+  a.x = in; a.U = Uprep ? Uprep : U; a.y = out; a.bias = bias; a.ref = ref; a.slope = slope; a.gain = gain;
   const int quads = (a.Cin / 4) * a.Cout;
-  hipLaunchKernelGGL(wino::wino_filter_kernel<MODE>, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
+  if (!Uprep) hipLaunchKernelGGL(wino::wino_filter_kernel<MODE>, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
   CONTRAD_CHECK_LAUNCH();
   hipLaunchKernelGGL(wino::wino_kernel<MODE>, dim3(wino_grid(a)), dim3(512), wino::LDS_DWORDS * 4, stream, a);
   CONTRAD_CHECK_LAUNCH();
   return 0;
+}
+
+// ---------------- every transformed filter of a network in one launch (contrad_conv2d_filter_prep) ----------------
+// Block b serves the job j with block_start[j] <= b < block_start[j + 1]; its threads do what the threads of the job's own
+// *_filter_kernel do (the filter_quad functions of wino.h, wino22.h, wino23.h, wino44.h: the same arithmetic, the same bits).
+enum { FILTER_WINO = 7, FILTER_WINO22 = 8, FILTER_WINO44 = 9, FILTER_WINO23 = 10 };
+
+__global__ __launch_bounds__(256) void filter_prep_kernel(const contrad_filter_batch b) {
+  int j = 0;
+  while (j + 1 < b.n && (int)blockIdx.x >= b.block_start[j + 1]) ++j;
+  const contrad_filter_job& q = b.jobs[j];
+  const int idx = ((int)blockIdx.x - b.block_start[j]) * 256 + (int)threadIdx.x;
+  switch (q.kind * 2 + q.mode) {
+    case FILTER_WINO * 2 + MODE_FWD: wino::filter_quad<MODE_FWD>(q.wp, q.U, q.C, q.K, q.ldw, idx); break;
+    case FILTER_WINO * 2 + MODE_DGRAD: wino::filter_quad<MODE_DGRAD>(q.wp, q.U, q.C, q.K, q.ldw, idx); break;
+    case FILTER_WINO22 * 2 + MODE_FWD: wino22::filter_quad<MODE_FWD>(q.wp, q.U, q.C, q.K, q.ldw, idx); break;
+    case FILTER_WINO22 * 2 + MODE_DGRAD: wino22::filter_quad<MODE_DGRAD>(q.wp, q.U, q.C, q.K, q.ldw, idx); break;
+    case FILTER_WINO44 * 2 + MODE_FWD: wino44::filter_quad<MODE_FWD>(q.wp, q.U, q.C, q.K, q.ldw, idx); break;
+    case FILTER_WINO44 * 2 + MODE_DGRAD: wino44::filter_quad<MODE_DGRAD>(q.wp, q.U, q.C, q.K, q.ldw, idx); break;
+    case FILTER_WINO23 * 2 + MODE_FWD: wino23::filter_quad(q.wp, q.U, q.C, q.K, q.ldw, idx); break;
+    default: break;
+  }
+}
+
+// threads of a job's transform (one per four input channels x one output channel [x phase]); 0 = unknown kind / mode
+long long filter_threads(int kind, int mode, int C, int K) {
+  if (mode != MODE_FWD && mode != MODE_DGRAD) return 0;
+  const long long quads = (long long)((mode == MODE_FWD ? C : K) / 4) * (mode == MODE_FWD ? K : C);
+  if (kind == FILTER_WINO || kind == FILTER_WINO44) return quads;
+  if (kind == FILTER_WINO22) return 4 * quads;
+  if (kind == FILTER_WINO23) return mode == MODE_FWD ? 4 * quads : 0;
+  return 0;
+}
+
+// The transformed filter the planned path of (d, mode) reads when the call has its workspace: the order of
+// contrad_conv2d_fwd_add / contrad_conv2d_dgrad_ws.  0 = a direct kernel.
+int filter_kind_planned(const contrad_conv_desc* d, int mode, long long* bytes) {
+  long long nb = 0;
+  int kind = 0;
+  if (wino44_planned(d, mode)) { kind = FILTER_WINO44; nb = wino44_workspace_bytes(d); }
+  else if (wino_planned(d, mode)) { kind = FILTER_WINO; nb = wino_workspace_bytes(d); }
+  else if (wino22_planned(d, mode)) { kind = FILTER_WINO22; nb = wino22_workspace_bytes(d); }
+  else if (mode == MODE_FWD && wino23_planned(d, mode)) { kind = FILTER_WINO23; nb = wino23_workspace_bytes(d); }
+  if (bytes) *bytes = nb;
+  return kind;
+}
+
+// Was `u` made for the path this call is about to take?  (host check: kind, mode, shape and the weight it was made from)
+inline bool filter_fits(const contrad_filter_job* u, int kind, int mode, const contrad_conv_desc* d, const float* wp) {
+  return u && u->U && u->kind == kind && u->mode == mode && u->C == d->C && u->K == d->K && u->ldw == d->ldw && u->wp == wp &&
+         ((uintptr_t)u->U & 15) == 0;
 }
 
 template <int MODE, int BM, int BN, bool BAL>
@@ -2042,9 +2093,10 @@ extern "C" long long contrad_conv2d_fwd_workspace_bytes(const contrad_conv_desc*
   return (long long)p.splits * d->N * d->Ho * d->Wo * d->K * (long long)sizeof(float);
 }
 
-extern "C" int contrad_conv2d_fwd_add(const contrad_conv_desc* d, const float* x, const float* wp,
-                                      const float* bias, const float* addend, float* y, float slope, float gain,
-                                      float* workspace, long long workspace_bytes, contrad_stream_t stream) {
+extern "C" int contrad_conv2d_fwd_add_u(const contrad_conv_desc* d, const float* x, const float* wp,
+                                        const float* bias, const float* addend, float* y, float slope, float gain,
+                                        float* workspace, long long workspace_bytes, const contrad_filter_job* u,
+                                        contrad_stream_t stream) {
   int rc = check_desc(d);
   if (rc) return rc;
   CONTRAD_ARG(x && wp && y);
@@ -2057,19 +2109,23 @@ extern "C" int contrad_conv2d_fwd_add(const contrad_conv_desc* d, const float* x
   a.st_nt = st_nt_for(M, d->ldy);
   if (wino44_planned(d, MODE_FWD) && workspace && workspace_bytes >= wino44_workspace_bytes(d)) {   // Winograd F(4x4, 3x3), wino44.h
     CONTRAD_ARG(aligned16(x, wp, workspace));
-    return launch_wino44<MODE_FWD>(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream);
+    return launch_wino44<MODE_FWD>(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream,
+                                   filter_fits(u, FILTER_WINO44, MODE_FWD, d, wp) ? u->U : nullptr);
   }
   if (wino_planned(d, MODE_FWD) && workspace && workspace_bytes >= wino_workspace_bytes(d)) {   // Winograd F(2x2, 3x3), wino.h
     CONTRAD_ARG(aligned16(x, wp, workspace));
-    return launch_wino<MODE_FWD>(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream);
+    return launch_wino<MODE_FWD>(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream,
+                                 filter_fits(u, FILTER_WINO, MODE_FWD, d, wp) ? u->U : nullptr);
   }
   if (wino22_planned(d, MODE_FWD) && workspace && workspace_bytes >= wino22_workspace_bytes(d)) {   // F(2x2, 2x2) on the phases, wino22.h
     CONTRAD_ARG(aligned16(x, wp, workspace));
-    return launch_wino22<MODE_FWD>(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream);
+    return launch_wino22<MODE_FWD>(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream,
+                                   filter_fits(u, FILTER_WINO22, MODE_FWD, d, wp) ? u->U : nullptr);
   }
   if (wino23_planned(d, MODE_FWD) && workspace && workspace_bytes >= wino23_workspace_bytes(d)) {   // 3x3 stride 2: F(2x2, 2x2) on the phases, wino23.h
     CONTRAD_ARG(aligned16(x, wp, workspace));
-    return launch_wino23(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream);
+    return launch_wino23(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream,
+                         filter_fits(u, FILTER_WINO23, MODE_FWD, d, wp) ? u->U : nullptr);
   }
   // (without a workspace of contrad_conv2d_fwd_workspace_bytes the Winograd plans above fall through to the direct kernels
   // below; contrad_conv2d_path / _executed_fraction describe the plan WITH that workspace, _grid_blocks either one)
@@ -2120,6 +2176,12 @@ extern "C" int contrad_conv2d_fwd_add(const contrad_conv_desc* d, const float* x
   return 0;
 }
 
+extern "C" int contrad_conv2d_fwd_add(const contrad_conv_desc* d, const float* x, const float* wp,
+                                      const float* bias, const float* addend, float* y, float slope, float gain,
+                                      float* workspace, long long workspace_bytes, contrad_stream_t stream) {
+  return contrad_conv2d_fwd_add_u(d, x, wp, bias, addend, y, slope, gain, workspace, workspace_bytes, nullptr, stream);
+}
+
 extern "C" int contrad_conv2d_fwd(const contrad_conv_desc* d, const float* x, const float* wp,
                                   const float* bias, float* y, float slope, float gain, float* workspace,
                                   long long workspace_bytes, contrad_stream_t stream) {
@@ -2136,24 +2198,28 @@ extern "C" long long contrad_conv2d_dgrad_workspace_bytes(const contrad_conv_des
   return (long long)p.splits * d->N * d->H * d->W * d->ldx * (long long)sizeof(float);
 }
 
-extern "C" int contrad_conv2d_dgrad_ws(const contrad_conv_desc* d, const float* gy, const float* wp,
-                                       float* dx, const float* act_ref, float slope, float gain,
-                                       float* workspace, long long workspace_bytes, contrad_stream_t stream) {
+extern "C" int contrad_conv2d_dgrad_ws_u(const contrad_conv_desc* d, const float* gy, const float* wp,
+                                         float* dx, const float* act_ref, float slope, float gain,
+                                         float* workspace, long long workspace_bytes, const contrad_filter_job* u,
+                                         contrad_stream_t stream) {
   int rc = check_desc(d);
   if (rc) return rc;
   CONTRAD_ARG(gy && wp && dx);
   if (vec_ok(d, MODE_DGRAD)) CONTRAD_ARG(aligned16(gy, wp, dx) && aligned16(act_ref, nullptr, nullptr));
   if (wino44_planned(d, MODE_DGRAD) && workspace && workspace_bytes >= wino44_workspace_bytes(d)) {   // wino44.h: mirrored filter
     CONTRAD_ARG(aligned16(gy, wp, workspace));
-    return launch_wino44<MODE_DGRAD>(d, gy, wp, nullptr, act_ref, dx, slope, gain, workspace, (hipStream_t)stream);
+    return launch_wino44<MODE_DGRAD>(d, gy, wp, nullptr, act_ref, dx, slope, gain, workspace, (hipStream_t)stream,
+                                     filter_fits(u, FILTER_WINO44, MODE_DGRAD, d, wp) ? u->U : nullptr);
   }
   if (wino_planned(d, MODE_DGRAD) && workspace && workspace_bytes >= wino_workspace_bytes(d)) {   // wino.h: mirrored filter
     CONTRAD_ARG(aligned16(gy, wp, workspace));
-    return launch_wino<MODE_DGRAD>(d, gy, wp, nullptr, act_ref, dx, slope, gain, workspace, (hipStream_t)stream);
+    return launch_wino<MODE_DGRAD>(d, gy, wp, nullptr, act_ref, dx, slope, gain, workspace, (hipStream_t)stream,
+                                   filter_fits(u, FILTER_WINO, MODE_DGRAD, d, wp) ? u->U : nullptr);
   }
   if (wino22_planned(d, MODE_DGRAD) && workspace && workspace_bytes >= wino22_workspace_bytes(d)) {   // wino22.h: one item per dx phase
     CONTRAD_ARG(aligned16(gy, wp, workspace));
-    return launch_wino22<MODE_DGRAD>(d, gy, wp, nullptr, act_ref, dx, slope, gain, workspace, (hipStream_t)stream);
+    return launch_wino22<MODE_DGRAD>(d, gy, wp, nullptr, act_ref, dx, slope, gain, workspace, (hipStream_t)stream,
+                                     filter_fits(u, FILTER_WINO22, MODE_DGRAD, d, wp) ? u->U : nullptr);
   }
   if (conv_c32_ok(d))   // stride-1 pad-1 3x3: the same weight-stationary kernel with the filter mirrored (conv_c32.h)
     return launch_conv_c32<MODE_DGRAD>(d, gy, wp, dx, nullptr, nullptr, act_ref, slope, gain, (hipStream_t)stream);
@@ -2240,10 +2306,45 @@ extern "C" int contrad_conv2d_dgrad_ws(const contrad_conv_desc* d, const float* 
   return dispatch<MODE_DGRAD>(a, bm, bn, vec, dim3(tm_pad * a.tiles_n, s * s), (hipStream_t)stream);
 }
 
+extern "C" int contrad_conv2d_dgrad_ws(const contrad_conv_desc* d, const float* gy, const float* wp,
+                                       float* dx, const float* act_ref, float slope, float gain,
+                                       float* workspace, long long workspace_bytes, contrad_stream_t stream) {
+  return contrad_conv2d_dgrad_ws_u(d, gy, wp, dx, act_ref, slope, gain, workspace, workspace_bytes, nullptr, stream);
+}
+
 extern "C" int contrad_conv2d_dgrad(const contrad_conv_desc* d, const float* gy, const float* wp,
                                     float* dx, const float* act_ref, float slope, float gain,
                                     contrad_stream_t stream) {
   return contrad_conv2d_dgrad_ws(d, gy, wp, dx, act_ref, slope, gain, nullptr, 0, stream);   // never splits K
+}
+
+extern "C" int contrad_conv2d_filter_kind(const contrad_conv_desc* d, int mode, long long* bytes) {
+  if (bytes) *bytes = 0;
+  if (check_desc(d)) return -22;
+  if (mode != MODE_FWD && mode != MODE_DGRAD) return -22;
+  return filter_kind_planned(d, mode, bytes);
+}
+
+extern "C" int contrad_conv2d_filter_prep(const contrad_filter_batch* b, contrad_stream_t stream) {
+  CONTRAD_ARG(b && b->n >= 0 && b->n <= CONTRAD_FILTER_MAX_JOBS);
+  if (b->n == 0) return 0;
+  contrad_filter_batch k = *b;
+  long long blocks = 0;
+  for (int j = 0; j < k.n; ++j) {
+    const contrad_filter_job& q = k.jobs[j];
+    CONTRAD_ARG(q.wp && q.U && q.C > 0 && q.K > 0 && q.ldw >= q.K && (q.ldw & 3) == 0);
+    CONTRAD_ARG(aligned16(q.wp, q.U, nullptr));
+    const long long threads = filter_threads(q.kind, q.mode, q.C, q.K);
+    // (the channel counts every family's *_ok asks of its input side: whole quads; the 16-byte loads of the mirrored read)
+    CONTRAD_ARG(threads > 0 && ((q.mode == MODE_FWD ? q.C : q.K) & 7) == 0);
+    k.block_start[j] = (int)blocks;
+    blocks += cdivll(threads, 256);
+    CONTRAD_ARG(blocks < (1ll << 30));
+  }
+  for (int j = k.n; j <= CONTRAD_FILTER_MAX_JOBS; ++j) k.block_start[j] = (int)blocks;
+  hipLaunchKernelGGL(filter_prep_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, k);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int contrad_conv2d_wino_ok(const contrad_conv_desc* d, int mode) {

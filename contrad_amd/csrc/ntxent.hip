@@ -28,6 +28,23 @@ struct ContrastArgs {
   float inv_temp;
 };
 
+// Up to two independent problems per launch (ContraD's D-step: NT-Xent on 2N rows and SupCon on 3N rows; each alone leaves
+// most of the chip idle): problem = blockIdx.z of the main kernels (grid = the larger problem's; blocks past a problem's
+// own row tiles / column splits leave at once), blockIdx.x of the loss reduce, blockIdx.y of the slab reduce.  Every
+// problem keeps its own S, workspace and summation order: results are those of separate launches.
+constexpr int MAXP = CONTRAD_CONTRAST_MAX_PROBLEMS;
+struct ContrastBatch {
+  ContrastArgs a[MAXP];
+  int S[MAXP];               // column splits
+  float* part[MAXP];         // workspace
+  float coef[MAXP];          // anchor_coef
+  float* lse[MAXP];          // fwd: out, bwd: in
+  float* rowloss[MAXP];
+  float* loss[MAXP];
+  const float* gscale[MAXP];
+  float* dz[MAXP];
+};
+
 __device__ __forceinline__ bool is_anchor(const ContrastArgs& a, int i) {
   return a.mode == 0 ? (i < a.R) : (i >= 2 * a.N && i < a.R);
 }
@@ -82,7 +99,12 @@ __device__ __forceinline__ f32x16 s_tile(const float* Ar, const float* Zr, int r
 }
 
 template <int DP>
-__global__ __launch_bounds__(256) void contrast_fwd_kernel(ContrastArgs a, float* __restrict__ part) {
+__global__ __launch_bounds__(256) void contrast_fwd_kernel(const ContrastBatch b) {
+  const int pb = blockIdx.z;
+  const ContrastArgs a = b.a[pb];
+  const int S = b.S[pb];
+  if ((int)blockIdx.x * RT >= a.R || (int)blockIdx.y >= S) return;      // (the grid is the larger problem's)
+  float* __restrict__ part = b.part[pb];
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int LD = DP + 1;
   float* Ar = smem;
@@ -100,7 +122,7 @@ __global__ __launch_bounds__(256) void contrast_fwd_kernel(ContrastArgs a, float
 #pragma unroll
   for (int r = 0; r < 16; ++r) { m[r] = -INFINITY; s[r] = 0.f; tsum[r] = 0.f; }
 
-  for (int c0 = blockIdx.y * CT; c0 < a.R; c0 += gridDim.y * CT) {
+  for (int c0 = blockIdx.y * CT; c0 < a.R; c0 += S * CT) {
     __syncthreads();
     stage_rows<DP>(Zr, a.z, c0, a.R, a.D);
     __syncthreads();
@@ -161,9 +183,15 @@ __global__ __launch_bounds__(256) void contrast_fwd_kernel(ContrastArgs a, float
 // loss = c * sum_i rowloss[i] (single block -> one fixed summation order).
 // (one block of 1024 threads: one or two rows per thread.  With 256 threads every thread walked 4 - 6 rows x 2 S dependent
 // load groups one after the other: 30 us for 200 KB, pure latency.)
-__global__ __launch_bounds__(1024) void contrast_loss_reduce_kernel(ContrastArgs a, const float* __restrict__ part, int S, float c,
-                                            float* __restrict__ lse_out, float* __restrict__ rowloss_out,
-                                            float* __restrict__ loss_out) {
+__global__ __launch_bounds__(1024) void contrast_loss_reduce_kernel(const ContrastBatch b) {
+  const int pb = blockIdx.x;
+  const ContrastArgs a = b.a[pb];
+  const float* __restrict__ part = b.part[pb];
+  const int S = b.S[pb];
+  const float c = b.coef[pb];
+  float* __restrict__ lse_out = b.lse[pb];
+  float* __restrict__ rowloss_out = b.rowloss[pb];
+  float* __restrict__ loss_out = b.loss[pb];
   __shared__ float red[16];
   float v = 0.f;
   for (int i = threadIdx.x; i < a.R; i += blockDim.x) {
@@ -186,9 +214,16 @@ __global__ __launch_bounds__(1024) void contrast_loss_reduce_kernel(ContrastArgs
 }
 
 template <int DP>
-__global__ __launch_bounds__(256) void contrast_bwd_kernel(ContrastArgs a, const float* __restrict__ lse,
-                                                           float coef, const float* __restrict__ gscale,
-                                                           float* __restrict__ dz, float* __restrict__ part) {
+__global__ __launch_bounds__(256) void contrast_bwd_kernel(const ContrastBatch b) {
+  const int pb = blockIdx.z;
+  const ContrastArgs a = b.a[pb];
+  const int S = b.S[pb];
+  if ((int)blockIdx.x * RT >= a.R || (int)blockIdx.y >= S) return;      // (the grid is the larger problem's)
+  const float* __restrict__ lse = b.lse[pb];
+  const float coef = b.coef[pb];
+  const float* __restrict__ gscale = b.gscale[pb];
+  float* __restrict__ dz = b.dz[pb];
+  float* __restrict__ part = b.part[pb];
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int LD = DP + 1;
   constexpr int LDW = RT + 1;
@@ -214,7 +249,7 @@ __global__ __launch_bounds__(256) void contrast_bwd_kernel(ContrastArgs a, const
 #pragma unroll
     for (int r = 0; r < 16; ++r) dacc[t][r] = 0.f;
 
-  for (int c0 = blockIdx.y * CT; c0 < a.R; c0 += gridDim.y * CT) {
+  for (int c0 = blockIdx.y * CT; c0 < a.R; c0 += S * CT) {
     __syncthreads();
     stage_rows<DP>(Zr, a.z, c0, a.R, a.D);
     if (tid < CT) lse_c[tid] = (c0 + tid < a.R) ? lse[c0 + tid] : 0.f;
@@ -254,7 +289,7 @@ __global__ __launch_bounds__(256) void contrast_bwd_kernel(ContrastArgs a, const
     for (int r = 0; r < 16; ++r) {
       const int i = r0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
       if (i < a.R && dcol < a.D) {
-        if (gridDim.y == 1) dz[(size_t)i * a.D + dcol] = dacc[t][r] * scale;
+        if (S == 1) dz[(size_t)i * a.D + dcol] = dacc[t][r] * scale;
         else part[((size_t)blockIdx.y * a.R + i) * a.D + dcol] = dacc[t][r];   // unscaled slab of this split
       }
     }
@@ -262,8 +297,15 @@ __global__ __launch_bounds__(256) void contrast_bwd_kernel(ContrastArgs a, const
 }
 
 // dz = scale * sum_s part[s]  (fixed order)
-__global__ void contrast_bwd_reduce_kernel(const float* __restrict__ part, int S, long long n, float coef_temp,
-                                           const float* __restrict__ gscale, float* __restrict__ dz) {
+__global__ void contrast_bwd_reduce_kernel(const ContrastBatch b) {
+  const int pb = blockIdx.y;
+  const int S = b.S[pb];
+  if (S == 1) return;      // (that problem's main kernel wrote dz itself)
+  const float* __restrict__ part = b.part[pb];
+  const long long n = (long long)b.a[pb].R * b.a[pb].D;
+  const float coef_temp = b.coef[pb] * b.a[pb].inv_temp;
+  const float* __restrict__ gscale = b.gscale[pb];
+  float* __restrict__ dz = b.dz[pb];
   const float scale = coef_temp * (gscale ? gscale[0] : 1.f);
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
     float v = 0.f;
@@ -273,9 +315,19 @@ __global__ void contrast_bwd_reduce_kernel(const float* __restrict__ part, int S
 }
 
 // ---- row L2 normalisation (F.normalize, contrad.py:43,48): one wave per row ----
-__global__ void l2norm_fwd_kernel(const float* __restrict__ u, int ldu, float* __restrict__ z,
-                                  float* __restrict__ invn, int R, int D, float eps) {
-  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+// (up to two matrices per launch: the blocks of problem 0 come first, then problem 1's)
+struct L2Batch {
+  contrad_l2norm_problem p[MAXP];
+  int block_start[MAXP + 1];
+};
+
+__global__ void l2norm_fwd_kernel(const L2Batch b, float eps) {
+  const int pb = ((int)blockIdx.x >= b.block_start[1]) ? 1 : 0;
+  const float* __restrict__ u = b.p[pb].u;
+  float* __restrict__ z = b.p[pb].z;
+  float* __restrict__ invn = b.p[pb].inv_norm;
+  const int ldu = b.p[pb].ldu, R = b.p[pb].R, D = b.p[pb].D;
+  const int row = ((int)blockIdx.x - b.block_start[pb]) * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= R) return;
   float ss = 0.f;
@@ -287,12 +339,21 @@ __global__ void l2norm_fwd_kernel(const float* __restrict__ u, int ldu, float* _
 }
 
 // du = (dz - z * <z, dz>) * inv_norm   (rows whose norm was clamped by eps are not on this path)
-__global__ void l2norm_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ z,
-                                  const float* __restrict__ invn, float* __restrict__ du, int ldu, int R,
-                                  int D, int accumulate) {
-  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+// (rows [R, R + zero_rows) of du get zeros: the projection rows a loss does not read, without a fill of their own)
+__global__ void l2norm_bwd_kernel(const L2Batch b) {
+  const int pb = ((int)blockIdx.x >= b.block_start[1]) ? 1 : 0;
+  const float* __restrict__ dz = b.p[pb].dz;
+  const float* __restrict__ z = b.p[pb].z;
+  const float* __restrict__ invn = b.p[pb].inv_norm;
+  float* __restrict__ du = b.p[pb].du;
+  const int ldu = b.p[pb].ldu, R = b.p[pb].R, D = b.p[pb].D, accumulate = b.p[pb].accumulate;
+  const int row = ((int)blockIdx.x - b.block_start[pb]) * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (row >= R) return;
+  if (row >= R) {
+    if (row < R + b.p[pb].zero_rows)
+      for (int d = lane; d < D; d += 64) du[(size_t)row * ldu + d] = 0.f;
+    return;
+  }
   float dot = 0.f;
   for (int d = lane; d < D; d += 64) dot += dz[(size_t)row * D + d] * z[(size_t)row * D + d];
   dot = wave_sum(dot);
@@ -310,7 +371,7 @@ template <int DP>
 size_t bwd_smem() { return (size_t)(2 * 64 * (DP + 1) + 64 * 65 + 128) * sizeof(float); }
 
 template <int DP>
-int launch_fwd(const ContrastArgs& a, int S, float* part, hipStream_t s) {
+int launch_fwd(const ContrastBatch& b, dim3 grid, hipStream_t s) {
   static bool set = false;
   if (!set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&contrast_fwd_kernel<DP>),
@@ -318,13 +379,12 @@ int launch_fwd(const ContrastArgs& a, int S, float* part, hipStream_t s) {
     if (e != hipSuccess) return (int)e;
     set = true;
   }
-  hipLaunchKernelGGL((contrast_fwd_kernel<DP>), dim3(cdiv(a.R, RT), S), dim3(256), fwd_smem<DP>(), s, a, part);
+  hipLaunchKernelGGL((contrast_fwd_kernel<DP>), grid, dim3(256), fwd_smem<DP>(), s, b);
   CONTRAD_CHECK_LAUNCH();
   return 0;
 }
 template <int DP>
-int launch_bwd(const ContrastArgs& a, int S, const float* lse, float coef, const float* gscale, float* dz,
-               float* part, hipStream_t s) {
+int launch_bwd(const ContrastBatch& b, dim3 grid, hipStream_t s) {
   static bool set = false;
   if (!set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&contrast_bwd_kernel<DP>),
@@ -332,8 +392,7 @@ int launch_bwd(const ContrastArgs& a, int S, const float* lse, float coef, const
     if (e != hipSuccess) return (int)e;
     set = true;
   }
-  hipLaunchKernelGGL((contrast_bwd_kernel<DP>), dim3(cdiv(a.R, RT), S), dim3(256), bwd_smem<DP>(), s, a, lse,
-                     coef, gscale, dz, part);
+  hipLaunchKernelGGL((contrast_bwd_kernel<DP>), grid, dim3(256), bwd_smem<DP>(), s, b);
   CONTRAD_CHECK_LAUNCH();
   return 0;
 }
@@ -363,64 +422,149 @@ extern "C" long long contrad_contrast_workspace_bytes(int R, int D) {
   return (long long)splits(R) * per * (long long)sizeof(float);
 }
 
+// padded feature width of the kernel instance that serves D
+static int dp_class(int D) { return D <= 64 ? 64 : D <= 128 ? 128 : 256; }
+
+// problems [lo, hi) of `p` (one kernel instance: equal dp_class) as one launch pair
+static int contrast_fwd_group(const contrad_contrast_problem* p, int lo, int hi, hipStream_t s) {
+  ContrastBatch b{};
+  int gx = 0, gy = 0;
+  for (int j = lo; j < hi; ++j) {
+    const contrad_contrast_problem& q = p[j];
+    const int k = j - lo;
+    b.a[k] = ContrastArgs{q.z, q.R, q.D, q.N, q.mode, q.inv_temp};
+    b.S[k] = splits(q.R);
+    b.part[k] = q.workspace; b.coef[k] = anchor_coef(q.N, q.mode);
+    b.lse[k] = q.lse; b.rowloss[k] = q.rowloss; b.loss[k] = q.loss;
+    gx = gx > cdiv(q.R, RT) ? gx : cdiv(q.R, RT);
+    gy = gy > b.S[k] ? gy : b.S[k];
+  }
+  const dim3 grid(gx, gy, hi - lo);
+  const int dp = dp_class(p[lo].D);
+  int rc = dp == 64 ? launch_fwd<64>(b, grid, s) : dp == 128 ? launch_fwd<128>(b, grid, s) : launch_fwd<256>(b, grid, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(contrast_loss_reduce_kernel, dim3(hi - lo), dim3(1024), 0, s, b);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+static int contrast_bwd_group(const contrad_contrast_problem* p, int lo, int hi, hipStream_t s) {
+  ContrastBatch b{};
+  int gx = 0, gy = 0;
+  long long nmax = 0;
+  for (int j = lo; j < hi; ++j) {
+    const contrad_contrast_problem& q = p[j];
+    const int k = j - lo;
+    b.a[k] = ContrastArgs{q.z, q.R, q.D, q.N, q.mode, q.inv_temp};
+    b.S[k] = splits(q.R);
+    b.part[k] = q.workspace; b.coef[k] = anchor_coef(q.N, q.mode);
+    b.lse[k] = q.lse; b.gscale[k] = q.grad_scale; b.dz[k] = q.dz;
+    gx = gx > cdiv(q.R, RT) ? gx : cdiv(q.R, RT);
+    gy = gy > b.S[k] ? gy : b.S[k];
+    if (b.S[k] > 1 && (long long)q.R * q.D > nmax) nmax = (long long)q.R * q.D;
+  }
+  const dim3 grid(gx, gy, hi - lo);
+  const int dp = dp_class(p[lo].D);
+  int rc = dp == 64 ? launch_bwd<64>(b, grid, s) : dp == 128 ? launch_bwd<128>(b, grid, s) : launch_bwd<256>(b, grid, s);
+  if (rc || nmax == 0) return rc;      // (no problem split its columns: every dz is written)
+  int blocks = (int)((nmax + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(contrast_bwd_reduce_kernel, dim3(blocks, hi - lo), dim3(256), 0, s, b);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+static int contrast_check(const contrad_contrast_problem* p, int n, bool bwd) {
+  CONTRAD_ARG(p && n >= 1 && n <= CONTRAD_CONTRAST_MAX_PROBLEMS);
+  for (int j = 0; j < n; ++j) {
+    const contrad_contrast_problem& q = p[j];
+    int rc = check(q.R, q.D, q.N, q.mode);
+    if (rc) return rc;
+    CONTRAD_ARG(q.z && q.lse && q.workspace);
+    if (bwd) CONTRAD_ARG(q.dz != nullptr); else CONTRAD_ARG(q.rowloss && q.loss);
+    CONTRAD_ARG(q.workspace_bytes >= contrad_contrast_workspace_bytes(q.R, q.D));
+  }
+  return 0;
+}
+
+extern "C" int contrad_contrast_fwd_batched(const contrad_contrast_problem* p, int n, contrad_stream_t stream) {
+  int rc = contrast_check(p, n, false);
+  if (rc) return rc;
+  if (n == 2 && dp_class(p[0].D) != dp_class(p[1].D)) {      // two kernel instances: two launches
+    rc = contrast_fwd_group(p, 0, 1, (hipStream_t)stream);
+    return rc ? rc : contrast_fwd_group(p, 1, 2, (hipStream_t)stream);
+  }
+  return contrast_fwd_group(p, 0, n, (hipStream_t)stream);
+}
+
+extern "C" int contrad_contrast_bwd_batched(const contrad_contrast_problem* p, int n, contrad_stream_t stream) {
+  int rc = contrast_check(p, n, true);
+  if (rc) return rc;
+  if (n == 2 && dp_class(p[0].D) != dp_class(p[1].D)) {
+    rc = contrast_bwd_group(p, 0, 1, (hipStream_t)stream);
+    return rc ? rc : contrast_bwd_group(p, 1, 2, (hipStream_t)stream);
+  }
+  return contrast_bwd_group(p, 0, n, (hipStream_t)stream);
+}
+
 extern "C" int contrad_contrast_fwd(const float* z, int R, int D, int N, int mode, float inv_temp,
                                     float* lse, float* rowloss, float* loss, float* workspace,
                                     long long workspace_bytes, contrad_stream_t stream) {
-  int rc = check(R, D, N, mode);
-  if (rc) return rc;
-  CONTRAD_ARG(z && lse && rowloss && loss && workspace);
-  CONTRAD_ARG(workspace_bytes >= contrad_contrast_workspace_bytes(R, D));
-  ContrastArgs a{z, R, D, N, mode, inv_temp};
-  hipStream_t s = (hipStream_t)stream;
-  const int S = splits(R);
-  if (D <= 64) rc = launch_fwd<64>(a, S, workspace, s);
-  else if (D <= 128) rc = launch_fwd<128>(a, S, workspace, s);
-  else rc = launch_fwd<256>(a, S, workspace, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL(contrast_loss_reduce_kernel, dim3(1), dim3(1024), 0, s, a, workspace, S, anchor_coef(N, mode),
-                     lse, rowloss, loss);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
+  contrad_contrast_problem q{};
+  q.z = z; q.R = R; q.D = D; q.N = N; q.mode = mode; q.inv_temp = inv_temp;
+  q.lse = lse; q.rowloss = rowloss; q.loss = loss; q.workspace = workspace; q.workspace_bytes = workspace_bytes;
+  return contrad_contrast_fwd_batched(&q, 1, stream);
 }
 
 extern "C" int contrad_contrast_bwd(const float* z, const float* lse, int R, int D, int N, int mode,
                                     float inv_temp, const float* grad_scale, float* dz, float* workspace,
                                     long long workspace_bytes, contrad_stream_t stream) {
-  int rc = check(R, D, N, mode);
-  if (rc) return rc;
-  CONTRAD_ARG(z && lse && dz && workspace);
-  CONTRAD_ARG(workspace_bytes >= contrad_contrast_workspace_bytes(R, D));
-  ContrastArgs a{z, R, D, N, mode, inv_temp};
-  hipStream_t s = (hipStream_t)stream;
-  const float c = anchor_coef(N, mode);
-  const int S = splits(R);
-  if (D <= 64) rc = launch_bwd<64>(a, S, lse, c, grad_scale, dz, workspace, s);
-  else if (D <= 128) rc = launch_bwd<128>(a, S, lse, c, grad_scale, dz, workspace, s);
-  else rc = launch_bwd<256>(a, S, lse, c, grad_scale, dz, workspace, s);
-  if (rc || S == 1) return rc;
-  const long long n = (long long)R * D;
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(contrast_bwd_reduce_kernel, dim3(blocks), dim3(256), 0, s, workspace, S, n, c * inv_temp,
-                     grad_scale, dz);
+  contrad_contrast_problem q{};
+  q.z = z; q.R = R; q.D = D; q.N = N; q.mode = mode; q.inv_temp = inv_temp;
+  q.lse = const_cast<float*>(lse); q.grad_scale = grad_scale; q.dz = dz; q.workspace = workspace; q.workspace_bytes = workspace_bytes;
+  return contrad_contrast_bwd_batched(&q, 1, stream);
+}
+
+static int l2norm_launch(const contrad_l2norm_problem* p, int n, bool bwd, float eps, hipStream_t s) {
+  CONTRAD_ARG(p && n >= 1 && n <= CONTRAD_CONTRAST_MAX_PROBLEMS);
+  L2Batch b{};
+  int blocks = 0;
+  for (int j = 0; j < n; ++j) {
+    const contrad_l2norm_problem& q = p[j];
+    CONTRAD_ARG(q.z && q.inv_norm && q.R > 0 && q.D > 0 && q.ldu >= q.D);
+    if (bwd) CONTRAD_ARG(q.dz && q.du && q.zero_rows >= 0); else CONTRAD_ARG(q.u != nullptr);
+    b.p[j] = q;
+    b.block_start[j] = blocks;
+    blocks += cdiv(q.R + (bwd ? q.zero_rows : 0), 4);
+  }
+  for (int j = n; j <= CONTRAD_CONTRAST_MAX_PROBLEMS; ++j) b.block_start[j] = blocks;
+  if (bwd) hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(blocks), dim3(256), 0, s, b);
+  else hipLaunchKernelGGL(l2norm_fwd_kernel, dim3(blocks), dim3(256), 0, s, b, eps);
   CONTRAD_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int contrad_l2norm_fwd_batched(const contrad_l2norm_problem* p, int n, float eps, contrad_stream_t stream) {
+  return l2norm_launch(p, n, false, eps, (hipStream_t)stream);
+}
+
+extern "C" int contrad_l2norm_bwd_batched(const contrad_l2norm_problem* p, int n, contrad_stream_t stream) {
+  return l2norm_launch(p, n, true, 0.f, (hipStream_t)stream);
 }
 
 extern "C" int contrad_l2norm_fwd(const float* u, int ldu, float* z, float* inv_norm, int R, int D,
                                   float eps, contrad_stream_t stream) {
   CONTRAD_ARG(u && z && inv_norm && R > 0 && D > 0 && ldu >= D);
-  hipLaunchKernelGGL(l2norm_fwd_kernel, dim3(cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, u, ldu, z,
-                     inv_norm, R, D, eps);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
+  contrad_l2norm_problem q{};
+  q.u = u; q.ldu = ldu; q.z = z; q.inv_norm = inv_norm; q.R = R; q.D = D;
+  return l2norm_launch(&q, 1, false, eps, (hipStream_t)stream);
 }
 
 extern "C" int contrad_l2norm_bwd(const float* dz, const float* z, const float* inv_norm, float* du,
                                   int ldu, int R, int D, int accumulate, contrad_stream_t stream) {
   CONTRAD_ARG(dz && z && inv_norm && du && R > 0 && D > 0 && ldu >= D);
-  hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, dz, z,
-                     inv_norm, du, ldu, R, D, accumulate);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
+  contrad_l2norm_problem q{};
+  q.dz = dz; q.z = const_cast<float*>(z); q.inv_norm = const_cast<float*>(inv_norm); q.du = du; q.ldu = ldu; q.R = R; q.D = D;
+  q.accumulate = accumulate;
+  return l2norm_launch(&q, 1, true, 0.f, (hipStream_t)stream);
 }

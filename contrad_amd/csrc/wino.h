@@ -8,7 +8,8 @@
 //   y = A^T [ sum_c (G g G^T) (.) (B^T d B) ] A      16 independent GEMMs  M_xi[tile][k] = sum_c V_xi[tile][c] U_xi[c][k]
 //
 // = 16 multiply-adds per 2x2 output tile, channel pair instead of 36 (2.25x fewer).  Nothing transformed ever reaches HBM
-// except U = G g G^T (written once per call by wino_filter_kernel from the packed weight: 16/9 of the weight's size).
+// except U = G g G^T (written by wino_filter_kernel per call, or once per weight prep by filter_prep_kernel, igemm.hip, from the
+// packed weight: 16/9 of the weight's size).
 // The data gradient of such a layer is the same correlation over gy with the filter mirrored and its channel roles
 // swapped: the same kernel with another U.
 //
@@ -422,10 +423,10 @@ __global__ __launch_bounds__(512, 2) void wino_kernel(const Args p) {
 //   DGRAD: g'[c][k][a][b] = W[k][c][2 - a][2 - b]  input channels k (gy's), output channels c:       U[xi][k/8][(k%8)/4][c][k%4]
 // One thread = four input channels x one output channel (one float4 per xi plane; lanes along the output channel: stores
 // fully coalesced; FWD loads coalesced along k, DGRAD loads 16-byte pieces of rows 4 * ldw bytes apart).
+// (filter_quad: the work of thread `idx`, shared by the per-call kernel below and the batched prep, igemm.hip: filter_prep_kernel)
 template <int MODE>
-__global__ __launch_bounds__(256) void wino_filter_kernel(const float* __restrict__ wp, float* __restrict__ U, int C, int K, int ldw) {
+__device__ __forceinline__ void filter_quad(const float* __restrict__ wp, float* __restrict__ U, int C, int K, int ldw, int idx) {
   const int cin = (MODE == MODE_FWD) ? C : K, cout = (MODE == MODE_FWD) ? K : C;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= (cin >> 2) * cout) return;
   const int o = idx % cout, q4 = idx / cout;       // output channel, input-channel quad
   float g[9][4];
@@ -465,6 +466,11 @@ __global__ __launch_bounds__(256) void wino_filter_kernel(const float* __restric
       Uo[((size_t)(xi * nch + (q4 >> 1)) * 2 + (q4 & 1)) * cout + o] = make_float4(u[0], u[1], u[2], u[3]);
     }
   }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void wino_filter_kernel(const float* __restrict__ wp, float* __restrict__ U, int C, int K, int ldw) {
+  filter_quad<MODE>(wp, U, C, K, ldw, blockIdx.x * 256 + threadIdx.x);
 }
 
 

@@ -376,11 +376,11 @@ __global__ __launch_bounds__(512, 2) void wino22_kernel(const Args p) {
 //   FWD:   input phase (p, q):  g[a][b] = w[kh(p,a)][kw(q,b)],  kh(1,a) = 2a, kh(0,a) = 1 + 2a;   input channels c, output channels k
 //   DGRAD: output phase (ph, pw): g[al][be] = w[kh'(ph,al)][kw'(pw,be)], kh'(0,al) = 3 - 2 al, kh'(1,al) = 2 - 2 al;   input channels k, output c
 // U[phase][xi][cin / 8][(cin % 8) / 4][cout][cin % 4].  One thread = one phase x four input channels x one output channel.
+// (filter_quad: the work of thread `idx`, shared by the per-call kernel below and the batched prep, igemm.hip: filter_prep_kernel)
 template <int MODE>
-__global__ __launch_bounds__(256) void wino22_filter_kernel(const float* __restrict__ wp, float* __restrict__ U, int C, int K, int ldw) {
+__device__ __forceinline__ void filter_quad(const float* __restrict__ wp, float* __restrict__ U, int C, int K, int ldw, int idx) {
   const int cin = (MODE == MODE_FWD) ? C : K, cout = (MODE == MODE_FWD) ? K : C;
   const int per = (cin >> 2) * cout;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= 4 * per) return;
   const int ph = idx / per, rem = idx - ph * per;
   const int o = rem % cout, q4 = rem / cout;
@@ -415,6 +415,11 @@ __global__ __launch_bounds__(256) void wino22_filter_kernel(const float* __restr
       }
       Uo[((size_t)((i * 3 + j) * nch + (q4 >> 1)) * 2 + (q4 & 1)) * cout + o] = make_float4(u[0], u[1], u[2], u[3]);
     }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void wino22_filter_kernel(const float* __restrict__ wp, float* __restrict__ U, int C, int K, int ldw) {
+  filter_quad<MODE>(wp, U, C, K, ldw, blockIdx.x * 256 + threadIdx.x);
 }
 
 

@@ -386,9 +386,9 @@ __global__ __launch_bounds__(512, 2) void wino23_kernel(const Args p) {
 // U_ph = G g_ph G^T (G = [[1,0],[1,1],[0,1]]) per input phase (p, q) from the packed 3x3 weight Wp[(kh * 3 + kw) * C + c][ldw]:
 // g[a][b] = w4[kh(p,a)][kw(q,b)], kh(1,a) = 2a, kh(0,a) = 1 + 2a (wino22.h), w4[k][l] = w[k - 1][l - 1] and 0 for k = 0 or l = 0.
 // U[phase][xi][cin / 8][(cin % 8) / 4][cout][cin % 4].  One thread = one phase x four input channels x one output channel.
-__global__ __launch_bounds__(256) void wino23_filter_kernel(const float* __restrict__ wp, float* __restrict__ U, int C, int K, int ldw) {
+// (filter_quad: the work of thread `idx`, shared by the per-call kernel below and the batched prep, igemm.hip: filter_prep_kernel)
+__device__ __forceinline__ void filter_quad(const float* __restrict__ wp, float* __restrict__ U, int C, int K, int ldw, int idx) {
   const int per = (C >> 2) * K;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= 4 * per) return;
   const int ph = idx / per, rem = idx - ph * per;
   const int o = rem % K, q4 = rem / K;
@@ -417,6 +417,10 @@ __global__ __launch_bounds__(256) void wino23_filter_kernel(const float* __restr
       }
       Uo[((size_t)((i * 3 + j) * nch + (q4 >> 1)) * 2 + (q4 & 1)) * K + o] = make_float4(u[0], u[1], u[2], u[3]);
     }
+}
+
+__global__ __launch_bounds__(256) void wino23_filter_kernel(const float* __restrict__ wp, float* __restrict__ U, int C, int K, int ldw) {
+  filter_quad(wp, U, C, K, ldw, blockIdx.x * 256 + threadIdx.x);
 }
 
 }  // namespace wino23

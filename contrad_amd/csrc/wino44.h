@@ -411,10 +411,13 @@ __global__ __launch_bounds__(512, 2) void wino44_kernel(const Args p) {
 //   FWD:   g[k][c] = W[k][c][.][.]                 input channels c, output channels k:  U[xi][c/8][(c%8)/4][k][c%4]
 //   DGRAD: g'[c][k][a][b] = W[k][c][2 - a][2 - b]  input channels k (gy's), output channels c:  U[xi][k/8][(k%8)/4][c][k%4]
 // One thread = four input channels x one output channel.
+// (filter_quad: the work of thread `idx`, shared by the per-call kernel below and the batched prep, igemm.hip: filter_prep_kernel.
+// NOT inlined: which of the products of G's fractional rows the compiler contracts into FMAs depends on the code around them --
+// inlined into the per-call kernel the forward variant came out one ulp off the kernel it replaced --, so both callers share
+// ONE compiled body; its floating-point instructions are those of the former kernel.)
 template <int MODE>
-__global__ __launch_bounds__(256) void wino44_filter_kernel(const float* __restrict__ wp, float* __restrict__ U, int C, int K, int ldw) {
+__device__ __noinline__ void filter_quad(const float* __restrict__ wp, float* __restrict__ U, int C, int K, int ldw, int idx) {
   const int cin = (MODE == MODE_FWD) ? C : K, cout = (MODE == MODE_FWD) ? K : C;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= (cin >> 2) * cout) return;
   const int o = idx % cout, q4 = idx / cout;
   float g[9][4];
@@ -456,6 +459,11 @@ __global__ __launch_bounds__(256) void wino44_filter_kernel(const float* __restr
       Uo[((size_t)(xi * nch + (q4 >> 1)) * 2 + (q4 & 1)) * cout + o] = make_float4(u[0], u[1], u[2], u[3]);
     }
   }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void wino44_filter_kernel(const float* __restrict__ wp, float* __restrict__ U, int C, int K, int ldw) {
+  filter_quad<MODE>(wp, U, C, K, ldw, blockIdx.x * 256 + threadIdx.x);
 }
 
 }  // namespace wino44

@@ -335,16 +335,16 @@ class GraphedDStep(object):
         self.images.copy_(images)
 
     def _refresh_inputs(self):
-        from .hostio import upload
+        from .hostio import upload_into
         G, N = self.G, self.N
-        dev = self.images.device
         z = torch.empty(N, G.nz).uniform_(-1, 1)                        # G.sample_latent's draw (sndcgan.py:50-52)
         Pm, cf, _ = self.aug.sample(3 * N, self.images.shape[2], self.images.shape[3])
         Pm[:, 15] = float(cf)
-        self.z.copy_(upload(z, dev))
-        self.params.copy_(upload(Pm, dev))
+        # pulled straight into the static tensors (was: pulls into temporaries, a cat of the pieces, a copy)
+        upload_into(z, self.z)
+        upload_into(Pm, self.params)
         world = dist.get_world_size() if self.dist else 1
-        self.hyper.copy_(upload(torch.tensor([self.opt.hyper_values(1.0 / world)], dtype=torch.float32), dev).view(3))
+        upload_into(torch.tensor([self.opt.hyper_values(1.0 / world)], dtype=torch.float32), self.hyper.view(1, 3))
 
     def _body(self):
         from . import ops

@@ -26,8 +26,9 @@ _RING = 8                      # staging slots per (shape, dtype); a slot is onl
 _rings = {}
 
 
-def _pull(t, device):
-    """One piece: host tensor -> pinned ring slot -> device tensor written by contrad_pull_host on the current stream."""
+def _pull(t, device, out=None):
+    """One piece: host tensor -> pinned ring slot -> device tensor (``out``: a contiguous device tensor of t's shape, else
+    a new one) written by contrad_pull_host on the current stream."""
     from . import ops
     key = (tuple(t.shape), t.dtype)
     ring = _rings.get(key)
@@ -39,7 +40,8 @@ def _pull(t, device):
     if done is not None:
         done.synchronize()     # (returns at once unless the caller is more than _RING uploads ahead of the GPU)
     buf.copy_(t)
-    out = torch.empty(t.shape, dtype=t.dtype, device=device)
+    if out is None:
+        out = torch.empty(t.shape, dtype=t.dtype, device=device)
     ops.lib().call('contrad_pull_host', buf.data_ptr(), out.data_ptr(), t.numel(), ops._stream())
     slots[i][1] = torch.cuda.Event()
     slots[i][1].record()
@@ -55,6 +57,26 @@ def upload(t, device):
         return _pull(t.contiguous(), device) if nbytes <= 2 * _CHUNK else t.to(device)
     rows = max(1, _CHUNK // (t.shape[1] * t.element_size()))
     return torch.cat([_pull(t[i:i + rows].contiguous(), device) for i in range(0, t.shape[0], rows)], 0)
+
+
+def upload_into(t, dst):
+    """``dst.copy_(upload(t, dst.device))`` without the temporaries: the pieces are pulled straight into (row slices of)
+    the contiguous device tensor ``dst`` -- a captured step's static inputs -- instead of into new tensors that are then
+    concatenated and copied.  Same piece sizes as upload()."""
+    if (_SYNC or t.dtype != torch.float32 or dst.dtype != torch.float32 or dst.device.type != 'cuda'
+            or not dst.is_contiguous() or tuple(dst.shape) != tuple(t.shape)):
+        dst.copy_(upload(t, dst.device).view(dst.shape))
+        return
+    nbytes = t.numel() * t.element_size()
+    if nbytes <= _CHUNK or t.dim() != 2:
+        if nbytes <= 2 * _CHUNK:
+            _pull(t.contiguous(), dst.device, out=dst)
+        else:
+            dst.copy_(t)
+        return
+    rows = max(1, _CHUNK // (t.shape[1] * t.element_size()))
+    for i in range(0, t.shape[0], rows):
+        _pull(t[i:i + rows].contiguous(), dst.device, out=dst[i:i + rows])
 
 
 class StepThrottle(object):

@@ -106,13 +106,27 @@ class _DFunction(torch.autograd.Function):
             ops.sn_weight_prep(specs[7:], wps[7:], ldws[7:], training, scratch, offs[7:], sigma[7:], u_snaps[7:],
                                v_snaps[7:])
 
+        # every transformed Winograd filter the six trunk layers read, forward and data gradient, in one launch behind the
+        # weight prep (the conv calls made one each); the U buffers live in the ctx until the backward
+        filters = None
+        if ops.FILTER_PREP:
+            reqs, hw = [], (images.shape[2], images.shape[3])
+            for i in range(1, 7):
+                ci, co, k, s, p = _D_CONVS[i]
+                d = ops.fwd_desc((B, hw[0], hw[1], ci), wps[i], co, k, k, s, p)
+                reqs.append((0, d, wps[i]))
+                if trunk_grad:
+                    reqs.append((1, d, wps[i]))
+                hw = (d.Ho, d.Wo)
+            filters = ops.filter_prep(reqs, dev)
+
         biases = [m.bias for m in plan.layers]
         acts = []
         x = ops.rgb_conv_fwd(images, wps[0], biases[0], 64, 3, 2.0, -1.0, _SLOPE, 1.0)
         acts.append(x)
         for i in range(1, 7):
             ci, co, k, s, p = _D_CONVS[i]
-            x = ops.conv2d_fwd(x, wps[i], biases[i], co, k, k, s, p, _SLOPE, 1.0)
+            x = ops.conv2d_fwd(x, wps[i], biases[i], co, k, k, s, p, _SLOPE, 1.0, filters=filters)
             acts.append(x)
         bias_cat = torch.cat([biases[7], biases[8], biases[9]])
         # first head layers: Linear over the flattened features == 1x1 conv on the (B,1,1,hb*wb*512) NHWC view (the
@@ -126,7 +140,7 @@ class _DFunction(torch.autograd.Function):
             D._last_activations = (acts, hidden)
         ctx.plan, ctx.D = plan, D
         ctx.images, ctx.acts, ctx.hidden = images, acts, hidden
-        ctx.wps, ctx.ldws, ctx.merged, ctx.wbuf = wps, ldws, merged, wbuf
+        ctx.wps, ctx.ldws, ctx.merged, ctx.wbuf, ctx.filters = wps, ldws, merged, wbuf, filters
         ctx.sigma, ctx.u_snaps, ctx.v_snaps, ctx.snapbuf = sigma, u_snaps, v_snaps, snapbuf
         ctx.sg_linear, ctx.trunk_grad = sg_linear, trunk_grad
         ctx.param_shapes = [tuple(p.shape) for p in params]
@@ -193,11 +207,15 @@ class _DFunction(torch.autograd.Function):
                 exchange(gwps[li])
         # ---- heads, first (merged) layer ----
         if need_params:
-            gb_hidden = torch.empty(3 * dh, device=dev, dtype=torch.float32)
+            # the three bias gradients lie side by side in bbuf (dh is a multiple of 4): the kernel writes them in place
+            o7 = gbias[7].storage_offset()
+            adjacent = all(gbias[7 + j].storage_offset() == o7 + j * dh for j in range(3))
+            gb_hidden = bbuf[o7:o7 + 3 * dh] if adjacent else torch.empty(3 * dh, device=dev, dtype=torch.float32)
             ops.conv2d_wgrad(a6.view(B, 1, 1, plan.feat), g_hidden, 1, 1, 1, 0, out=gmerged, dbias=gb_hidden)
             exchange(gmerged)                  # 12.6 M of the 18.6 M parameters: hidden behind the trunk backward
-            for j in range(3):
-                gbias[7 + j].copy_(gb_hidden[j * dh:(j + 1) * dh])
+            if not adjacent:
+                for j in range(3):
+                    gbias[7 + j].copy_(gb_hidden[j * dh:(j + 1) * dh])
         g = None
         if ctx.trunk_grad:
             lo = dh if ctx.sg_linear else 0
@@ -215,7 +233,7 @@ class _DFunction(torch.autograd.Function):
                     ops.conv2d_wgrad(acts[i - 1], g, k, k, s, p, out=gwps[i], dbias=gbias[i])
                     exchange(gwps[i])
                 g = ops.conv2d_dgrad(g, wps[i], tuple(acts[i - 1].shape), k, k, s, p, act_ref=acts[i - 1],
-                                     slope=_SLOPE, gain=1.0)
+                                     slope=_SLOPE, gain=1.0, filters=ctx.filters)
             if need_params:
                 ops.rgb_conv_wgrad(images, g, 3, 2.0, -1.0, gwps[0], gbias[0])
                 exchange(gwps[0])
@@ -386,6 +404,7 @@ class G_SNDCGAN(nn.Module):
         self.sync_bn = True
         self._packed = None
         self._packed_key = None
+        self._packed_filters = {}
 
     def sample_latent(self, n_samples):
         # U(-1,1) from the CPU generator, as the reference (sndcgan.py:50-52); handed over by contrad_amd/hostio.py
@@ -395,7 +414,7 @@ class G_SNDCGAN(nn.Module):
     def invalidate_cache(self):
         """Forget the packed weights: the next forward re-packs (a captured step must RECORD the pack launch, and the
         buffers a capture allocated hold nothing until the first replay)."""
-        self._packed, self._packed_key = None, None
+        self._packed, self._packed_key, self._packed_filters = None, None, {}
 
     def _weights(self):
         ws = [self.linear.weight] + [self.main[3 * j].weight for j in range(4)]
@@ -412,7 +431,24 @@ class G_SNDCGAN(nn.Module):
             sigma = torch.empty(len(specs), device=dev, dtype=torch.float32)
             ops.sn_weight_prep(specs, wps, ldws, False, scratch, offs, sigma)
             self._packed, self._packed_key, self._packed_buf = wps, key, buf
+            self._packed_filters = {}
         return self._packed
+
+    def _filters(self, N):
+        """Transformed Winograd filters of the three transposed convs at batch ``N`` (the plan depends on it), made from
+        the current pack in one launch and kept with it: same key, same invalidate_cache(), so a captured step records
+        the launch and a changed G is never served a stale U.  Call right after _weights()."""
+        if not ops.FILTER_PREP:
+            return None
+        pf = self._packed_filters.get(N)
+        if pf is None:
+            reqs, H, W = [], self.s_hb, self.s_wb
+            for j in range(3):
+                ci, co, k, s, p = self._CONVT[j]
+                H, W = 2 * H, 2 * W
+                reqs.append((1, ops.dgrad_desc((N, H, W, co), self._packed[1 + j], ci, k, k, s, p), self._packed[1 + j]))
+            pf = self._packed_filters[N] = ops.filter_prep(reqs, self._packed[0].device)
+        return pf
 
     def _bn(self, x2d, bn, conv_bias, out2d, perm_hw=1):
         if not self.training:
@@ -423,8 +459,13 @@ class G_SNDCGAN(nn.Module):
             stats = torch.stack([mean, bn.running_var + mean * mean]).contiguous()
             ops.bn_relu_apply(x2d, out2d, stats, 1.0, bn.weight, bn.bias, bn.eps, perm_hw)
             return
-        stats = ops.colstats(x2d, with_sq=True)
         count = float(x2d.shape[0])
+        if ops.BN_FUSED and not _sync_on(self.sync_bn):
+            # one device: the launch that sums the partial statistics also updates the running ones
+            stats = ops.bn_batch_stats(x2d, conv_bias, bn.momentum, bn.running_mean, bn.running_var, bn.num_batches_tracked)
+            ops.bn_relu_apply(x2d, out2d, stats, count, bn.weight, bn.bias, bn.eps, perm_hw)
+            return
+        stats = ops.colstats(x2d, with_sq=True)
         if _sync_on(self.sync_bn):
             # SyncBatchNorm (train_gan.py:268): one packed all-reduce of {sum, sumsq} per layer over RCCL
             dist.all_reduce(stats)
@@ -472,6 +513,7 @@ class G_SNDCGAN(nn.Module):
             return self._forward_with_grad(z)
         wps = self._weights()
         N = z.shape[0]
+        filters = self._filters(N)
         hb, wb = self.s_hb, self.s_wb
         f = 512 * hb * wb
         z = z.contiguous().float()
@@ -481,7 +523,7 @@ class G_SNDCGAN(nn.Module):
         for j in range(3):
             ci, co, k, s, p = self._CONVT[j]
             H, W = x.shape[1], x.shape[2]
-            y = ops.conv2d_dgrad(x, wps[1 + j], (N, 2 * H, 2 * W, co), k, k, s, p)
+            y = ops.conv2d_dgrad(x, wps[1 + j], (N, 2 * H, 2 * W, co), k, k, s, p, filters=filters)
             y2 = ops.as_rows(y)
             self._bn(y2, self.main[3 * j + 1], self.main[3 * j].bias, y2)
             x = y

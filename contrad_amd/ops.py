@@ -7,10 +7,11 @@ Activations are NHWC: a tensor of shape (N, H, W, C) whose last dim is contiguou
 ``stride(2)`` is the leading dimension (allows channel-sliced views of wider buffers).
 """
 import ctypes
+import os
 
 import torch
 
-from ._lib import ConvDesc, lib
+from ._lib import ConvDesc, ContrastProblem, FilterBatch, FilterJob, FILTER_MAX_JOBS, L2normProblem, lib
 
 
 def _p(t):
@@ -150,8 +151,85 @@ def unpack_weight(wp, K, C, KH, KW):
 # --------------------------------------------------------------------------------------------------
 # convolution engine
 # --------------------------------------------------------------------------------------------------
-def conv2d_fwd(x, wp, bias, K, KH, KW, stride, pad, slope=1.0, gain=1.0, out=None, addend=None):
-    """x: (N,H,W,C) NHWC; wp packed (KH*KW*C, ldw); returns y (N,Ho,Wo,K) = gain * lrelu(conv + bias) [+ addend]."""
+# Transformed Winograd filters made once per weight prep (contrad_conv2d_filter_prep) instead of by every conv call.
+# (dev switch, read once: CONTRAD_DEV_FILTER_PREP=0 keeps the networks on the per-call transform, for A/B runs)
+FILTER_PREP = os.environ.get('CONTRAD_DEV_FILTER_PREP', '1') != '0'
+# (the same for the two other launch mergers of the D-step: both contrastive problems per launch, training/gan/contrad.py;
+# the BatchNorm statistics reduce and running update in one launch, models/gan/sndcgan.py)
+CONTRAST_PAIR = os.environ.get('CONTRAD_DEV_CONTRAST_PAIR', '1') != '0'
+BN_FUSED = os.environ.get('CONTRAD_DEV_BN_FUSED', '1') != '0'
+
+
+def filter_kind(d, mode):
+    """(kind, bytes) of the transformed filter conv2d_fwd (mode 0) / conv2d_dgrad (mode 1) read for descriptor ``d``; kind 0:
+    the plan takes a direct kernel."""
+    nb = ctypes.c_longlong(0)
+    kind = lib().raw('contrad_conv2d_filter_kind')(ctypes.byref(d), mode, ctypes.byref(nb))
+    if kind < 0:
+        raise RuntimeError('contrad_hip: bad conv descriptor (%d)' % kind)
+    return kind, nb.value
+
+
+def fwd_desc(x_shape, wp, K, KH, KW, stride, pad):
+    """Descriptor of conv2d_fwd on a dense NHWC input of ``x_shape`` writing a dense output."""
+    N, H, W, C = x_shape
+    return make_desc(N, H, W, C, K, KH, KW, stride, pad, C, K, wp.stride(0))
+
+
+def dgrad_desc(x_shape, wp, K, KH, KW, stride, pad):
+    """Descriptor of conv2d_dgrad producing a dense dx of ``x_shape`` from a dense gy with K channels."""
+    return fwd_desc(x_shape, wp, K, KH, KW, stride, pad)
+
+
+class PreparedFilters(object):
+    """Transformed Winograd filters of a set of layers, made by ONE launch (``filter_prep``) right after the weight prep
+    that packed their weights.  ``get`` hands the job of (mode, packed weight) to the conv call; the C side checks that
+    it fits the path the call plans and transforms per call otherwise, so a shape the request list did not foresee
+    (another batch size, a strided view) is slower, never wrong.  Holds the U storage: keep it alive until the last
+    consumer has been launched (the autograd ctx of D, the pack cache of G)."""
+
+    def __init__(self):
+        self.jobs = {}
+        self.buf = None
+
+    def get(self, mode, wp):
+        return self.jobs.get((mode, wp.data_ptr()))
+
+
+def filter_prep(requests, device):
+    """requests: iterable of (mode, ConvDesc, packed weight).  Allocates the U buffers (one allocation) and fills all of
+    them in one launch per FILTER_MAX_JOBS jobs; requests whose plan is not Winograd are dropped.  Allocates: call it where
+    the packed weights are allocated, never between launches of a step that must not allocate."""
+    pf = PreparedFilters()
+    todo, tot = [], 0
+    for mode, d, wp in requests:
+        kind, nb = filter_kind(d, mode)
+        if kind == 0 or (mode, wp.data_ptr()) in pf.jobs:
+            continue
+        _chk(wp, 'wp')
+        j = FilterJob(wp.data_ptr(), 0, kind, mode, d.C, d.K, d.ldw)
+        pf.jobs[(mode, wp.data_ptr())] = j
+        todo.append((j, tot))
+        tot += round_up(nb // 4, 4)
+    if not todo:
+        return pf
+    pf.buf = torch.empty(tot, device=device, dtype=torch.float32)
+    base = pf.buf.data_ptr()
+    for j, off in todo:
+        j.U = base + 4 * off
+    for start in range(0, len(todo), FILTER_MAX_JOBS):
+        b = FilterBatch()
+        chunk = todo[start:start + FILTER_MAX_JOBS]
+        b.n = len(chunk)
+        for i, (j, _) in enumerate(chunk):
+            b.jobs[i] = j
+        lib().call('contrad_conv2d_filter_prep', ctypes.byref(b), _stream())
+    return pf
+
+
+def conv2d_fwd(x, wp, bias, K, KH, KW, stride, pad, slope=1.0, gain=1.0, out=None, addend=None, filters=None):
+    """x: (N,H,W,C) NHWC; wp packed (KH*KW*C, ldw); returns y (N,Ho,Wo,K) = gain * lrelu(conv + bias) [+ addend].
+    ``filters``: a PreparedFilters that may hold this layer's transformed filter (the per-call transform is then skipped)."""
     _chk(x, 'x'); _chk(wp, 'wp'); _chk(bias, 'bias'); _chk(addend, 'addend')
     N, H, W, C = x.shape
     Ho, Wo = out_size(H, KH, stride, pad), out_size(W, KW, stride, pad)
@@ -163,13 +241,19 @@ def conv2d_fwd(x, wp, bias, K, KH, KW, stride, pad, slope=1.0, gain=1.0, out=Non
     ws = _workspace(nbytes, x.device) if nbytes > 0 else None
     if addend is not None and (tuple(addend.shape) != tuple(out.shape) or _ld(addend) != _ld(out)):
         raise RuntimeError('contrad_hip: addend must match y in shape and leading dimension')
+    u = filters.get(0, wp) if filters is not None else None
+    if u is not None:
+        _conv_call(0, d, 'contrad_conv2d_fwd_add_u', ctypes.byref(d), _p(x), _p(wp), _p(bias), _p(addend), _p(out),
+                   float(slope), float(gain), _p(ws), nbytes, ctypes.byref(u), _stream())
+        return out
     _conv_call(0, d, 'contrad_conv2d_fwd_add', ctypes.byref(d), _p(x), _p(wp), _p(bias), _p(addend), _p(out),
                float(slope), float(gain), _p(ws), nbytes, _stream())
     return out
 
 
-def conv2d_dgrad(gy, wp, x_shape, KH, KW, stride, pad, act_ref=None, slope=1.0, gain=1.0, out=None):
-    """gy: (N,Ho,Wo,K); returns dx (N,H,W,C) for x_shape=(N,H,W,C); optional fused act' of the producer."""
+def conv2d_dgrad(gy, wp, x_shape, KH, KW, stride, pad, act_ref=None, slope=1.0, gain=1.0, out=None, filters=None):
+    """gy: (N,Ho,Wo,K); returns dx (N,H,W,C) for x_shape=(N,H,W,C); optional fused act' of the producer.
+    ``filters``: as in conv2d_fwd."""
     _chk(gy, 'gy'); _chk(wp, 'wp'); _chk(act_ref, 'act_ref')
     N, H, W, C = x_shape
     K = gy.shape[3]
@@ -183,6 +267,11 @@ def conv2d_dgrad(gy, wp, x_shape, KH, KW, stride, pad, act_ref=None, slope=1.0, 
         raise RuntimeError('contrad_hip: gy spatial size does not match the conv geometry')
     nbytes = lib().raw('contrad_conv2d_dgrad_workspace_bytes')(ctypes.byref(d))
     ws = _workspace(nbytes, gy.device) if nbytes > 0 else None
+    u = filters.get(1, wp) if filters is not None else None
+    if u is not None:
+        _conv_call(1, d, 'contrad_conv2d_dgrad_ws_u', ctypes.byref(d), _p(gy), _p(wp), _p(out), _p(act_ref),
+                   float(slope), float(gain), _p(ws), nbytes, ctypes.byref(u), _stream())
+        return out
     _conv_call(1, d, 'contrad_conv2d_dgrad_ws', ctypes.byref(d), _p(gy), _p(wp), _p(out), _p(act_ref),
                float(slope), float(gain), _p(ws), nbytes, _stream())
     return out
@@ -364,6 +453,78 @@ def contrast_bwd(z, lse, N, mode, temperature, grad_scale=None):
     return dz
 
 
+# The same calls on two independent problems per launch (ContraD: NT-Xent on z1, SupCon on z2); every result is bitwise
+# that of the single call.
+def l2norm_fwd_pair(u1, u2):
+    """-> (z1, inv1, z2, inv2) in one launch."""
+    probs = (L2normProblem * 2)()
+    outs = []
+    for q, u in zip(probs, (u1, u2)):
+        _chk(u, 'u')
+        R, D = u.shape
+        z = torch.empty((R, D), device=u.device, dtype=torch.float32)
+        inv = torch.empty((R,), device=u.device, dtype=torch.float32)
+        q.u, q.ldu, q.z, q.inv_norm, q.R, q.D = u.data_ptr(), _ld(u), z.data_ptr(), inv.data_ptr(), R, D
+        outs += [z, inv]
+    lib().call('contrad_l2norm_fwd_batched', probs, 2, 1e-12, _stream())
+    return tuple(outs)
+
+
+def l2norm_bwd_pair(items):
+    """items: two of (dz, z, inv, out, zero_rows); rows [R, R + zero_rows) of ``out`` (a view of a taller buffer) get zeros.
+    One launch."""
+    probs = (L2normProblem * 2)()
+    for q, (dz, z, inv, out, zero_rows) in zip(probs, items):
+        R, D = z.shape
+        q.dz, q.z, q.inv_norm, q.du = dz.data_ptr(), z.data_ptr(), inv.data_ptr(), out.data_ptr()
+        q.ldu, q.R, q.D, q.accumulate, q.zero_rows = _ld(out), R, D, 0, int(zero_rows)
+    lib().call('contrad_l2norm_bwd_batched', probs, 2, _stream())
+
+
+def _contrast_pair(items, temperature):
+    probs = (ContrastProblem * 2)()
+    sizes = []
+    for z, N, mode in items:
+        _chk(z, 'z')
+        if not z.is_contiguous():
+            raise RuntimeError('contrad_hip: z must be contiguous')
+        sizes.append(round_up(lib().raw('contrad_contrast_workspace_bytes')(z.shape[0], z.shape[1]), 16))
+    ws = _workspace(sum(sizes), items[0][0].device)
+    off = 0
+    for q, (z, N, mode), nb in zip(probs, items, sizes):
+        q.z, q.R, q.D, q.N, q.mode, q.inv_temp = z.data_ptr(), z.shape[0], z.shape[1], N, mode, 1.0 / temperature
+        q.workspace, q.workspace_bytes = ws.data_ptr() + off, nb
+        off += nb
+    return probs, ws
+
+
+def contrast_fwd_pair(z1, N1, mode1, z2, N2, mode2, temperature):
+    """-> (loss1, lse1, loss2, lse2): contrast_fwd of both problems in one pair of launches."""
+    probs, ws = _contrast_pair(((z1, N1, mode1), (z2, N2, mode2)), temperature)
+    outs = []
+    for q, z in zip(probs, (z1, z2)):
+        R = z.shape[0]
+        lse = torch.empty((R,), device=z.device, dtype=torch.float32)
+        rowloss = torch.empty((R,), device=z.device, dtype=torch.float32)
+        loss = torch.empty((1,), device=z.device, dtype=torch.float32)
+        q.lse, q.rowloss, q.loss = lse.data_ptr(), rowloss.data_ptr(), loss.data_ptr()
+        outs += [loss, lse, rowloss]
+    lib().call('contrad_contrast_fwd_batched', probs, 2, _stream())
+    return outs[0], outs[1], outs[3], outs[4]
+
+
+def contrast_bwd_pair(z1, lse1, N1, mode1, gs1, z2, lse2, N2, mode2, gs2, temperature):
+    """-> (dz1, dz2): contrast_bwd of both problems in one pair of launches."""
+    probs, ws = _contrast_pair(((z1, N1, mode1), (z2, N2, mode2)), temperature)
+    outs = []
+    for q, z, lse, gs in zip(probs, (z1, z2), (lse1, lse2), (gs1, gs2)):
+        dz = torch.empty(tuple(z.shape), device=z.device, dtype=torch.float32)
+        q.lse, q.grad_scale, q.dz = lse.data_ptr(), (gs.data_ptr() if gs is not None else None), dz.data_ptr()
+        outs.append(dz)
+    lib().call('contrad_contrast_bwd_batched', probs, 2, _stream())
+    return outs[0], outs[1]
+
+
 # --------------------------------------------------------------------------------------------------
 # weight preparation (spectral norm / fixed scale + packing), batched
 # --------------------------------------------------------------------------------------------------
@@ -509,6 +670,21 @@ def bn_running_update(stats, count, conv_bias, momentum, running_mean, running_v
         raise RuntimeError('contrad_hip: num_batches_tracked must be an int64 tensor on the device')
     lib().call('contrad_bn_running_update', _p(stats), float(count), K, _p(conv_bias), float(momentum),
                _p(running_mean), _p(running_var), _p(num_batches_tracked), _stream())
+
+
+def bn_batch_stats(x2d, conv_bias, momentum, running_mean, running_var, num_batches_tracked=None):
+    """colstats(x2d, with_sq=True) + bn_running_update(count = rows) in two launches instead of three; returns stats (2, K)."""
+    _chk(x2d, 'x')
+    M, K = x2d.shape
+    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or not num_batches_tracked.is_cuda):
+        raise RuntimeError('contrad_hip: num_batches_tracked must be an int64 tensor on the device')
+    out = torch.empty((2, K), device=x2d.device, dtype=torch.float32)
+    nbytes = lib().raw('contrad_colstats_workspace_bytes')(ctypes.c_longlong(M), K, 1)
+    ws = _workspace(nbytes, x2d.device)
+    lib().call('contrad_bn_batch_stats', _p(x2d), ctypes.c_longlong(M), K, _ld(x2d), _p(out), _p(conv_bias),
+               float(momentum), _p(running_mean), _p(running_var), _p(num_batches_tracked), _p(ws),
+               ctypes.c_longlong(ws.numel() * 4), _stream())
+    return out
 
 
 GAN_LOSS_KINDS = {'nonsat': 0, 'wgan': 1, 'hinge': 2, 'lsgan': 3}

@@ -37,11 +37,20 @@ class _ContraDContrastive(torch.autograd.Function):
     @staticmethod
     def forward(ctx, proj, proj2, N, temperature, distributed):
         D = proj.shape[1]
-        z1, inv1 = ops.l2norm_fwd(proj[:2 * N])
-        z2, inv2 = ops.l2norm_fwd(proj2)
         from ...engine import dist_on
         world, rank = 1, 0
-        if distributed and dist_on():
+        gathered = distributed and dist_on()
+        if not gathered and ops.CONTRAST_PAIR:
+            # both problems per launch (csrc/ntxent.hip): NT-Xent on 2N rows and SupCon on 3N rows each leave most of the
+            # chip idle; results are bitwise those of the separate calls below
+            z1, inv1, z2, inv2 = ops.l2norm_fwd_pair(proj[:2 * N], proj2)
+            l1, lse1, l2, lse2 = ops.contrast_fwd_pair(z1, N, MODE_NT_XENT, z2, N, MODE_SUPCON_FAKE, temperature)
+            ctx.save_for_backward(z1, inv1, z2, inv2, z1, z2, lse1, lse2)
+            ctx.cfg = (N, N, temperature, world, rank, tuple(proj.shape), D)
+            return l1.reshape(()), l2.reshape(())
+        z1, inv1 = ops.l2norm_fwd(proj[:2 * N])
+        z2, inv2 = ops.l2norm_fwd(proj2)
+        if gathered:
             world, rank = dist.get_world_size(), dist.get_rank()
             packed = torch.cat([z1, z2], dim=0)                      # (5N, D): one message per rank
             g = all_gather_rows(packed)                              # (W, 5N, D) over RCCL / xGMI
@@ -60,6 +69,15 @@ class _ContraDContrastive(torch.autograd.Function):
     def backward(ctx, g1, g2):
         z1, inv1, z2, inv2, z1g, z2g, lse1, lse2 = ctx.saved_tensors
         N, Ng, temperature, world, rank, pshape, D = ctx.cfg
+        if world == 1 and ops.CONTRAST_PAIR:
+            gs1, gs2 = g1.reshape(1).contiguous().float(), g2.reshape(1).contiguous().float()
+            dz1, dz2 = ops.contrast_bwd_pair(z1g, lse1, Ng, MODE_NT_XENT, gs1, z2g, lse2, Ng, MODE_SUPCON_FAKE, gs2,
+                                             temperature)
+            dproj = torch.empty(pshape, device=z1.device, dtype=torch.float32)
+            dproj2 = torch.empty(pshape, device=z1.device, dtype=torch.float32)
+            # (rows 2N: of dproj, which NT-Xent does not read, are zeroed by the same launch)
+            ops.l2norm_bwd_pair(((dz1, z1, inv1, dproj[:2 * N], pshape[0] - 2 * N), (dz2, z2, inv2, dproj2, 0)))
+            return dproj, dproj2, None, None, None
         dz1 = ops.contrast_bwd(z1g, lse1, Ng, MODE_NT_XENT, temperature, g1.reshape(1).contiguous().float())
         dz2 = ops.contrast_bwd(z2g, lse2, Ng, MODE_SUPCON_FAKE, temperature, g2.reshape(1).contiguous().float())
         if world > 1:   # GatherLayer.backward semantics: keep this rank's rows only

@@ -123,6 +123,48 @@ int contrad_conv2d_wino44(const contrad_conv_desc* d, int mode, const float* in,
                           const float* ref, float* out, float slope, float gain, float* workspace,
                           long long workspace_bytes, contrad_stream_t stream);
 
+/* Transformed Winograd filters made ahead of the convolutions (csrc/igemm.hip: filter_prep_kernel).  The entry points above
+ * rebuild U = G g G^T from the packed weight in a small launch of their own on every call; a network whose packed weights
+ * all come from one contrad_sn_weight_prep makes every U it needs in ONE launch right after it and hands each to the
+ * call that consumes it:
+ *   1. contrad_conv2d_filter_kind(d, mode, &bytes): which transformed filter contrad_conv2d_fwd_add (mode 0) /
+ *      contrad_conv2d_dgrad_ws (mode 1) read for this descriptor WHEN GIVEN THEIR WORKSPACE -- 0: none (a direct kernel),
+ *      else the contrad_conv2d_path number of the family: 7 F(2x2,3x3), 8 F(2x2,2x2) on 4x4 stride 2, 9 F(4x4,3x3) (paths
+ *      9 and 11 read the same U), 10 F(2x2,2x2) on 3x3 stride 2 -- and its size in bytes (16 / 36 / 36 / 36 * C * K
+ *      floats; *bytes = 0 for kind 0; bytes may be NULL).  The plan depends on the whole descriptor, N included.
+ *      Negative = bad descriptor.
+ *   2. contrad_conv2d_filter_prep(batch): fills every job's U (caller-allocated, 16-byte aligned, `bytes` long) from
+ *      its packed weight wp [KH*KW*C][ldw]; C, K, ldw are the descriptor's.  One launch for the whole batch; U's bits
+ *      are those the per-call transform writes.  -22 for an unknown kind / mode, misaligned pointers or n out of range.
+ *   3. contrad_conv2d_fwd_add_u / contrad_conv2d_dgrad_ws_u: contrad_conv2d_fwd_add / contrad_conv2d_dgrad_ws with the
+ *      job `u` (a HOST struct, read during the call only; may be NULL) whose U was prepared.  The call checks on the host
+ *      that `u` fits the path it is about to take -- same kind as the plan of (d, mode) with this workspace, same mode, C, K,
+ *      ldw and the same wp pointer -- and then launches the main kernel alone, reading u->U; otherwise it behaves exactly
+ *      like the entry point without `_u` (per-call transform into `workspace`, or a direct kernel).  The workspace
+ *      arguments keep their meaning: a call without the workspace of *_workspace_bytes does not take a Winograd path,
+ *      with or without `u`.  The caller keeps u->U unchanged from the prep until the consuming launch has run. */
+#define CONTRAD_FILTER_MAX_JOBS 16
+typedef struct {
+  const float* wp;   /* packed weight [KH*KW*C][ldw]                                              */
+  float* U;          /* transformed filter (out of the prep, in of the conv call)                 */
+  int kind;          /* 7, 8, 9 or 10: contrad_conv2d_filter_kind                                 */
+  int mode;          /* 0: for contrad_conv2d_fwd_add_u, 1: for contrad_conv2d_dgrad_ws_u         */
+  int C, K, ldw;     /* the descriptor's input channels, output channels, packed leading dimension */
+} contrad_filter_job;
+typedef struct {
+  int n;
+  contrad_filter_job jobs[CONTRAD_FILTER_MAX_JOBS];
+  int block_start[CONTRAD_FILTER_MAX_JOBS + 1]; /* filled by the launcher */
+} contrad_filter_batch;
+int contrad_conv2d_filter_kind(const contrad_conv_desc* d, int mode, long long* bytes);
+int contrad_conv2d_filter_prep(const contrad_filter_batch* b, contrad_stream_t stream);
+int contrad_conv2d_fwd_add_u(const contrad_conv_desc* d, const float* x, const float* wp, const float* bias,
+                             const float* addend, float* y, float slope, float gain, float* workspace,
+                             long long workspace_bytes, const contrad_filter_job* u, contrad_stream_t stream);
+int contrad_conv2d_dgrad_ws_u(const contrad_conv_desc* d, const float* gy, const float* wp, float* dx,
+                              const float* act_ref, float slope, float gain, float* workspace,
+                              long long workspace_bytes, const contrad_filter_job* u, contrad_stream_t stream);
+
 /* dwp[(kh,kw,c),k] = sum_{n,ho,wo} x[n,ho*s-p+kh,wo*s-p+kw,c] * gy[n,ho,wo,k]      (split over the
  * n*ho*wo axis into deterministic partial slabs in `workspace`, then reduced in fixed order).
  * dbias (may be NULL; needs C, K, ldx, ldy multiples of 4): dbias[k] = sum_{n,ho,wo} gy[n,ho,wo,k], the bias
@@ -190,6 +232,43 @@ int contrad_l2norm_fwd(const float* u, int ldu, float* z, float* inv_norm, int R
 /* du (+)= (dz - z <z,dz>) * inv_norm */
 int contrad_l2norm_bwd(const float* dz, const float* z, const float* inv_norm, float* du, int ldu, int R,
                        int D, int accumulate, contrad_stream_t stream);
+
+/* The same four calls on up to two independent problems per launch (ContraD's D-step runs NT-Xent on 2N rows and SupCon
+ * on 3N rows; each alone fills a fraction of the chip): one grid over both for the main kernel and one for each reduce.
+ * Every problem keeps its own column splits, workspace (contrad_contrast_workspace_bytes each, disjoint) and fixed summation
+ * order, so each result is bitwise that of the single-problem call.  Problems whose D fall into different kernel instances
+ * (D <= 64, <= 128, <= 256) are launched one after the other.  `p` is a HOST array, read during the call only.
+ *   forward:  reads z, R, D, N, mode, inv_temp;  writes lse[R], rowloss[R], loss[1].
+ *   backward: reads z, lse, grad_scale (may be NULL);  writes dz[R,D]. */
+#define CONTRAD_CONTRAST_MAX_PROBLEMS 2
+typedef struct {
+  const float* z;          /* [R][D] row-normalised                                   */
+  int R, D, N, mode;
+  float inv_temp;
+  float* lse;              /* [R]  out of the forward, in of the backward             */
+  float* rowloss;          /* [R]  forward scratch                                    */
+  float* loss;             /* [1]  forward out                                        */
+  const float* grad_scale; /* backward, may be NULL                                   */
+  float* dz;               /* [R][D] backward out                                     */
+  float* workspace;
+  long long workspace_bytes;
+} contrad_contrast_problem;
+int contrad_contrast_fwd_batched(const contrad_contrast_problem* p, int n, contrad_stream_t stream);
+int contrad_contrast_bwd_batched(const contrad_contrast_problem* p, int n, contrad_stream_t stream);
+/* contrad_l2norm_fwd / _bwd on up to two matrices per launch.  Backward only: rows [R, R + zero_rows) of du are set to
+ * zero by the same launch (the projection rows a loss does not read get their zero gradient without a fill of their own). */
+typedef struct {
+  const float* u;          /* forward in  [R][ldu]                                    */
+  float* z;                /* [R][D]  forward out, backward in                        */
+  float* inv_norm;         /* [R]     forward out, backward in                        */
+  const float* dz;         /* [R][D]  backward in                                     */
+  float* du;               /* [R + zero_rows][ldu] backward out                       */
+  int ldu, R, D;
+  int accumulate;          /* backward: du += (rows below R only)                     */
+  int zero_rows;
+} contrad_l2norm_problem;
+int contrad_l2norm_fwd_batched(const contrad_l2norm_problem* p, int n, float eps, contrad_stream_t stream);
+int contrad_l2norm_bwd_batched(const contrad_l2norm_problem* p, int n, contrad_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Weight preparation, batched over the layers of a network: spectral normalisation (one power
@@ -279,6 +358,14 @@ int contrad_bn_relu_bwd_apply(const float* dy, const float* x, float* dx, long l
 int contrad_bn_running_update(const float* stats, float count, int K, const float* conv_bias, float momentum,
                               float* running_mean, float* running_var, long long* num_batches_tracked,
                               contrad_stream_t stream);
+/* The batch statistics of a train-mode BatchNorm on one device in two launches: stats[2][K] = {sum, sumsq} over the M rows of
+ * x (contrad_colstats with with_sq = 1: the same partial sums, lanes and order, bitwise the same stats) and, by the launch
+ * that sums the partials, contrad_bn_running_update with count = M (conv_bias / num_batches_tracked may be NULL).
+ * SyncBatchNorm needs the reduced stats for its all-reduce BEFORE the running update and keeps the separate calls.
+ * workspace: contrad_colstats_workspace_bytes(M, K, 1). */
+int contrad_bn_batch_stats(const float* x, long long M, int K, int ld, float* stats, const float* conv_bias,
+                           float momentum, float* running_mean, float* running_var, long long* num_batches_tracked,
+                           float* workspace, long long workspace_bytes, contrad_stream_t stream);
 /* contrad.loss_D_fn's GAN term (training/gan/contrad.py:51-64) on logits[3N] (stride ld): kind 0 nonsat,
  * 1 wgan, 2 hinge, 3 lsgan.  out3 = {loss, mean d_real, mean d_gen}; grad[3N] = d loss / d logits. */
 int contrad_gan_d_loss(const float* logits, int ld, int N, int kind, float* out3, float* grad,
