@@ -19,12 +19,18 @@
 // Development switches (tile modes, split-K on/off, forced tiles ...; tools/README.md) exist only in the variant built with
 // -DCONTRAD_DEV_SWITCHES (libcontrad_hip_dev.so, contrad_amd/build.py; tools/build_variant.sh): the shipped library never
 // reads its environment, so an integrator's environment cannot change a launch plan (no hidden state).
-#ifdef CONTRAD_DEV_SWITCHES
 #include <stdlib.h>
+#ifdef CONTRAD_DEV_SWITCHES
 static inline const char* contrad_dev_env(const char* name) { return getenv(name); }
 #else
 static inline const char* contrad_dev_env(const char*) { return nullptr; }
 #endif
+// The forms a switch takes (read once: `static const bool enabled = contrad_dev_on("CONTRAD_X");`): on unless "0", off
+// unless "1", an integer with a default.  The shipped build folds each to its default and keeps neither name nor call.
+static inline bool contrad_dev_on(const char* name) { const char* e = contrad_dev_env(name); return !(e && e[0] == '0'); }
+static inline bool contrad_dev_off_by_default(const char* name) { const char* e = contrad_dev_env(name); return e && e[0] == '1'; }
+static inline int contrad_dev_int(const char* name, int dflt) { const char* e = contrad_dev_env(name); return e ? atoi(e) : dflt; }
+static inline long long contrad_dev_ll(const char* name, long long dflt) { const char* e = contrad_dev_env(name); return e ? atoll(e) : dflt; }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

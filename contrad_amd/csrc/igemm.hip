@@ -864,24 +864,29 @@ long long wino_items(const contrad_conv_desc* d, int mode) {
 }
 
 constexpr int WINO_CUS = 256;      // one persistent block per CU of the MI355X
+
+// The transformed filter U a Winograd family reads: its kind is the family's contrad_conv2d_path number (9 serves 11 too), and
+// its bytes are the workspace such a call needs (16 transform points per filter for F(2x2, 3x3), 36 for the others).
+enum { FILTER_WINO = 7, FILTER_WINO22 = 8, FILTER_WINO44 = 9, FILTER_WINO23 = 10 };
+long long filter_bytes(int kind, const contrad_conv_desc* d) {
+  return (kind == FILTER_WINO ? 16ll : 36ll) * d->C * d->K * (long long)sizeof(float);
+}
 bool wino44_planned(const contrad_conv_desc* d, int mode);     // (below: F(4x4, 3x3) goes first)
 
 // Does the plan send the layer there?  A block is a whole CU and an item (64 tiles x 64 couts x all channels) its unit of
 // work: the launch needs about a round of items, and the last round must not be mostly empty.
 bool wino_planned(const contrad_conv_desc* d, int mode) {
-  static const bool enabled = []() { const char* e = contrad_dev_env("CONTRAD_WINO"); return !(e && e[0] == '0'); }();
+  static const bool enabled = contrad_dev_on("CONTRAD_WINO");
   if (!enabled || !wino_ok(d, mode)) return false;
   if (wino44_planned(d, mode)) return false;       // (F(4x4, 3x3) takes the launch)
   const long long items = wino_items(d, mode);
   const long long rounds = cdivll(items, WINO_CUS);
-  static const long long min_items = []() { const char* e = contrad_dev_env("CONTRAD_WINO_MIN_ITEMS"); return e ? atoll(e) : 150ll; }();
+  static const long long min_items = contrad_dev_ll("CONTRAD_WINO_MIN_ITEMS", 150ll);
   // (a single partial round: from 150 items.  Per-rank batches of the headline config on one GPU, profiles/r06_ab_plan_thresholds.txt:
   // 200 / 150 / 90 items -> 3.12 / 2.82 / 2.89 ms per step at batch 64, 4.39 / 4.25 / 4.24 at batch 128)
   if (items < WINO_CUS) return items >= min_items;
   return rounds * WINO_CUS * 10 <= items * 14;
 }
-
-long long wino_workspace_bytes(const contrad_conv_desc* d) { return 16ll * d->C * d->K * (long long)sizeof(float); }
 
 int wino_grid(const wino::Args& a) {
   const int l0 = cdiv(a.NP, 8) * a.NKB;           // items of the fullest XCD
@@ -911,7 +916,7 @@ bool wino44_ok(const contrad_conv_desc* d, int mode) {
 // Does a launch of `items` whole-CU items fill the chip well enough?  A single round from 230 items, else a last round that is not
 // mostly empty (rounds x CUs <= 1.4 x items).
 static inline bool wino44_round_ok(long long items) {
-  static const long long min_items = []() { const char* e = contrad_dev_env("CONTRAD_WINO44_MIN_ITEMS"); return e ? atoll(e) : 230ll; }();
+  static const long long min_items = contrad_dev_ll("CONTRAD_WINO44_MIN_ITEMS", 230ll);
   if (items < WINO_CUS) return items >= min_items;
   return cdivll(items, WINO_CUS) * WINO_CUS * 10 <= items * 14;
 }
@@ -928,8 +933,8 @@ static inline long long wino44_patches(const contrad_conv_desc* d) {
 // 0.24 ms; of 16 x 16 x 128: 0.095 -> 0.079 ms -- with enough items the 64-wide blocks are 10 - 25 % faster: one exchange and one
 // transform of V per 64 couts instead of per 32, profiles/r06_ab_wino44n_plan.txt)
 static inline bool wino44_n32(const contrad_conv_desc* d, int mode) {
-  static const bool all = []() { const char* e = contrad_dev_env("CONTRAD_WINO44N_ALL"); return e && e[0] == '1'; }();      // (dev: every shape on it)
-  static const bool fill = []() { const char* e = contrad_dev_env("CONTRAD_WINO44N_FILL"); return !(e && e[0] == '0'); }();  // (dev: the third rule off)
+  static const bool all = contrad_dev_off_by_default("CONTRAD_WINO44N_ALL");      // (dev: every shape on it)
+  static const bool fill = contrad_dev_on("CONTRAD_WINO44N_FILL");  // (dev: the third rule off)
   const int cout = mode == MODE_FWD ? d->K : d->C;
   if ((cout & 63) != 0 || d->W == 4 || all) return true;
   const long long items64 = wino44_patches(d) * (cout / 64);
@@ -962,15 +967,13 @@ long long wino44_items(const contrad_conv_desc* d, int mode) {
 // An item is 512 output pixels x 64 (32) couts x all channels on a whole CU: twice wino.h's.  The plan takes F(4x4, 3x3) when the
 // launch has a full round of them and its last round is not mostly empty; else the layer falls through to wino_planned.
 bool wino44_planned(const contrad_conv_desc* d, int mode) {
-  static const bool enabled = []() { const char* e = contrad_dev_env("CONTRAD_WINO44"); return !(e && e[0] == '0'); }();
-  static const bool enabled2 = []() { const char* e = contrad_dev_env("CONTRAD_WINO"); return !(e && e[0] == '0'); }();
+  static const bool enabled = contrad_dev_on("CONTRAD_WINO44");
+  static const bool enabled2 = contrad_dev_on("CONTRAD_WINO");
   if (!enabled || !enabled2 || !wino44_ok(d, mode)) return false;
-  static const bool enabled_n = []() { const char* e = contrad_dev_env("CONTRAD_WINO44N"); return !(e && e[0] == '0'); }();
+  static const bool enabled_n = contrad_dev_on("CONTRAD_WINO44N");
   if (!enabled_n && wino44_n32(d, mode)) return false;       // (32-wide cout blocks: wino44n.h)
   return wino44_round_ok(wino44_items(d, mode));
 }
-
-long long wino44_workspace_bytes(const contrad_conv_desc* d) { return 36ll * d->C * d->K * (long long)sizeof(float); }
 
 int wino44_grid(const wino44::Args& a) {
   const int l0 = cdiv(a.NP, 8) * a.NKB;           // items of the fullest XCD
@@ -1051,18 +1054,18 @@ long long wino22_items(const contrad_conv_desc* d, int mode) {
 }
 
 bool wino22_planned(const contrad_conv_desc* d, int mode) {
-  static const bool enabled = []() { const char* e = contrad_dev_env("CONTRAD_WINO22"); return !(e && e[0] == '0'); }();
+  static const bool enabled = contrad_dev_on("CONTRAD_WINO22");
   if (!enabled || !wino22_ok(d, mode)) return false;
   const long long items = wino22_items(d, mode);
   const long long rounds = cdivll(items, WINO_CUS);
   // (1.78x fewer multiply-adds, not 2.25x: a last round that is a quarter empty already loses to the direct kernels -- forward of
   // 256 -> 512 channels at 1536 images, 384 items: 0.622 ms against 0.558, profiles/r06_ab_wino22_layers.txt)
-  static const long long min_items = []() { const char* e = contrad_dev_env("CONTRAD_WINO22_MIN_ITEMS"); return e ? atoll(e) : 150ll; }();
+  static const long long min_items = contrad_dev_ll("CONTRAD_WINO22_MIN_ITEMS", 150ll);
   if (items < WINO_CUS) return items >= min_items;
   return rounds * WINO_CUS * 100 <= items * 125;
 }
 
-long long wino22_workspace_bytes(const contrad_conv_desc* d) { return 4ll * 9 * d->C * d->K * (long long)sizeof(float); }
+int wino22_grid(const wino22::Args& a) { return 8 * std::min(WINO_CUS / 8, cdiv(a.NTB, 8) * a.NKB * (a.dgrad ? 4 : 1)); }
 
 template <int MODE, int NRAW>
 int launch_wino22_inst(const wino22::Args& a, int blocks, hipStream_t stream) {
@@ -1082,8 +1085,7 @@ int launch_wino22(const contrad_conv_desc* d, const float* in, const float* wp, 
   const int quads = 4 * (a.Cin / 4) * a.Cout;
   if (!Uprep) hipLaunchKernelGGL(wino22::wino22_filter_kernel<MODE>, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
   CONTRAD_CHECK_LAUNCH();
-  const int l0 = cdiv(a.NTB, 8) * a.NKB * (MODE == MODE_DGRAD ? 4 : 1);
-  const int blocks = 8 * std::min(WINO_CUS / 8, l0);
+  const int blocks = wino22_grid(a);
   const int items = 2 * a.NIMG * (a.GH + 1) * (a.GW + 1);      // raw box pieces per chunk (pixel x k-quad)
   const int nraw = cdiv(items, 256);
   if (nraw <= 5) return launch_wino22_inst<MODE, 5>(a, blocks, stream);
@@ -1122,15 +1124,13 @@ wino23::Args wino23_args(const contrad_conv_desc* d) {
 }
 
 bool wino23_planned(const contrad_conv_desc* d, int mode) {
-  static const bool enabled = []() { const char* e = contrad_dev_env("CONTRAD_WINO23"); return !(e && e[0] == '0'); }();
+  static const bool enabled = contrad_dev_on("CONTRAD_WINO23");
   if (!enabled || !wino23_ok(d, mode)) return false;
   const wino23::Args a = wino23_args(d);
   const long long items = (long long)a.NP * a.NKB;
   if (items < WINO_CUS) return items >= 230;
   return cdivll(items, WINO_CUS) * WINO_CUS * 10 <= items * 14;
 }
-
-long long wino23_workspace_bytes(const contrad_conv_desc* d) { return 4ll * 9 * d->C * d->K * (long long)sizeof(float); }
 
 int wino23_grid(const wino23::Args& a) { return 8 * std::min(WINO_CUS / 8, cdiv(a.NP, 8) * a.NKB); }
 
@@ -1184,14 +1184,15 @@ wino22::WArgs wino22_wgrad_args(const contrad_conv_desc* d) {
   return a;
 }
 int wino22_wgrad_splits(const wino22::WArgs& a) { return cdiv(a.Q, a.qps); }
+int wino22_wgrad_grid(const wino22::WArgs& a) { return a.RBN * a.KB * wino22_wgrad_splits(a); }
 
 bool wino22_wgrad_planned(const contrad_conv_desc* d) {
-  static const bool enabled = []() { const char* e = contrad_dev_env("CONTRAD_WINO22_WGRAD"); return !(e && e[0] == '0'); }();
-  static const bool enabled2 = []() { const char* e = contrad_dev_env("CONTRAD_WINO22"); return !(e && e[0] == '0'); }();
+  static const bool enabled = contrad_dev_on("CONTRAD_WINO22_WGRAD");
+  static const bool enabled2 = contrad_dev_on("CONTRAD_WINO22");
   if (!enabled || !enabled2 || !wino22_wgrad_ok(d)) return false;
   const wino22::WArgs a = wino22_wgrad_args(d);
-  const long long blocks = (long long)a.RBN * a.KB * wino22_wgrad_splits(a);
-  static const int min_qps = []() { const char* e = contrad_dev_env("CONTRAD_WINO_MIN_QPS"); return e ? atoi(e) : 16; }();
+  const long long blocks = wino22_wgrad_grid(a);
+  static const int min_qps = contrad_dev_int("CONTRAD_WINO_MIN_QPS", 16);
   return a.qps >= min_qps && blocks * 10 >= WINO_CUS * 7 && blocks <= WINO_CUS;
 }
 
@@ -1227,15 +1228,16 @@ wino::WArgs wino_wgrad_args(const contrad_conv_desc* d) {
   return a;
 }
 int wino_wgrad_splits(const wino::WArgs& a) { return cdiv(a.Q, a.qps); }
+int wino_wgrad_grid(const wino::WArgs& a) { return a.CB * a.KB * wino_wgrad_splits(a); }
 
 // planned when every block gets a contraction long enough to pay for its prologue and its 4x4 -> 3x3 epilogue
 bool wino_wgrad_planned(const contrad_conv_desc* d) {
-  static const bool enabled = []() { const char* e = contrad_dev_env("CONTRAD_WINO_WGRAD"); return !(e && e[0] == '0'); }();
-  static const bool enabled2 = []() { const char* e = contrad_dev_env("CONTRAD_WINO"); return !(e && e[0] == '0'); }();
+  static const bool enabled = contrad_dev_on("CONTRAD_WINO_WGRAD");
+  static const bool enabled2 = contrad_dev_on("CONTRAD_WINO");
   if (!enabled || !enabled2 || !wino_wgrad_ok(d)) return false;
   const wino::WArgs a = wino_wgrad_args(d);
-  const long long blocks = (long long)a.CB * a.KB * wino_wgrad_splits(a);
-  static const int min_qps = []() { const char* e = contrad_dev_env("CONTRAD_WINO_MIN_QPS"); return e ? atoi(e) : 16; }();
+  const long long blocks = wino_wgrad_grid(a);
+  static const int min_qps = contrad_dev_int("CONTRAD_WINO_MIN_QPS", 16);
   return a.qps >= min_qps && blocks * 10 >= WINO_CUS * 7 && blocks <= WINO_CUS;
 }
 
@@ -1263,8 +1265,6 @@ int launch_wino(const contrad_conv_desc* d, const float* in, const float* wp, co
 // ---------------- every transformed filter of a network in one launch (contrad_conv2d_filter_prep) ----------------
 // Block b serves the job j with block_start[j] <= b < block_start[j + 1]; its threads do what the threads of the job's own
 // *_filter_kernel do (the filter_quad functions of wino.h, wino22.h, wino23.h, wino44.h: the same arithmetic, the same bits).
-enum { FILTER_WINO = 7, FILTER_WINO22 = 8, FILTER_WINO44 = 9, FILTER_WINO23 = 10 };
-
 __global__ __launch_bounds__(256) void filter_prep_kernel(const contrad_filter_batch b) {
   int j = 0;
   while (j + 1 < b.n && (int)blockIdx.x >= b.block_start[j + 1]) ++j;
@@ -1290,19 +1290,6 @@ long long filter_threads(int kind, int mode, int C, int K) {
   if (kind == FILTER_WINO22) return 4 * quads;
   if (kind == FILTER_WINO23) return mode == MODE_FWD ? 4 * quads : 0;
   return 0;
-}
-
-// The transformed filter the planned path of (d, mode) reads when the call has its workspace: the order of
-// contrad_conv2d_fwd_add / contrad_conv2d_dgrad_ws.  0 = a direct kernel.
-int filter_kind_planned(const contrad_conv_desc* d, int mode, long long* bytes) {
-  long long nb = 0;
-  int kind = 0;
-  if (wino44_planned(d, mode)) { kind = FILTER_WINO44; nb = wino44_workspace_bytes(d); }
-  else if (wino_planned(d, mode)) { kind = FILTER_WINO; nb = wino_workspace_bytes(d); }
-  else if (wino22_planned(d, mode)) { kind = FILTER_WINO22; nb = wino22_workspace_bytes(d); }
-  else if (mode == MODE_FWD && wino23_planned(d, mode)) { kind = FILTER_WINO23; nb = wino23_workspace_bytes(d); }
-  if (bytes) *bytes = nb;
-  return kind;
 }
 
 // Was `u` made for the path this call is about to take?  (host check: kind, mode, shape and the weight it was made from)
@@ -1341,7 +1328,7 @@ int launch_lean(const IgemmArgs& a, dim3 grid, hipStream_t stream) {
 
 // Does the shape fit the lean loop (igemm_lean.h)?  pps = WGRAD position tiles per split.
 bool lean_ok(const contrad_conv_desc* d, int mode, long long pps) {
-  static const bool enabled = []() { const char* e = contrad_dev_env("CONTRAD_IGEMM_LEAN"); return !(e && e[0] == '0'); }();
+  static const bool enabled = contrad_dev_on("CONTRAD_IGEMM_LEAN");
   if (!enabled || BK != 16) return false;
   const long long lim = 1ll << 31;
   if (d->KH * d->KW > 32) return false;
@@ -1399,7 +1386,7 @@ void pick_tile(long long M, int Ncol, bool vec, bool lean, int mult4, int* bm, i
   // back is the instruction overhead per block -- prologue, epilogue and loop control around only 144 MFMAs per wave --
   // plus the loop's memory instructions: ablation table in DESIGN.md section 7, tools/dev/ablate32.sh.)
   if (lean && Ncol <= 32) { *bm = 128; *bn = 32; return; }
-  static const int forced = []() { const char* e = contrad_dev_env("CONTRAD_IGEMM_TILE"); return e ? atoi(e) : 0; }();  // dev: "128064"
+  static const int forced = contrad_dev_int("CONTRAD_IGEMM_TILE", 0);  // dev: "128064"
   if (forced) { *bm = forced / 1000; *bn = forced % 1000; return; }
   if (g_plan_override.bm > 0) { *bm = g_plan_override.bm; *bn = g_plan_override.bn; return; }
   static const int cand[4][2] = {{128, 128}, {64, 128}, {128, 64}, {64, 64}};
@@ -1448,32 +1435,36 @@ int check_desc(const contrad_conv_desc* d) {
   return 0;
 }
 
-int wgrad_plan(const contrad_conv_desc* d, int* bm, int* bn, int* tiles_m, int* tiles_n, int* splits,
-               int* ptiles_per_split) {
+// The plan of an igemm launch.  FWD / DGRAD: tile, split-K count and K-tiles per split, tile mode (0 image-major, 1 pixel-major,
+// 2 border classes), balanced (strided DGRAD: equal-work block order).  WGRAD: tile, position splits and position tiles per
+// split, pixmajor 0 / 1.
+struct FwdPlan { int bm, bn, splits, tps, pixmajor, balanced; };
+
+// WGRAD plan (pixmajor is conv_route's to fill: wgrad_pixmajor_ok, below)
+FwdPlan wgrad_plan(const contrad_conv_desc* d) {
+  FwdPlan p{64, 64, 1, 0, 0, 0};
   const int Kg = d->KH * d->KW * d->C;
   const long long P = (long long)d->N * d->Ho * d->Wo;
-  *bn = (d->K > 64) ? 128 : 64;
-  *bm = (Kg > 64) ? 128 : 64;
-  static const int forced = []() { const char* e = contrad_dev_env("CONTRAD_WGRAD_TILE"); return e ? atoi(e) : 0; }();  // dev
-  if (forced) { *bm = forced / 1000; *bn = forced % 1000; }
-  if (g_plan_override.bm > 0) { *bm = g_plan_override.bm; *bn = g_plan_override.bn; }
-  static const int target = []() { const char* e = contrad_dev_env("CONTRAD_WGRAD_BLOCKS"); return e ? atoi(e) : 1024; }();  // dev
-  if (!vec_ok(d, MODE_WGRAD)) { *bm = 64; *bn = 64; }
-  *tiles_m = cdiv(Kg, *bm);
-  *tiles_n = cdiv(d->K, *bn);
+  p.bn = (d->K > 64) ? 128 : 64;
+  p.bm = (Kg > 64) ? 128 : 64;
+  static const int forced = contrad_dev_int("CONTRAD_WGRAD_TILE", 0);  // dev
+  if (forced) { p.bm = forced / 1000; p.bn = forced % 1000; }
+  if (g_plan_override.bm > 0) { p.bm = g_plan_override.bm; p.bn = g_plan_override.bn; }
+  static const int target = contrad_dev_int("CONTRAD_WGRAD_BLOCKS", 1024);  // dev
+  if (!vec_ok(d, MODE_WGRAD)) { p.bm = 64; p.bn = 64; }
   const long long ptiles = cdivll(P, BK);
   // 2 blocks are resident per CU (LDS): aim at <= 1024 blocks = two full rounds of the 256 CUs, never a ragged
   // third one (9 x 114 = 1026 blocks cost +30 % on the 3x3 layers before this was a floor)
-  long long want = target / ((long long)(*tiles_m) * (*tiles_n));
+  long long want = target / ((long long)cdiv(Kg, p.bm) * cdiv(d->K, p.bn));
   if (g_plan_override.splits > 0) want = g_plan_override.splits;   // dev: split count from the tuner
   if (want < 1) want = 1;
   long long pps = cdivll(ptiles, want);
   if (pps < 4) pps = 4;  // at least 128 positions per split
   if (pps > ptiles) pps = ptiles;
-  *ptiles_per_split = (int)pps;
-  *splits = (int)cdivll(ptiles, pps);
-  if (d->K <= 32 && *bm == 128 && vec_ok(d, MODE_WGRAD) && lean_ok(d, MODE_WGRAD, pps)) *bn = 32;   // (tiles_n stays 1)
-  return 0;
+  p.tps = (int)pps;
+  p.splits = (int)cdivll(ptiles, pps);
+  if (d->K <= 32 && p.bm == 128 && vec_ok(d, MODE_WGRAD) && lean_ok(d, MODE_WGRAD, pps)) p.bn = 32;   // (still one N-tile)
+  return p;
 }
 
 // Single-output 1x1 layer (the 512 -> 1 logit of the discriminator heads): y[m] = gain * lrelu(x[m] . w + bias) [+ addend].
@@ -1522,8 +1513,6 @@ __global__ void fwd_reduce_kernel(const float* __restrict__ ws, int splits, long
 // FWD plan: tile + split-K count from a small cost model (measured rates of the lean tiles, 768 blocks = a full
 // chip, partial slabs priced at 4 TB/s).  Split-K only pays for small-M, deep-K GEMMs: the merged head layer
 // (M = 3N rows, K = 8192) and the last conv layers at small per-rank batches.
-struct FwdPlan { int bm, bn, splits, tps, pixmajor, balanced; };   // balanced: strided DGRAD, equal-work block order
-
 // tile + split count for a lean GEMM of M x Ncol outputs over t_total K-tiles (shared by FWD and stride-1 DGRAD)
 void split_plan(long long M, int Ncol, int t_total, double flops, FwdPlan* p) {
   static const int cand[4][2] = {{128, 128}, {64, 128}, {128, 64}, {64, 64}};
@@ -1559,7 +1548,7 @@ bool fwd_k1_ok(const contrad_conv_desc* d) {
 }
 
 bool splitk_enabled() {
-  static const bool on = []() { const char* e = contrad_dev_env("CONTRAD_IGEMM_SPLITK"); return !(e && e[0] == '0'); }();
+  static const bool on = contrad_dev_on("CONTRAD_IGEMM_SPLITK");
   return on;
 }
 
@@ -1575,7 +1564,7 @@ constexpr double PIXMAJOR_MAX_VALID = 0.80;
 constexpr double PIXMAJOR_WGRAD_MAX_VALID = 0.85;
 
 bool pixmajor_enabled() {
-  static const bool on = []() { const char* e = contrad_dev_env("CONTRAD_PIXMAJOR"); return !(e && e[0] == '0'); }();
+  static const bool on = contrad_dev_on("CONTRAD_PIXMAJOR");
   return on;
 }
 
@@ -1686,7 +1675,7 @@ bool dgrad_pixmajor_ok(const contrad_conv_desc* d, int bm) {
   // stride 1 only: the kernel walks pixel-major tiles inside the parity classes of a strided layer just as well (parity
   // holds, CONTRAD_PIXMAJOR_STRIDED=1), but a class tile then contracts over 1 .. 4 taps only and the 4x4 stride-2
   // layer onto 4x4 maps ran 0.714 -> 0.757 ms at 1536 images
-  static const bool strided = []() { const char* e = contrad_dev_env("CONTRAD_PIXMAJOR_STRIDED"); return e && e[0] == '1'; }();
+  static const bool strided = contrad_dev_off_by_default("CONTRAD_PIXMAJOR_STRIDED");
   if (!pixmajor_enabled() || d->H * d->W > 256 || d->N < bm) return false;
   if (d->stride != 1 && !strided) {
     int bm2, bn2;           // the tile the plan takes for this layer (the balanced order depends on its N-tile count)
@@ -1716,7 +1705,7 @@ bool wgrad_pixmajor_ok(const contrad_conv_desc* d, int bm, long long pps) {
 // imbalance is NOT what keeps these tiles at 0.7 of the image-major tiles' issue rate (their operand traffic is, DESIGN.md
 // section 3).  taps[p] = valid taps of pixel p (any positive weights).
 void pixel_order(const int* taps, int npix, unsigned char* out) {
-  static const int mode = []() { const char* e = contrad_dev_env("CONTRAD_PIXORDER"); return e ? atoi(e) : 1; }();
+  static const int mode = contrad_dev_int("CONTRAD_PIXORDER", 1);
   int idx[256];
   for (int i = 0; i < npix; ++i) idx[i] = i;
   if (mode >= 1) {   // stable sort by taps, descending (insertion sort: npix <= 256, host, once per call)
@@ -1746,7 +1735,7 @@ void pixel_order(const int* taps, int npix, unsigned char* out) {
 bool pixel_order_full(const int* taps, int npix, int nib, int tiles_n, unsigned char* out, int nruns) {
   // nruns: XCD runs the table's tiles are spread over (8: the whole launch; a strided layer's class-major launch gives
   // every parity class 2 of the 8 runs and uses one table for all four classes)
-  static const bool on = []() { const char* e = contrad_dev_env("CONTRAD_PIXORDER_FULL"); return !(e && e[0] == '0'); }();
+  static const bool on = contrad_dev_on("CONTRAD_PIXORDER_FULL");
   const int nt = nib * npix;
   if (!on || nt > 256 || nt < nruns || nruns < 1 || nruns > 8 || tiles_n < 1 || tiles_n > 8 || (32 % tiles_n)) return false;
   // base order: image-block major; inside a block the pixels sorted by taps and dealt round-robin into `pieces` groups, so
@@ -1863,7 +1852,7 @@ bool border_classes(const contrad_conv_desc* d, int mode, BorderClasses* bc) {
 
 // tile mode of a lean FWD / DGRAD launch: 0 image-major, 1 pixel-major, 2 border classes
 int tile_mode_override() {
-  static const int m = []() { const char* e = contrad_dev_env("CONTRAD_TILEMODE"); return e ? atoi(e) : -1; }();   // dev
+  static const int m = contrad_dev_int("CONTRAD_TILEMODE", -1);   // dev
   return m;
 }
 
@@ -1907,12 +1896,6 @@ void fill_border_classes(const contrad_conv_desc* d, int mode, int bm, IgemmArgs
   a->tiles_m = 8 * most;
 }
 
-int border_class_tiles(const contrad_conv_desc* d, int mode, int bm) {
-  IgemmArgs a{};
-  fill_border_classes(d, mode, bm, &a);
-  return a.tiles_m;
-}
-
 FwdPlan fwd_plan(const contrad_conv_desc* d) {
   const long long M = (long long)d->N * d->Ho * d->Wo;
   const bool vec = vec_ok(d, MODE_FWD);
@@ -1938,7 +1921,7 @@ long long dgrad_balance(const contrad_conv_desc* d, int tiles_m, IgemmArgs* a);
 // ids, and 32 of them = one block for every CU of an XCD (round 2 had a fixed 8, which is this for the 4 N-tiles of the
 // 512-channel layers only; with 1 / 2 / 8 N-tiles 32 / 16 / 4 measured 20 - 35 % faster on single-round launches).
 int dgrad_cgroup(int tiles_m, int tiles_n) {
-  static const int forced = []() { const char* e = contrad_dev_env("CONTRAD_DGRAD_CGROUP"); return e ? atoi(e) : 0; }();
+  static const int forced = contrad_dev_int("CONTRAD_DGRAD_CGROUP", 0);
   int g = forced > 0 ? forced : std::max(1, 32 / std::max(tiles_n, 1));
   return g < tiles_m ? g : tiles_m;
 }
@@ -1984,7 +1967,7 @@ FwdPlan dgrad_plan(const contrad_conv_desc* d, bool may_split) {
 // stride-2 layers of SNDCGAN have four equal classes and keep the plain order).  Fills a->cbal / cb_reps / cb_start and
 // returns the number of blocks per N-tile (M-direction), or 0 when the plain order stays.
 long long dgrad_balance(const contrad_conv_desc* d, int tiles_m, IgemmArgs* a) {
-  static const bool on = []() { const char* e = contrad_dev_env("CONTRAD_DGRAD_BALANCE"); return !(e && e[0] == '0'); }();
+  static const bool on = contrad_dev_on("CONTRAD_DGRAD_BALANCE");
   const int s = d->stride;
   if (!on || s != 2) return 0;
   int taps[4], most = 0, least = 1 << 30;
@@ -2034,6 +2017,19 @@ __global__ void dgrad_reduce_kernel(const float* __restrict__ ws, int splits, lo
   }
 }
 
+// dwp / dbias = the fixed-order sum of `slabs` partial weight gradients (Kg x K each, bias partials behind them)
+int launch_wgrad_reduce(const float* ws, float* dwp, int Kg, int K, int ldw, int slabs, const float* bias_ws, float* dbias,
+                        hipStream_t stream) {
+  const long long total = (long long)Kg * K;
+  // split-lanes per element group: enough threads (~64 k) to cover the memory latency when the output is small
+  int R = 1;
+  while (R < 64 && R * 2 <= slabs && (total / 4) * R < 65536) R <<= 1;
+  const long long blocks = std::max(1ll, std::min(2048ll, ((total / 4) * R + 255) / 256));
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, ws, dwp, Kg, K, ldw, slabs, bias_ws, dbias, R);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
 int launch_wino22_wgrad(const contrad_conv_desc* d, const float* x, const float* gy, float* dwp, float* dbias,
                         float* workspace, hipStream_t stream) {
   static const hipError_t attr = hipFuncSetAttribute((const void*)wino22::wino22_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2041,19 +2037,11 @@ int launch_wino22_wgrad(const contrad_conv_desc* d, const float* x, const float*
   if (attr != hipSuccess) return (int)attr;
   wino22::WArgs a = wino22_wgrad_args(d);
   const int splits = wino22_wgrad_splits(a);
-  const long long total = 16ll * d->C * d->K;
   a.x = x; a.gy = gy; a.ws = workspace;
-  a.bias_ws = dbias ? workspace + (size_t)splits * total : nullptr;
-  hipLaunchKernelGGL(wino22::wino22_wgrad_kernel, dim3(a.RBN * a.KB * splits), dim3(512), wino22::W_LDS_DWORDS * 4, stream, a);
+  a.bias_ws = dbias ? workspace + (size_t)splits * 16 * d->C * d->K : nullptr;
+  hipLaunchKernelGGL(wino22::wino22_wgrad_kernel, dim3(wino22_wgrad_grid(a)), dim3(512), wino22::W_LDS_DWORDS * 4, stream, a);
   CONTRAD_CHECK_LAUNCH();
-  int R = 1;
-  while (R < 64 && R * 2 <= splits && (total / 4) * R < 65536) R <<= 1;
-  long long rb = ((total / 4) * R + 255) / 256;
-  if (rb > 2048) rb = 2048;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((int)rb), dim3(256), 0, stream, workspace, dwp, 16 * d->C, d->K, d->ldw, splits,
-                     a.bias_ws, dbias, R);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
+  return launch_wgrad_reduce(workspace, dwp, 16 * d->C, d->K, d->ldw, splits, a.bias_ws, dbias, stream);
 }
 
 int launch_wino_wgrad(const contrad_conv_desc* d, const float* x, const float* gy, float* dwp, float* dbias,
@@ -2063,19 +2051,210 @@ int launch_wino_wgrad(const contrad_conv_desc* d, const float* x, const float* g
   if (attr != hipSuccess) return (int)attr;
   wino::WArgs a = wino_wgrad_args(d);
   const int splits = wino_wgrad_splits(a);
-  const long long total = 9ll * d->C * d->K;
   a.x = x; a.gy = gy; a.ws = workspace;
-  a.bias_ws = dbias ? workspace + (size_t)splits * total : nullptr;
-  hipLaunchKernelGGL(wino::wino_wgrad_kernel, dim3(a.CB * a.KB * splits), dim3(512), wino::W_LDS_DWORDS * 4, stream, a);
+  a.bias_ws = dbias ? workspace + (size_t)splits * 9 * d->C * d->K : nullptr;
+  hipLaunchKernelGGL(wino::wino_wgrad_kernel, dim3(wino_wgrad_grid(a)), dim3(512), wino::W_LDS_DWORDS * 4, stream, a);
   CONTRAD_CHECK_LAUNCH();
-  int R = 1;
-  while (R < 64 && R * 2 <= splits && (total / 4) * R < 65536) R <<= 1;
-  long long rb = ((total / 4) * R + 255) / 256;
-  if (rb > 2048) rb = 2048;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((int)rb), dim3(256), 0, stream, workspace, dwp, 9 * d->C, d->K, d->ldw, splits,
-                     a.bias_ws, dbias, R);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
+  return launch_wgrad_reduce(workspace, dwp, 9 * d->C, d->K, d->ldw, splits, a.bias_ws, dbias, stream);
+}
+
+// The Winograd launch of filter kind `kind`, forward or data gradient.  U is the workspace, filled here by the family's filter
+// kernel, or the caller's prepared filter `u` when that was made for exactly this call (filter_fits).
+template <int MODE>
+int launch_wino_kind(int kind, const contrad_conv_desc* d, const float* in, const float* wp, const float* bias, const float* ref,
+                     float* out, float slope, float gain, float* workspace, const contrad_filter_job* u, hipStream_t stream) {
+  CONTRAD_ARG(aligned16(in, wp, workspace));
+  const float* U = filter_fits(u, kind, MODE, d, wp) ? u->U : nullptr;
+  if (kind == FILTER_WINO44) return launch_wino44<MODE>(d, in, wp, bias, ref, out, slope, gain, workspace, stream, U);
+  if (kind == FILTER_WINO) return launch_wino<MODE>(d, in, wp, bias, ref, out, slope, gain, workspace, stream, U);
+  if (kind == FILTER_WINO22) return launch_wino22<MODE>(d, in, wp, bias, ref, out, slope, gain, workspace, stream, U);
+  if (kind == FILTER_WINO23 && MODE == MODE_FWD) return launch_wino23(d, in, wp, bias, ref, out, slope, gain, workspace, stream, U);
+  return -22;
+}
+
+// ---------------- the route: which kernel family serves (d, mode), with what workspace and what igemm plan ----------------
+// The family numbers are the public ones of contrad_conv2d_path (include/contrad_hip.h).
+enum Family {
+  FAM_SCALAR = 0, FAM_GENERAL = 1, FAM_LEAN = 2, FAM_LEAN_SKIP = 3,      // igemm: !VEC, general, lean, lean on tiles that skip padding taps
+  FAM_WGRAD_C32 = 4, FAM_FWD_K1 = 5, FAM_CONV_C32 = 6,
+  FAM_WINO = 7, FAM_WINO22 = 8, FAM_WINO44 = 9, FAM_WINO23 = 10, FAM_WINO44N = 11
+};
+
+struct Route {
+  int family;                   // Family
+  int filter_kind;              // FILTER_* of a Winograd forward / data-gradient route, else 0
+  long long workspace_bytes;    // what a call must bring to run this route (0: none); with a workspace: what *_workspace_bytes reports
+  FwdPlan plan;                 // families 0 - 3 only
+  bool vec;                     // families 0 - 3: float4-addressable operands (family != FAM_SCALAR)
+};
+
+// The igemm engine's own route (families 0 - 3): what serves the layer when no special family takes it.
+Route igemm_route(const contrad_conv_desc* d, int mode, bool may_split) {
+  Route r{};
+  r.vec = vec_ok(d, mode);
+  const long long Kg = (long long)d->KH * d->KW * d->C;
+  if (mode == MODE_WGRAD) {
+    r.plan = wgrad_plan(d);
+    r.plan.pixmajor = wgrad_pixmajor_ok(d, r.plan.bm, r.plan.tps) ? 1 : 0;
+    r.workspace_bytes = (long long)r.plan.splits * (Kg + 1) * d->K * (long long)sizeof(float);   // slabs + bias partials
+  } else {
+    r.plan = mode == MODE_FWD ? fwd_plan(d) : dgrad_plan(d, may_split);
+    const long long slab = mode == MODE_FWD ? (long long)d->N * d->Ho * d->Wo * d->K : (long long)d->N * d->H * d->W * d->ldx;
+    if (r.plan.splits > 1) r.workspace_bytes = r.plan.splits * slab * (long long)sizeof(float);
+  }
+  const bool lean = r.vec && lean_ok(d, mode, mode == MODE_WGRAD ? r.plan.tps : 0);
+  r.family = !r.vec ? FAM_SCALAR : !lean ? FAM_GENERAL : r.plan.pixmajor ? FAM_LEAN_SKIP : FAM_LEAN;
+  return r;
+}
+
+// THE precedence list of the engine: the launchers switch on the family this returns and every plan query reports its fields,
+// so a query cannot drift from a launch.  has_workspace / workspace_bytes describe the call (the queries ask with and
+// without); two fall-through rules are part of the ABI and stay exactly as they were:
+//   * Winograd forward / data gradient reads its transformed filter from the workspace.  A call whose workspace is NULL or
+//     smaller than the filter falls through SILENTLY to the direct route below -- for the data gradient that route is
+//     dgrad_plan(d, workspace != nullptr), i.e. a too-small but present workspace still lets the plan split K.
+//   * A split-K route (and every weight-gradient route) whose workspace is too small is an argument error: the launchers
+//     return -22 when workspace_bytes < Route::workspace_bytes.
+Route conv_route(const contrad_conv_desc* d, int mode, bool has_workspace, long long workspace_bytes = 1ll << 62) {
+  Route r{};
+  if (mode == MODE_WGRAD) {
+    if (wino_wgrad_planned(d)) { r.family = FAM_WINO; r.workspace_bytes = wino_wgrad_workspace_bytes(d); return r; }
+    if (wino22_wgrad_planned(d)) { r.family = FAM_WINO22; r.workspace_bytes = wino22_wgrad_workspace_bytes(d); return r; }
+    if (wgrad_c32_ok(d)) {      // one partial per block, summed like split-K slabs
+      r.family = FAM_WGRAD_C32;
+      r.workspace_bytes = (long long)wgrad_c32_blocks(d) * ((long long)d->KH * d->KW * d->C + 1) * d->K * (long long)sizeof(float);
+      return r;
+    }
+    return igemm_route(d, mode, true);
+  }
+  if (wino44_planned(d, mode)) { r.family = wino44_n32(d, mode) ? FAM_WINO44N : FAM_WINO44; r.filter_kind = FILTER_WINO44; }
+  else if (wino_planned(d, mode)) r.family = r.filter_kind = FILTER_WINO;
+  else if (wino22_planned(d, mode)) r.family = r.filter_kind = FILTER_WINO22;
+  else if (wino23_planned(d, mode)) r.family = r.filter_kind = FILTER_WINO23;      // (forward only: wino23_ok)
+  long long filter_need = 0;
+  if (r.filter_kind) {
+    r.workspace_bytes = filter_need = filter_bytes(r.filter_kind, d);
+    if (has_workspace && workspace_bytes >= filter_need) return r;
+    r = Route{};                // (the silent fall-through)
+  }
+  if (conv_c32_ok(d)) { r.family = FAM_CONV_C32; return r; }      // weight-stationary 32 -> 32 channel 3x3 (conv_c32.h)
+  if (mode == MODE_FWD && fwd_k1_ok(d)) { r.family = FAM_FWD_K1; return r; }
+  r = igemm_route(d, mode, has_workspace);
+  // (a split-K plan reached by the fall-through still asks for what *_workspace_bytes names, the filter: -22, as it always was)
+  if (r.plan.splits > 1) r.workspace_bytes = std::max(r.workspace_bytes, filter_need);
+  return r;
+}
+
+// ---------------- igemm launches: one setup per mode fills the kernel's geometry and returns its grid ----------------
+// (the launchers add the operand pointers and the epilogue's scalars; contrad_conv2d_grid_blocks reports grid.x * grid.y)
+
+// valid taps of every output pixel (FWD) / of every dx pixel of a stride-1 data gradient
+void fwd_taps(const contrad_conv_desc* d, int* taps) {
+  for (int ho = 0; ho < d->Ho; ++ho)
+    for (int wo = 0; wo < d->Wo; ++wo) {
+      int vh = 0, vw = 0;
+      for (int kh = 0; kh < d->KH; ++kh) vh += (unsigned)(ho * d->stride - d->pad + kh) < (unsigned)d->H;
+      for (int kw = 0; kw < d->KW; ++kw) vw += (unsigned)(wo * d->stride - d->pad + kw) < (unsigned)d->W;
+      taps[ho * d->Wo + wo] = vh * vw;
+    }
+}
+void dgrad_taps(const contrad_conv_desc* d, int* taps) {
+  for (int h = 0; h < d->H; ++h)
+    for (int w = 0; w < d->W; ++w) {
+      int vh = 0, vw = 0;
+      for (int kh = 0; kh < d->KH; ++kh) vh += (unsigned)(h + d->pad - kh) < (unsigned)d->Ho;
+      for (int kw = 0; kw < d->KW; ++kw) vw += (unsigned)(w + d->pad - kw) < (unsigned)d->Wo;
+      taps[h * d->W + w] = vh * vw;
+    }
+}
+
+// The pixel table of a pixel-major FWD / DGRAD plan (p.pixmajor == 1; npix <= 256 pixels per image or parity class): fills
+// order[256] and returns px_full -- 0: per-image-block order (pixel_order), 1: order of the whole launch (pixel_order_full),
+// 2: strided data gradient, class (0,0)'s table for all four classes in a class-major launch.
+int pixel_table(const contrad_conv_desc* d, int mode, const FwdPlan& p, int npix, unsigned char* order) {
+  const int s = mode == MODE_DGRAD ? d->stride : 1;
+  const int nib = cdiv(d->N, p.bm), tiles_n = cdiv(mode == MODE_FWD ? d->K : d->C, p.bn);
+  int taps[256];
+  unsigned char full[256] = {};
+  for (int i = 0; i < npix; ++i) taps[i] = 1;       // (strided: per-class pixel sets, left in row-major order)
+  if (mode == MODE_FWD) fwd_taps(d, taps);
+  else if (s == 1) dgrad_taps(d, taps);
+  pixel_order(taps, npix, order);
+  int px_full = 0;
+  if (s == 1 && pixel_order_full(taps, npix, nib, tiles_n, full, 8)) px_full = 1;
+  else if (s == 2 && dgrad_strided_full_ok(d, p.bm, p.bn)) {
+    pixel_order_full(taps, dgrad_strided_class0_taps(d, taps), nib, tiles_n, full, 2);
+    px_full = 2;
+  }
+  if (px_full) memcpy(order, full, sizeof(full));
+  return px_full;
+}
+
+dim3 fwd_setup(const contrad_conv_desc* d, const FwdPlan& p, IgemmArgs* a) {
+  a->d = *d;
+  a->M = d->N * d->Ho * d->Wo; a->Ncol = d->K; a->Kg = d->KH * d->KW * d->C;      // (M < 2^31: check_desc)
+  a->st_nt = st_nt_for(a->M, d->ldy);
+  a->tiles_m = p.pixmajor == 1 ? cdiv(d->N, p.bm) * d->Ho * d->Wo : cdiv(a->M, p.bm);
+  a->tiles_n = cdiv(a->Ncol, p.bn);
+  a->pixmajor = p.pixmajor == 1;
+  if (p.pixmajor == 2) fill_border_classes(d, MODE_FWD, p.bm, a);      // (sets tiles_m)
+  if (p.pixmajor == 1) a->px_full = pixel_table(d, MODE_FWD, p, d->Ho * d->Wo, a->px_order);
+  a->ptiles_per_split = p.tps;
+  return dim3(a->tiles_m * a->tiles_n, p.splits);
+}
+
+// Every input pixel must be covered by at least one tap of its parity class, otherwise the class (whose gradient is exactly
+// zero) still writes zeros: handled by Kg == 0 -> T == 0 -> acc = 0.
+dim3 dgrad_setup(const contrad_conv_desc* d, const FwdPlan& p, IgemmArgs* a) {
+  const int s = d->stride;
+  const int Mc = d->N * cdiv(d->H, s) * cdiv(d->W, s);      // largest class (< 2^31: check_desc)
+  a->d = *d;
+  a->st_nt = st_nt_for((long long)d->N * d->H * d->W, d->ldx);
+  a->pixmajor = p.pixmajor == 1;
+  a->px_pixels = cdiv(d->H, s) * cdiv(d->W, s);
+  a->tiles_m = p.pixmajor == 1 ? cdiv(d->N, p.bm) * a->px_pixels : cdiv(Mc, p.bm);
+  a->tiles_n = cdiv(d->C, p.bn);
+  if (p.pixmajor == 2) fill_border_classes(d, MODE_DGRAD, p.bm, a);     // (sets tiles_m)
+  if (p.pixmajor == 1) a->px_full = pixel_table(d, MODE_DGRAD, p, a->px_pixels, a->px_order);
+  if (p.splits > 1) {
+    // stride-1 split-K: every split writes raw partial sums into its own slab (dx's layout), dgrad_reduce_kernel sums
+    // them in a fixed order and applies the fused act' epilogue
+    a->dsplits = p.splits;
+    a->ptiles_per_split = p.tps;
+    a->slab_elems = (long long)d->N * d->H * d->W * d->ldx;
+    return dim3(a->tiles_m * a->tiles_n, p.splits);
+  }
+  // Block order of the strided lean DGRAD: the parity classes of a 3x3 stride-2 conv contract over 4, 2, 2 and 1 taps.
+  // With the classes of one M-tile on consecutive block ids (tile_n, class, tile_m) the kernel took exactly as long as
+  // its heaviest class alone (measured by launching single classes: 1.03 ms for class (0,0) vs 1.10 ms for all four;
+  // k3 / k4 / k5 kernels: 72 / 128 / 96 TF/s = 9/16, 16/16, 25/36 of the balanced rate) -- blocks that become resident
+  // together should carry equal work.  Groups of 8 M-tiles, class-major inside a group: neighbours are equal, and the
+  // gy rows a group's classes share are still cache-resident when the next class reads them.  3x3 s2 at batch 32:
+  // 72 -> 99, 84 -> 102, 78 -> 117, 82 -> 99 TF/s; groups of 32 / 64 lose again on layers with < ~100 M-tiles (few
+  // groups -> a tail of light classes).  tools/bench_conv.py; CONTRAD_DGRAD_CGROUP=0 restores the old order.
+  a->cgroup = (s > 1) ? dgrad_cgroup(a->tiles_m, a->tiles_n) : 0;
+  if (a->px_full == 2) a->cgroup = a->tiles_m;           // class-major over the whole launch: class c = XCD runs 2c, 2c + 1
+  // ... and equal work per block where the classes are unequal (3x3 stride 2: 4 / 2 / 2 / 1 taps): a block of a light
+  // class walks 2 / 4 consecutive M-tiles (dgrad_balance(); igemm_lean.h).  Neighbours are then equal AND every block of
+  // the launch carries the same number of K-tiles, so the tail of the launch is not a few 4-tap blocks running alone.
+  if (p.balanced && p.pixmajor == 0) {      // (balanced: lean plans only, dgrad_plan)
+    const long long blocks = dgrad_balance(d, a->tiles_m, a);
+    if (blocks > 0) {
+      a->cgroup = 0;
+      return dim3((unsigned)(blocks * a->tiles_n), 1);
+    }
+  }
+  const int tm_pad = a->cgroup > 0 ? cdiv(a->tiles_m, a->cgroup) * a->cgroup : a->tiles_m;
+  return dim3(tm_pad * a->tiles_n, s * s);
+}
+
+dim3 wgrad_setup(const contrad_conv_desc* d, const FwdPlan& p, IgemmArgs* a) {
+  a->d = *d;
+  a->M = d->KH * d->KW * d->C; a->Ncol = d->K; a->Kg = a->M;
+  a->tiles_m = cdiv(a->M, p.bm); a->tiles_n = cdiv(a->Ncol, p.bn);
+  a->P = d->N * d->Ho * d->Wo; a->ptiles_per_split = p.tps;      // (P < 2^31: check_desc)
+  a->pixmajor = p.pixmajor;
+  return dim3(a->tiles_m * a->tiles_n, p.splits);
 }
 
 }  // namespace
@@ -2084,13 +2263,7 @@ extern "C" int contrad_abi_version(void) { return 3; }
 
 extern "C" long long contrad_conv2d_fwd_workspace_bytes(const contrad_conv_desc* d) {
   if (check_desc(d)) return -22;
-  if (wino44_planned(d, MODE_FWD)) return wino44_workspace_bytes(d);
-  if (wino_planned(d, MODE_FWD)) return wino_workspace_bytes(d);
-  if (wino22_planned(d, MODE_FWD)) return wino22_workspace_bytes(d);
-  if (wino23_planned(d, MODE_FWD)) return wino23_workspace_bytes(d);
-  const FwdPlan p = fwd_plan(d);
-  if (p.splits <= 1) return 0;
-  return (long long)p.splits * d->N * d->Ho * d->Wo * d->K * (long long)sizeof(float);
+  return conv_route(d, MODE_FWD, true).workspace_bytes;
 }
 
 extern "C" int contrad_conv2d_fwd_add_u(const contrad_conv_desc* d, const float* x, const float* wp,
@@ -2101,77 +2274,38 @@ extern "C" int contrad_conv2d_fwd_add_u(const contrad_conv_desc* d, const float*
   if (rc) return rc;
   CONTRAD_ARG(x && wp && y);
   if (vec_ok(d, MODE_FWD)) CONTRAD_ARG(aligned16(x, wp, y) && aligned16(addend, nullptr, nullptr));
-  IgemmArgs a{};
-  a.A = x; a.B = wp; a.C = y; a.bias = bias; a.addend = addend; a.d = *d; a.slope = slope; a.gain = gain;
   const long long M = (long long)d->N * d->Ho * d->Wo;
   CONTRAD_ARG(M < (1ll << 31));
-  a.M = (int)M; a.Ncol = d->K; a.Kg = d->KH * d->KW * d->C;
-  a.st_nt = st_nt_for(M, d->ldy);
-  if (wino44_planned(d, MODE_FWD) && workspace && workspace_bytes >= wino44_workspace_bytes(d)) {   // Winograd F(4x4, 3x3), wino44.h
-    CONTRAD_ARG(aligned16(x, wp, workspace));
-    return launch_wino44<MODE_FWD>(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream,
-                                   filter_fits(u, FILTER_WINO44, MODE_FWD, d, wp) ? u->U : nullptr);
+  // (alignment is an argument error above, so the dispatch is exactly the route: what contrad_conv2d_path / _grid_blocks report)
+  const Route r = conv_route(d, MODE_FWD, workspace != nullptr, workspace_bytes);
+  hipStream_t s = (hipStream_t)stream;
+  switch (r.family) {
+    case FAM_WINO: case FAM_WINO22: case FAM_WINO44: case FAM_WINO23: case FAM_WINO44N:
+      return launch_wino_kind<MODE_FWD>(r.filter_kind, d, x, wp, bias, addend, y, slope, gain, workspace, u, s);
+    case FAM_CONV_C32:
+      return launch_conv_c32<MODE_FWD>(d, x, wp, y, bias, addend, nullptr, slope, gain, s);
+    case FAM_FWD_K1:
+      hipLaunchKernelGGL(fwd_k1_kernel, dim3((unsigned)cdivll(M, 4)), dim3(256), 0, s, x, wp, M, d->C, d->ldx, d->ldw, bias, slope,
+                         gain, y, d->ldy, addend);
+      CONTRAD_CHECK_LAUNCH();
+      return 0;
+    default: break;      // the igemm engine
   }
-  if (wino_planned(d, MODE_FWD) && workspace && workspace_bytes >= wino_workspace_bytes(d)) {   // Winograd F(2x2, 3x3), wino.h
-    CONTRAD_ARG(aligned16(x, wp, workspace));
-    return launch_wino<MODE_FWD>(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream,
-                                 filter_fits(u, FILTER_WINO, MODE_FWD, d, wp) ? u->U : nullptr);
-  }
-  if (wino22_planned(d, MODE_FWD) && workspace && workspace_bytes >= wino22_workspace_bytes(d)) {   // F(2x2, 2x2) on the phases, wino22.h
-    CONTRAD_ARG(aligned16(x, wp, workspace));
-    return launch_wino22<MODE_FWD>(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream,
-                                   filter_fits(u, FILTER_WINO22, MODE_FWD, d, wp) ? u->U : nullptr);
-  }
-  if (wino23_planned(d, MODE_FWD) && workspace && workspace_bytes >= wino23_workspace_bytes(d)) {   // 3x3 stride 2: F(2x2, 2x2) on the phases, wino23.h
-    CONTRAD_ARG(aligned16(x, wp, workspace));
-    return launch_wino23(d, x, wp, bias, addend, y, slope, gain, workspace, (hipStream_t)stream,
-                         filter_fits(u, FILTER_WINO23, MODE_FWD, d, wp) ? u->U : nullptr);
-  }
-  // (without a workspace of contrad_conv2d_fwd_workspace_bytes the Winograd plans above fall through to the direct kernels
-  // below; contrad_conv2d_path / _executed_fraction describe the plan WITH that workspace, _grid_blocks either one)
-  if (conv_c32_ok(d))   // weight-stationary kernel (conv_c32.h); (alignment is an argument error above, so with the workspace
-                        // the dispatch is exactly what contrad_conv2d_path / _grid_blocks report)
-    return launch_conv_c32<MODE_FWD>(d, x, wp, y, bias, addend, nullptr, slope, gain, (hipStream_t)stream);
-  if (fwd_k1_ok(d)) {
-    hipLaunchKernelGGL(fwd_k1_kernel, dim3((unsigned)cdivll(M, 4)), dim3(256), 0, (hipStream_t)stream, x, wp, M, d->C,
-                       d->ldx, d->ldw, bias, slope, gain, y, d->ldy, addend);
-    CONTRAD_CHECK_LAUNCH();
-    return 0;
-  }
-  const bool vec = vec_ok(d, MODE_FWD);
-  const FwdPlan p = fwd_plan(d);
-  a.tiles_m = p.pixmajor == 1 ? cdiv(d->N, p.bm) * d->Ho * d->Wo : cdiv(a.M, p.bm);
-  a.tiles_n = cdiv(a.Ncol, p.bn);
-  a.pixmajor = p.pixmajor == 1;
-  if (p.pixmajor == 2) fill_border_classes(d, MODE_FWD, p.bm, &a);      // (sets tiles_m)
-  if (p.pixmajor == 1) {
-    int taps[256];
-    for (int ho = 0; ho < d->Ho; ++ho)
-      for (int wo = 0; wo < d->Wo; ++wo) {
-        int vh = 0, vw = 0;
-        for (int kh = 0; kh < d->KH; ++kh) vh += (unsigned)(ho * d->stride - d->pad + kh) < (unsigned)d->H;
-        for (int kw = 0; kw < d->KW; ++kw) vw += (unsigned)(wo * d->stride - d->pad + kw) < (unsigned)d->W;
-        taps[ho * d->Wo + wo] = vh * vw;
-      }
-    pixel_order(taps, d->Ho * d->Wo, a.px_order);
-    unsigned char full[256];
-    if (pixel_order_full(taps, d->Ho * d->Wo, cdiv(d->N, p.bm), a.tiles_n, full, 8)) {
-      memcpy(a.px_order, full, sizeof(full));
-      a.px_full = 1;
-    }
-  }
-  a.ptiles_per_split = p.tps;
+  const FwdPlan& p = r.plan;
+  IgemmArgs a{};
+  a.A = x; a.B = wp; a.C = y; a.bias = bias; a.addend = addend; a.slope = slope; a.gain = gain;
+  const dim3 grid = fwd_setup(d, p, &a);
   if (p.splits > 1) {
-    CONTRAD_ARG(workspace && workspace_bytes >= contrad_conv2d_fwd_workspace_bytes(d));
+    CONTRAD_ARG(workspace && workspace_bytes >= r.workspace_bytes);
     a.C = workspace;
   }
-  rc = dispatch<MODE_FWD>(a, p.bm, p.bn, vec, dim3(a.tiles_m * a.tiles_n, p.splits), (hipStream_t)stream);
+  rc = dispatch<MODE_FWD>(a, p.bm, p.bn, r.vec, grid, s);
   if (rc || p.splits <= 1) return rc;
   const long long total = M * d->K;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(fwd_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, workspace, p.splits, M,
-                     d->K, bias, slope, gain, y, d->ldy, addend);
+  hipLaunchKernelGGL(fwd_reduce_kernel, dim3(blocks), dim3(256), 0, s, workspace, p.splits, M, d->K, bias, slope, gain, y,
+                     d->ldy, addend);
   CONTRAD_CHECK_LAUNCH();
   return 0;
 }
@@ -2190,12 +2324,7 @@ extern "C" int contrad_conv2d_fwd(const contrad_conv_desc* d, const float* x, co
 
 extern "C" long long contrad_conv2d_dgrad_workspace_bytes(const contrad_conv_desc* d) {
   if (check_desc(d)) return -22;
-  if (wino44_planned(d, MODE_DGRAD)) return wino44_workspace_bytes(d);
-  if (wino_planned(d, MODE_DGRAD)) return wino_workspace_bytes(d);
-  if (wino22_planned(d, MODE_DGRAD)) return wino22_workspace_bytes(d);
-  const FwdPlan p = dgrad_plan(d, true);
-  if (p.splits <= 1) return 0;
-  return (long long)p.splits * d->N * d->H * d->W * d->ldx * (long long)sizeof(float);
+  return conv_route(d, MODE_DGRAD, true).workspace_bytes;
 }
 
 extern "C" int contrad_conv2d_dgrad_ws_u(const contrad_conv_desc* d, const float* gy, const float* wp,
@@ -2206,104 +2335,31 @@ extern "C" int contrad_conv2d_dgrad_ws_u(const contrad_conv_desc* d, const float
   if (rc) return rc;
   CONTRAD_ARG(gy && wp && dx);
   if (vec_ok(d, MODE_DGRAD)) CONTRAD_ARG(aligned16(gy, wp, dx) && aligned16(act_ref, nullptr, nullptr));
-  if (wino44_planned(d, MODE_DGRAD) && workspace && workspace_bytes >= wino44_workspace_bytes(d)) {   // wino44.h: mirrored filter
-    CONTRAD_ARG(aligned16(gy, wp, workspace));
-    return launch_wino44<MODE_DGRAD>(d, gy, wp, nullptr, act_ref, dx, slope, gain, workspace, (hipStream_t)stream,
-                                     filter_fits(u, FILTER_WINO44, MODE_DGRAD, d, wp) ? u->U : nullptr);
+  const Route r = conv_route(d, MODE_DGRAD, workspace != nullptr, workspace_bytes);
+  hipStream_t s = (hipStream_t)stream;
+  switch (r.family) {
+    case FAM_WINO: case FAM_WINO22: case FAM_WINO44: case FAM_WINO44N:      // the filter mirrored; wino22: one item per dx phase
+      return launch_wino_kind<MODE_DGRAD>(r.filter_kind, d, gy, wp, nullptr, act_ref, dx, slope, gain, workspace, u, s);
+    case FAM_CONV_C32:      // the same weight-stationary kernel with the filter mirrored
+      return launch_conv_c32<MODE_DGRAD>(d, gy, wp, dx, nullptr, nullptr, act_ref, slope, gain, s);
+    default: break;      // the igemm engine
   }
-  if (wino_planned(d, MODE_DGRAD) && workspace && workspace_bytes >= wino_workspace_bytes(d)) {   // wino.h: mirrored filter
-    CONTRAD_ARG(aligned16(gy, wp, workspace));
-    return launch_wino<MODE_DGRAD>(d, gy, wp, nullptr, act_ref, dx, slope, gain, workspace, (hipStream_t)stream,
-                                   filter_fits(u, FILTER_WINO, MODE_DGRAD, d, wp) ? u->U : nullptr);
-  }
-  if (wino22_planned(d, MODE_DGRAD) && workspace && workspace_bytes >= wino22_workspace_bytes(d)) {   // wino22.h: one item per dx phase
-    CONTRAD_ARG(aligned16(gy, wp, workspace));
-    return launch_wino22<MODE_DGRAD>(d, gy, wp, nullptr, act_ref, dx, slope, gain, workspace, (hipStream_t)stream,
-                                     filter_fits(u, FILTER_WINO22, MODE_DGRAD, d, wp) ? u->U : nullptr);
-  }
-  if (conv_c32_ok(d))   // stride-1 pad-1 3x3: the same weight-stationary kernel with the filter mirrored (conv_c32.h)
-    return launch_conv_c32<MODE_DGRAD>(d, gy, wp, dx, nullptr, nullptr, act_ref, slope, gain, (hipStream_t)stream);
-  // every input pixel must be covered by at least one tap of its parity class, otherwise the class
-  // (whose gradient is exactly zero) still writes zeros: handled by Kg == 0 -> T == 0 -> acc = 0.
+  const FwdPlan& p = r.plan;
   IgemmArgs a{};
-  a.A = gy; a.B = wp; a.C = dx; a.act_ref = act_ref; a.d = *d; a.slope = slope; a.gain = gain;
-  a.st_nt = st_nt_for((long long)d->N * d->H * d->W, d->ldx);
-  const int s = d->stride;
-  const long long Mc = (long long)d->N * cdiv(d->H, s) * cdiv(d->W, s);  // largest class
-  CONTRAD_ARG(Mc < (1ll << 31));
-  const bool vec = vec_ok(d, MODE_DGRAD);
-  const FwdPlan pl = dgrad_plan(d, workspace != nullptr);
-  const int bm = pl.bm, bn = pl.bn;
-  a.pixmajor = pl.pixmajor == 1;
-  a.px_pixels = cdiv(d->H, s) * cdiv(d->W, s);
-  a.tiles_m = pl.pixmajor == 1 ? cdiv(d->N, bm) * a.px_pixels : cdiv((int)Mc, bm);
-  if (pl.pixmajor == 2) fill_border_classes(d, MODE_DGRAD, bm, &a);     // (sets tiles_m)
-  if (pl.pixmajor == 1) {
-    int taps[256];
-    for (int i = 0; i < a.px_pixels; ++i) taps[i] = 1;
-    if (s == 1)     // (strided: per-class pixel sets, left in row-major order)
-      for (int h = 0; h < d->H; ++h)
-        for (int w = 0; w < d->W; ++w) {
-          int vh = 0, vw = 0;
-          for (int kh = 0; kh < d->KH; ++kh) vh += (unsigned)(h + d->pad - kh) < (unsigned)d->Ho;
-          for (int kw = 0; kw < d->KW; ++kw) vw += (unsigned)(w + d->pad - kw) < (unsigned)d->Wo;
-          taps[h * d->W + w] = vh * vw;
-        }
-    pixel_order(taps, a.px_pixels, a.px_order);
-    unsigned char full[256];
-    if (s == 1 && pixel_order_full(taps, a.px_pixels, cdiv(d->N, bm), cdiv(d->C, bn), full, 8)) {
-      memcpy(a.px_order, full, sizeof(full));
-      a.px_full = 1;
-    } else if (s == 2 && dgrad_strided_full_ok(d, bm, bn)) {
-      int t0[256];
-      const int npix = dgrad_strided_class0_taps(d, t0);
-      pixel_order_full(t0, npix, cdiv(d->N, bm), cdiv(d->C, bn), full, 2);
-      memcpy(a.px_order, full, sizeof(full));
-      a.px_full = 2;
-    }
-  }
-  a.tiles_n = cdiv(d->C, bn);
-  if (pl.splits > 1) {
-    // stride-1 split-K: every split writes raw partial sums into its own slab (dx's layout), dgrad_reduce_kernel sums
-    // them in a fixed order and applies the fused act' epilogue
-    CONTRAD_ARG(workspace_bytes >= contrad_conv2d_dgrad_workspace_bytes(d));
-    a.dsplits = pl.splits;
-    a.ptiles_per_split = pl.tps;
-    a.slab_elems = (long long)d->N * d->H * d->W * d->ldx;
-    CONTRAD_ARG(a.slab_elems * 4 < (1ll << 40));
-    a.C = workspace; a.act_ref = nullptr;
-    rc = dispatch<MODE_DGRAD>(a, bm, bn, vec, dim3(a.tiles_m * a.tiles_n, pl.splits), (hipStream_t)stream);
-    if (rc) return rc;
-    const long long rows = (long long)d->N * d->H * d->W;
-    long long blocks = (rows * (d->C / 4) + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(dgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, workspace,
-                       pl.splits, a.slab_elems, rows, d->C, d->ldx, act_ref, slope, gain, dx);
-    CONTRAD_CHECK_LAUNCH();
-    return 0;
-  }
-  // Block order of the strided lean DGRAD: the parity classes of a 3x3 stride-2 conv contract over 4, 2, 2 and 1 taps.
-  // With the classes of one M-tile on consecutive block ids (tile_n, class, tile_m) the kernel took exactly as long as
-  // its heaviest class alone (measured by launching single classes: 1.03 ms for class (0,0) vs 1.10 ms for all four;
-  // k3 / k4 / k5 kernels: 72 / 128 / 96 TF/s = 9/16, 16/16, 25/36 of the balanced rate) -- blocks that become resident
-  // together should carry equal work.  Groups of 8 M-tiles, class-major inside a group: neighbours are equal, and the
-  // gy rows a group's classes share are still cache-resident when the next class reads them.  3x3 s2 at batch 32:
-  // 72 -> 99, 84 -> 102, 78 -> 117, 82 -> 99 TF/s; groups of 32 / 64 lose again on layers with < ~100 M-tiles (few
-  // groups -> a tail of light classes).  tools/bench_conv.py; CONTRAD_DGRAD_CGROUP=0 restores the old order.
-  a.cgroup = (s > 1) ? dgrad_cgroup(a.tiles_m, a.tiles_n) : 0;
-  if (a.px_full == 2) a.cgroup = a.tiles_m;           // class-major over the whole launch: class c = XCD runs 2c, 2c + 1
-  // ... and equal work per block where the classes are unequal (3x3 stride 2: 4 / 2 / 2 / 1 taps): a block of a light
-  // class walks 2 / 4 consecutive M-tiles (dgrad_balance(); igemm_lean.h).  Neighbours are then equal AND every block of
-  // the launch carries the same number of K-tiles, so the tail of the launch is not a few 4-tap blocks running alone.
-  if (pl.balanced && vec && lean_ok(d, MODE_DGRAD, 0) && !a.pixmajor && a.nwin == 0) {
-    const long long blocks = dgrad_balance(d, a.tiles_m, &a);
-    if (blocks > 0) {
-      a.cgroup = 0;
-      return dispatch<MODE_DGRAD>(a, bm, bn, vec, dim3((unsigned)(blocks * a.tiles_n), 1), (hipStream_t)stream);
-    }
-  }
-  const int tm_pad = a.cgroup > 0 ? cdiv(a.tiles_m, a.cgroup) * a.cgroup : a.tiles_m;
-  return dispatch<MODE_DGRAD>(a, bm, bn, vec, dim3(tm_pad * a.tiles_n, s * s), (hipStream_t)stream);
+  a.A = gy; a.B = wp; a.C = dx; a.act_ref = act_ref; a.slope = slope; a.gain = gain;
+  const dim3 grid = dgrad_setup(d, p, &a);
+  if (p.splits <= 1) return dispatch<MODE_DGRAD>(a, p.bm, p.bn, r.vec, grid, s);
+  CONTRAD_ARG(workspace_bytes >= r.workspace_bytes);
+  a.C = workspace; a.act_ref = nullptr;
+  rc = dispatch<MODE_DGRAD>(a, p.bm, p.bn, r.vec, grid, s);
+  if (rc) return rc;
+  const long long rows = (long long)d->N * d->H * d->W;
+  long long blocks = (rows * (d->C / 4) + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(dgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, workspace, p.splits, a.slab_elems, rows,
+                     d->C, d->ldx, act_ref, slope, gain, dx);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int contrad_conv2d_dgrad_ws(const contrad_conv_desc* d, const float* gy, const float* wp,
@@ -2322,7 +2378,9 @@ extern "C" int contrad_conv2d_filter_kind(const contrad_conv_desc* d, int mode, 
   if (bytes) *bytes = 0;
   if (check_desc(d)) return -22;
   if (mode != MODE_FWD && mode != MODE_DGRAD) return -22;
-  return filter_kind_planned(d, mode, bytes);
+  const Route r = conv_route(d, mode, true);
+  if (bytes && r.filter_kind) *bytes = r.workspace_bytes;
+  return r.filter_kind;
 }
 
 extern "C" int contrad_conv2d_filter_prep(const contrad_filter_batch* b, contrad_stream_t stream) {
@@ -2353,12 +2411,27 @@ extern "C" int contrad_conv2d_wino_ok(const contrad_conv_desc* d, int mode) {
   return (wino_ok(d, mode) || wino22_ok(d, mode) || wino23_ok(d, mode)) ? 1 : 0;
 }
 
+namespace {
+// The forced Winograd entry points: kind from the family's *_ok, the caller's checks, no prepared filter.
+int launch_wino_forced(int kind, const contrad_conv_desc* d, int mode, const float* in, const float* wp, const float* bias,
+                       const float* ref, float* out, float slope, float gain, float* workspace, long long workspace_bytes,
+                       hipStream_t stream) {
+  CONTRAD_ARG(kind != 0 && workspace_bytes >= filter_bytes(kind, d) && (mode == MODE_FWD || bias == nullptr));
+  if (mode == MODE_FWD) return launch_wino_kind<MODE_FWD>(kind, d, in, wp, bias, ref, out, slope, gain, workspace, nullptr, stream);
+  return launch_wino_kind<MODE_DGRAD>(kind, d, in, wp, nullptr, ref, out, slope, gain, workspace, nullptr, stream);
+}
+
+// the family contrad_conv2d_wino forces for (d, mode): 0 exactly when contrad_conv2d_wino_ok says 0
+int forced_wino_kind(const contrad_conv_desc* d, int mode) {
+  return wino22_ok(d, mode) ? FILTER_WINO22 : wino23_ok(d, mode) ? FILTER_WINO23 : wino_ok(d, mode) ? FILTER_WINO : 0;
+}
+}  // namespace
+
 extern "C" long long contrad_conv2d_wino_workspace_bytes(const contrad_conv_desc* d, int mode) {
   if (check_desc(d) || mode < 0 || mode > 2) return -22;
   if (mode == MODE_WGRAD) return wino_wgrad_ok(d) ? wino_wgrad_workspace_bytes(d) : wino22_wgrad_ok(d) ? wino22_wgrad_workspace_bytes(d) : -22;
-  if (wino22_ok(d, mode)) return wino22_workspace_bytes(d);     // (the dispatch order of contrad_conv2d_wino)
-  if (wino23_ok(d, mode)) return wino23_workspace_bytes(d);
-  return wino_ok(d, mode) ? wino_workspace_bytes(d) : -22;      // -22 exactly when contrad_conv2d_wino_ok says 0
+  const int kind = forced_wino_kind(d, mode);
+  return kind ? filter_bytes(kind, d) : -22;
 }
 
 extern "C" int contrad_conv2d_wino_wgrad(const contrad_conv_desc* d, const float* x, const float* gy, float* dwp,
@@ -2375,26 +2448,16 @@ extern "C" int contrad_conv2d_wino_wgrad(const contrad_conv_desc* d, const float
   return launch_wino_wgrad(d, x, gy, dwp, dbias, workspace, (hipStream_t)stream);
 }
 
+// 4x4 stride 2: F(2x2, 2x2) on the phases (wino22.h); 3x3 stride 2 pad 0, forward only: the same with the zero planes skipped
+// (wino23.h); else F(2x2, 3x3) (wino.h)
 extern "C" int contrad_conv2d_wino(const contrad_conv_desc* d, int mode, const float* in, const float* wp,
                                    const float* bias, const float* ref, float* out, float slope, float gain,
                                    float* workspace, long long workspace_bytes, contrad_stream_t stream) {
   int rc = check_desc(d);
   if (rc) return rc;
   CONTRAD_ARG(in && wp && out && workspace && (mode == MODE_FWD || mode == MODE_DGRAD));
-  CONTRAD_ARG(aligned16(in, wp, workspace));
-  if (wino22_ok(d, mode)) {        // 4x4 stride 2: F(2x2, 2x2) on the phases (wino22.h)
-    CONTRAD_ARG(workspace_bytes >= wino22_workspace_bytes(d) && (mode == MODE_FWD || bias == nullptr));
-    if (mode == MODE_FWD) return launch_wino22<MODE_FWD>(d, in, wp, bias, ref, out, slope, gain, workspace, (hipStream_t)stream);
-    return launch_wino22<MODE_DGRAD>(d, in, wp, nullptr, ref, out, slope, gain, workspace, (hipStream_t)stream);
-  }
-  if (wino23_ok(d, mode)) {        // 3x3 stride 2 pad 0 (forward only): F(2x2, 2x2) on the phases, zero planes skipped (wino23.h)
-    CONTRAD_ARG(workspace_bytes >= wino23_workspace_bytes(d));
-    return launch_wino23(d, in, wp, bias, ref, out, slope, gain, workspace, (hipStream_t)stream);
-  }
-  CONTRAD_ARG(wino_ok(d, mode) && workspace_bytes >= wino_workspace_bytes(d));
-  if (mode == MODE_FWD) return launch_wino<MODE_FWD>(d, in, wp, bias, ref, out, slope, gain, workspace, (hipStream_t)stream);
-  CONTRAD_ARG(bias == nullptr);
-  return launch_wino<MODE_DGRAD>(d, in, wp, nullptr, ref, out, slope, gain, workspace, (hipStream_t)stream);
+  return launch_wino_forced(forced_wino_kind(d, mode), d, mode, in, wp, bias, ref, out, slope, gain, workspace, workspace_bytes,
+                            (hipStream_t)stream);
 }
 
 extern "C" int contrad_conv2d_wino44_ok(const contrad_conv_desc* d, int mode) {
@@ -2405,7 +2468,7 @@ extern "C" int contrad_conv2d_wino44_ok(const contrad_conv_desc* d, int mode) {
 extern "C" long long contrad_conv2d_wino44_workspace_bytes(const contrad_conv_desc* d) {
   if (check_desc(d)) return -22;
   if (!wino44_ok(d, MODE_FWD) && !wino44_ok(d, MODE_DGRAD)) return -22;     // (neither mode runs: no workspace to size)
-  return wino44_workspace_bytes(d);
+  return filter_bytes(FILTER_WINO44, d);
 }
 
 extern "C" int contrad_conv2d_wino44(const contrad_conv_desc* d, int mode, const float* in, const float* wp,
@@ -2414,165 +2477,77 @@ extern "C" int contrad_conv2d_wino44(const contrad_conv_desc* d, int mode, const
   int rc = check_desc(d);
   if (rc) return rc;
   CONTRAD_ARG(in && wp && out && workspace && (mode == MODE_FWD || mode == MODE_DGRAD));
-  CONTRAD_ARG(aligned16(in, wp, workspace) && aligned16(ref, nullptr, nullptr));
-  CONTRAD_ARG(wino44_ok(d, mode) && workspace_bytes >= wino44_workspace_bytes(d));
-  if (mode == MODE_FWD) return launch_wino44<MODE_FWD>(d, in, wp, bias, ref, out, slope, gain, workspace, (hipStream_t)stream);
-  CONTRAD_ARG(bias == nullptr);
-  return launch_wino44<MODE_DGRAD>(d, in, wp, nullptr, ref, out, slope, gain, workspace, (hipStream_t)stream);
+  CONTRAD_ARG(aligned16(ref, nullptr, nullptr));
+  return launch_wino_forced(wino44_ok(d, mode) ? FILTER_WINO44 : 0, d, mode, in, wp, bias, ref, out, slope, gain, workspace,
+                            workspace_bytes, (hipStream_t)stream);
 }
 
+// The igemm engine's tile for this geometry, whichever family the route gives the layer to.
 extern "C" int contrad_conv2d_tile(const contrad_conv_desc* d, int mode, int* bm, int* bn) {
   int rc = check_desc(d);
   if (rc) return rc;
   CONTRAD_ARG(bm && bn && mode >= 0 && mode <= 2);
-  if (mode == MODE_FWD) {
-    const FwdPlan p = fwd_plan(d);
-    *bm = p.bm; *bn = p.bn;
-  } else if (mode == MODE_DGRAD) {
-    const FwdPlan p = dgrad_plan(d, true);
-    *bm = p.bm; *bn = p.bn;
-  } else {
-    int tm, tn, sp, pps;
-    wgrad_plan(d, bm, bn, &tm, &tn, &sp, &pps);
-  }
+  const FwdPlan p = igemm_route(d, mode, true).plan;
+  *bm = p.bm; *bn = p.bn;
   return 0;
 }
 
 extern "C" int contrad_conv2d_path(const contrad_conv_desc* d, int mode) {
   if (check_desc(d) || mode < 0 || mode > 2) return -22;
-  if (mode == MODE_FWD && fwd_k1_ok(d)) return 5;
-  if (mode != MODE_WGRAD && wino44_planned(d, mode)) return wino44_n32(d, mode) ? 11 : 9;
-  if (mode != MODE_WGRAD && wino_planned(d, mode)) return 7;
-  if (mode != MODE_WGRAD && wino22_planned(d, mode)) return 8;
-  if (wino23_planned(d, mode)) return 10;
-  if (mode == MODE_WGRAD && wino_wgrad_planned(d)) return 7;
-  if (mode == MODE_WGRAD && wino22_wgrad_planned(d)) return 8;
-  if (mode != MODE_WGRAD && conv_c32_ok(d)) return 6;
-  if (!vec_ok(d, mode)) return 0;
-  if (mode == MODE_WGRAD && wgrad_c32_ok(d)) return 4;
-  long long pps = 0;
-  if (mode == MODE_WGRAD) {
-    int bm, bn, tm, tn, sp, p;
-    wgrad_plan(d, &bm, &bn, &tm, &tn, &sp, &p);
-    pps = p;
-  }
-  if (!lean_ok(d, mode, pps)) return 1;
-  if (mode == MODE_FWD && fwd_plan(d).pixmajor) return 3;
-  if (mode == MODE_DGRAD && dgrad_plan(d, true).pixmajor) return 3;
-  if (mode == MODE_WGRAD) {
-    int bm, bn, tm, tn, sp, p;
-    wgrad_plan(d, &bm, &bn, &tm, &tn, &sp, &p);
-    if (wgrad_pixmajor_ok(d, bm, p)) return 3;
-  }
-  return 2;
+  return conv_route(d, mode, true).family;
 }
 
 extern "C" double contrad_conv2d_executed_fraction(const contrad_conv_desc* d, int mode) {
   if (check_desc(d) || mode < 0 || mode > 2) return -22.0;
-  if (contrad_conv2d_path(d, mode) == 9 || contrad_conv2d_path(d, mode) == 11) return 0.25;        // 36 transform-domain multiply-adds per 4x4 tile instead of 144
-  if (contrad_conv2d_path(d, mode) == 7) return 4.0 / 9.0;   // 16 transform-domain multiply-adds per 2x2 tile instead of 36
-  if (contrad_conv2d_path(d, mode) == 8) return 9.0 / 16.0;  // four phases x 9 per 2x2 tile instead of 64
-  if (contrad_conv2d_path(d, mode) == 10) return 25.0 / 36.0; // 9 + 6 + 6 + 4 planes of the four phases per 2x2 tile instead of 36
-  if (contrad_conv2d_path(d, mode) != 3) return 1.0;
-  return mode == MODE_DGRAD ? dgrad_valid_tap_fraction(d) : fwd_valid_tap_fraction(d);
+  switch (conv_route(d, mode, true).family) {
+    case FAM_WINO44: case FAM_WINO44N: return 0.25;      // 36 transform-domain multiply-adds per 4x4 tile instead of 144
+    case FAM_WINO: return 4.0 / 9.0;                     // 16 transform-domain multiply-adds per 2x2 tile instead of 36
+    case FAM_WINO22: return 9.0 / 16.0;                  // four phases x 9 per 2x2 tile instead of 64
+    case FAM_WINO23: return 25.0 / 36.0;                 // 9 + 6 + 6 + 4 planes of the four phases per 2x2 tile instead of 36
+    case FAM_LEAN_SKIP: return mode == MODE_DGRAD ? dgrad_valid_tap_fraction(d) : fwd_valid_tap_fraction(d);
+    default: return 1.0;
+  }
 }
 
 extern "C" long long contrad_conv2d_grid_blocks(const contrad_conv_desc* d, int mode, int with_workspace) {
   if (check_desc(d) || mode < 0 || mode > 2) return -22;
-  if (mode != MODE_WGRAD && with_workspace && wino44_planned(d, mode)) return wino44_grid(wino44_args(d, mode));   // (512 threads each)
-  if (mode != MODE_WGRAD && with_workspace && wino_planned(d, mode)) return wino_grid(wino_args(d, mode));
-  if (with_workspace && wino23_planned(d, mode)) return wino23_grid(wino23_args(d));
-  if (mode != MODE_WGRAD && with_workspace && wino22_planned(d, mode)) {
-    const wino22::Args a = wino22_args(d, mode);
-    return 8 * std::min(WINO_CUS / 8, cdiv(a.NTB, 8) * a.NKB * (mode == MODE_DGRAD ? 4 : 1));
+  const Route r = conv_route(d, mode, with_workspace != 0);
+  switch (r.family) {      // the special families: their own grid helpers (Winograd: 512 threads each)
+    case FAM_WINO:
+      return mode == MODE_WGRAD ? wino_wgrad_grid(wino_wgrad_args(d)) : wino_grid(wino_args(d, mode));
+    case FAM_WINO22:
+      return mode == MODE_WGRAD ? wino22_wgrad_grid(wino22_wgrad_args(d)) : wino22_grid(wino22_args(d, mode));
+    case FAM_WINO44: case FAM_WINO44N: return wino44_grid(wino44_args(d, mode));
+    case FAM_WINO23: return wino23_grid(wino23_args(d));
+    case FAM_WGRAD_C32: return wgrad_c32_blocks(d);
+    case FAM_CONV_C32: return conv_c32_blocks(d);
+    case FAM_FWD_K1: return cdivll((long long)d->N * d->Ho * d->Wo, 4);
+    default: break;
   }
-  if (mode == MODE_FWD) {
-    const FwdPlan p = fwd_plan(d);
-    const long long M = (long long)d->N * d->Ho * d->Wo;
-    if (fwd_k1_ok(d)) return cdivll(M, 4);
-    if (conv_c32_ok(d)) return conv_c32_blocks(d);
-    if (p.pixmajor == 1) return (long long)cdiv(d->N, p.bm) * d->Ho * d->Wo * cdiv(d->K, p.bn);
-    if (p.pixmajor == 2) return (long long)border_class_tiles(d, MODE_FWD, p.bm) * cdiv(d->K, p.bn);
-    return cdivll(M, p.bm) * cdiv(d->K, p.bn) * (with_workspace ? p.splits : 1);
-  }
-  if (mode == MODE_DGRAD) {
-    if (conv_c32_ok(d)) return conv_c32_blocks(d);
-    const int s = d->stride;
-    const long long Mc = (long long)d->N * cdiv(d->H, s) * cdiv(d->W, s);
-    const FwdPlan p = dgrad_plan(d, with_workspace != 0);
-    const int tiles_m = p.pixmajor == 2 ? border_class_tiles(d, MODE_DGRAD, p.bm)
-                        : p.pixmajor == 1 ? cdiv(d->N, p.bm) * cdiv(d->H, s) * cdiv(d->W, s) : cdiv((int)Mc, p.bm);
-    const int tiles_n = cdiv(d->C, p.bn);
-    if (p.splits > 1) return (long long)tiles_m * tiles_n * p.splits;
-    if (p.balanced && vec_ok(d, MODE_DGRAD) && lean_ok(d, MODE_DGRAD, 0) && p.pixmajor == 0) {
-      IgemmArgs a{};
-      const long long blocks = dgrad_balance(d, tiles_m, &a);
-      if (blocks > 0) return blocks * tiles_n;
-    }
-    if (p.pixmajor == 1 && s == 2) return (long long)tiles_m * tiles_n * s * s;     // class-major, one group (px_full == 2)
-    const int cgroup = (s > 1) ? dgrad_cgroup(tiles_m, tiles_n) : 0;
-    const int tm_pad = cgroup > 0 ? cdiv(tiles_m, cgroup) * cgroup : tiles_m;
-    return (long long)tm_pad * tiles_n * s * s;
-  }
-  if (wino_wgrad_planned(d)) { const wino::WArgs a = wino_wgrad_args(d); return (long long)a.CB * a.KB * wino_wgrad_splits(a); }
-  if (wino22_wgrad_planned(d)) { const wino22::WArgs a = wino22_wgrad_args(d); return (long long)a.RBN * a.KB * wino22_wgrad_splits(a); }
-  if (wgrad_c32_ok(d)) return wgrad_c32_blocks(d);
-  int bm, bn, tm, tn, splits, pps;
-  wgrad_plan(d, &bm, &bn, &tm, &tn, &splits, &pps);
-  return (long long)tm * tn * splits;
+  IgemmArgs a{};
+  const dim3 grid = mode == MODE_FWD ? fwd_setup(d, r.plan, &a) : mode == MODE_DGRAD ? dgrad_setup(d, r.plan, &a) : wgrad_setup(d, r.plan, &a);
+  // (a forward split-K plan has no launch without its workspace -- the call is -22 --: reported as one slab's blocks)
+  if (mode == MODE_FWD && !with_workspace) return grid.x;
+  return (long long)grid.x * grid.y;
 }
 
+// (a layer the plan gives to Winograd reports the table of its workspace-less fall-through route)
 extern "C" int contrad_conv2d_tile_order(const contrad_conv_desc* d, int mode, unsigned char* out, int capacity) {
   if (check_desc(d) || (mode != MODE_FWD && mode != MODE_DGRAD) || !out || capacity <= 0) return -22;
-  int taps[256];
-  unsigned char full[256];
-  int nt = 0;
-  if (mode == MODE_FWD) {
-    const FwdPlan p = fwd_plan(d);
-    if (p.pixmajor != 1 || !vec_ok(d, MODE_FWD)) return 0;
-    for (int ho = 0; ho < d->Ho; ++ho)
-      for (int wo = 0; wo < d->Wo; ++wo) {
-        int vh = 0, vw = 0;
-        for (int kh = 0; kh < d->KH; ++kh) vh += (unsigned)(ho * d->stride - d->pad + kh) < (unsigned)d->H;
-        for (int kw = 0; kw < d->KW; ++kw) vw += (unsigned)(wo * d->stride - d->pad + kw) < (unsigned)d->W;
-        taps[ho * d->Wo + wo] = vh * vw;
-      }
-    if (!pixel_order_full(taps, d->Ho * d->Wo, cdiv(d->N, p.bm), cdiv(d->K, p.bn), full, 8)) return 0;
-    nt = cdiv(d->N, p.bm) * d->Ho * d->Wo;
-  } else {
-    const FwdPlan p = dgrad_plan(d, true);
-    if (p.pixmajor != 1 || p.splits > 1 || !vec_ok(d, MODE_DGRAD)) return 0;
-    if (d->stride == 1) {
-      for (int h = 0; h < d->H; ++h)
-        for (int w = 0; w < d->W; ++w) {
-          int vh = 0, vw = 0;
-          for (int kh = 0; kh < d->KH; ++kh) vh += (unsigned)(h + d->pad - kh) < (unsigned)d->Ho;
-          for (int kw = 0; kw < d->KW; ++kw) vw += (unsigned)(w + d->pad - kw) < (unsigned)d->Wo;
-          taps[h * d->W + w] = vh * vw;
-        }
-      if (!pixel_order_full(taps, d->H * d->W, cdiv(d->N, p.bm), cdiv(d->C, p.bn), full, 8)) return 0;
-      nt = cdiv(d->N, p.bm) * d->H * d->W;
-    } else {
-      const int npix = dgrad_strided_class0_taps(d, taps);
-      if (!npix || !dgrad_strided_full_ok(d, p.bm, p.bn)) return 0;
-      pixel_order_full(taps, npix, cdiv(d->N, p.bm), cdiv(d->C, p.bn), full, 2);
-      nt = cdiv(d->N, p.bm) * npix;
-    }
-  }
+  const Route r = conv_route(d, mode, true, 0);
+  if (r.family != FAM_LEAN_SKIP || r.plan.pixmajor != 1 || r.plan.splits > 1) return 0;
+  const int npix = mode == MODE_FWD ? d->Ho * d->Wo : cdiv(d->H, d->stride) * cdiv(d->W, d->stride);
+  unsigned char order[256] = {};
+  if (!pixel_table(d, mode, r.plan, npix, order)) return 0;
+  const int nt = cdiv(d->N, r.plan.bm) * npix;
   if (nt > capacity) return -22;
-  memcpy(out, full, (size_t)nt);
+  memcpy(out, order, (size_t)nt);
   return nt;
 }
 
 extern "C" long long contrad_conv2d_wgrad_workspace_bytes(const contrad_conv_desc* d) {
   if (check_desc(d)) return -22;
-  if (wino_wgrad_planned(d)) return wino_wgrad_workspace_bytes(d);
-  if (wino22_wgrad_planned(d)) return wino22_wgrad_workspace_bytes(d);
-  if (wgrad_c32_ok(d))
-    return (long long)wgrad_c32_blocks(d) * ((long long)d->KH * d->KW * d->C + 1) * d->K * (long long)sizeof(float);
-  int bm, bn, tm, tn, splits, pps;
-  wgrad_plan(d, &bm, &bn, &tm, &tn, &splits, &pps);
-  return (long long)splits * ((long long)d->KH * d->KW * d->C + 1) * d->K * (long long)sizeof(float);
+  return conv_route(d, MODE_WGRAD, true).workspace_bytes;
 }
 
 extern "C" int contrad_conv2d_wgrad(const contrad_conv_desc* d, const float* x, const float* gy,
@@ -2582,50 +2557,30 @@ extern "C" int contrad_conv2d_wgrad(const contrad_conv_desc* d, const float* x, 
   if (rc) return rc;
   CONTRAD_ARG(x && gy && dwp && workspace);
   if (vec_ok(d, MODE_WGRAD)) CONTRAD_ARG(aligned16(x, gy, workspace));
-  CONTRAD_ARG(workspace_bytes >= contrad_conv2d_wgrad_workspace_bytes(d));
-  if (wino_wgrad_planned(d)) return launch_wino_wgrad(d, x, gy, dwp, dbias, workspace, (hipStream_t)stream);   // wino.h, F(3x3, 2x2)
-  if (wino22_wgrad_planned(d)) return launch_wino22_wgrad(d, x, gy, dwp, dbias, workspace, (hipStream_t)stream);   // wino22.h
-  if (wgrad_c32_ok(d)) {   // (C = K = 32: vec_ok holds, so the operands were checked for 16-byte alignment above)
-    // accumulator-stationary kernel for the 32 -> 32 channel 3x3 layers (wgrad_c32.h): one partial per block, summed
-    // by the same fixed-order reduce as the split-K slabs
-    const int blocks = wgrad_c32_blocks(d);
-    const long long total = (long long)d->KH * d->KW * d->C * d->K;
-    float* bias_ws = dbias ? workspace + (size_t)blocks * total : nullptr;
-    rc = launch_wgrad_c32(d, x, gy, workspace, bias_ws, (hipStream_t)stream);
-    if (rc) return rc;
-    int R = 1;
-    while (R < 64 && R * 2 <= blocks && (total / 4) * R < 65536) R <<= 1;
-    long long rb = ((total / 4) * R + 255) / 256;
-    if (rb > 2048) rb = 2048;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((int)rb), dim3(256), 0, (hipStream_t)stream, workspace, dwp,
-                       d->KH * d->KW * d->C, d->K, d->ldw, blocks, bias_ws, dbias, R);
-    CONTRAD_CHECK_LAUNCH();
-    return 0;
+  const Route r = conv_route(d, MODE_WGRAD, true);
+  CONTRAD_ARG(workspace_bytes >= r.workspace_bytes);
+  hipStream_t s = (hipStream_t)stream;
+  const int Kg = d->KH * d->KW * d->C;
+  switch (r.family) {
+    case FAM_WINO: return launch_wino_wgrad(d, x, gy, dwp, dbias, workspace, s);        // wino.h, F(3x3, 2x2)
+    case FAM_WINO22: return launch_wino22_wgrad(d, x, gy, dwp, dbias, workspace, s);    // wino22.h
+    case FAM_WGRAD_C32: {   // (C = K = 32: vec_ok holds, so the operands were checked for 16-byte alignment above)
+      // accumulator-stationary kernel for the 32 -> 32 channel 3x3 layers (wgrad_c32.h): one partial per block, summed
+      // by the same fixed-order reduce as the split-K slabs
+      const int blocks = wgrad_c32_blocks(d);
+      float* bias_ws = dbias ? workspace + (size_t)blocks * Kg * d->K : nullptr;
+      rc = launch_wgrad_c32(d, x, gy, workspace, bias_ws, s);
+      return rc ? rc : launch_wgrad_reduce(workspace, dwp, Kg, d->K, d->ldw, blocks, bias_ws, dbias, s);
+    }
+    default: break;      // the igemm engine
   }
-  int bm, bn, splits, pps;
+  const FwdPlan& p = r.plan;
+  CONTRAD_ARG(dbias == nullptr || r.vec);   // the fused bias gradient needs the float4 path
+  CONTRAD_ARG((long long)d->N * d->Ho * d->Wo < (1ll << 31) - 4096);
   IgemmArgs a{};
-  wgrad_plan(d, &bm, &bn, &a.tiles_m, &a.tiles_n, &splits, &pps);
-  a.A = x; a.B = gy; a.C = workspace; a.d = *d;
-  a.M = d->KH * d->KW * d->C; a.Ncol = d->K; a.Kg = a.M;
-  const bool fused_bias = dbias != nullptr && vec_ok(d, MODE_WGRAD);
-  CONTRAD_ARG(dbias == nullptr || fused_bias);   // the fused bias gradient needs the float4 path
-  a.bias_ws = fused_bias ? workspace + (size_t)splits * a.M * a.Ncol : nullptr;
-  const long long P = (long long)d->N * d->Ho * d->Wo;
-  CONTRAD_ARG(P < (1ll << 31) - 4096);
-  a.P = (int)P; a.ptiles_per_split = pps;
-  a.pixmajor = wgrad_pixmajor_ok(d, bm, pps) ? 1 : 0;
-  rc = dispatch<MODE_WGRAD>(a, bm, bn, vec_ok(d, MODE_WGRAD), dim3(a.tiles_m * a.tiles_n, splits),
-                            (hipStream_t)stream);
-  if (rc) return rc;
-  const long long total = (long long)a.M * a.Ncol;
-  // split-lanes per element group: enough threads (~64 k) to cover the memory latency when the output is small
-  int R = 1;
-  while (R < 64 && R * 2 <= splits && (total / 4) * R < 65536) R <<= 1;
-  long long blocks = ((total / 4) * R + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, workspace, dwp,
-                     a.M, a.Ncol, d->ldw, splits, a.bias_ws, fused_bias ? dbias : nullptr, R);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
+  a.A = x; a.B = gy; a.C = workspace;
+  a.bias_ws = dbias ? workspace + (size_t)p.splits * Kg * d->K : nullptr;
+  const dim3 grid = wgrad_setup(d, p, &a);
+  rc = dispatch<MODE_WGRAD>(a, p.bm, p.bn, r.vec, grid, s);
+  return rc ? rc : launch_wgrad_reduce(workspace, dwp, Kg, d->K, d->ldw, p.splits, a.bias_ws, dbias, s);
 }

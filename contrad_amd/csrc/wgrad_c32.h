@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_c32_kernel(const WgradC32Args a)
 
 // 3x3, stride 1, pad 1, 32 -> 32 channels, dense NHWC, grid divisible into 4 x 32 tiles
 inline bool wgrad_c32_ok(const contrad_conv_desc* d) {
-  static const bool enabled = []() { const char* e = contrad_dev_env("CONTRAD_WGRAD_C32"); return !(e && e[0] == '0'); }();
+  static const bool enabled = contrad_dev_on("CONTRAD_WGRAD_C32");
   return enabled && d->C == 32 && d->K == 32 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 &&
          d->ldx == 32 && d->ldy == 32 && d->ldw == 32 && (d->W % WC_TW) == 0 && (d->H % WC_TH) == 0 &&
          (long long)d->N * d->H * d->W >= 1 << 16;       // (small maps: the engine's split-K GEMM has enough reuse)

@@ -171,7 +171,8 @@ int contrad_conv2d_dgrad_ws_u(const contrad_conv_desc* d, const float* gy, const
  * gradient, accumulated for free from the gy tiles the kernel streams anyway. */
 long long contrad_conv2d_wgrad_workspace_bytes(const contrad_conv_desc* d);
 /* Introspection for profiling: block tile (bm x bn x 32) the launcher picks for `mode` (0 fwd, 1 dgrad,
- * 2 wgrad) on this geometry, i.e. which igemm_kernel<mode, bm, bn> instance runs. */
+ * 2 wgrad) on this geometry, i.e. which igemm_kernel<mode, bm, bn> instance runs when the layer is the igemm engine's
+ * (contrad_conv2d_path 0 - 3; for the other families: the tile it would take). */
 int contrad_conv2d_tile(const contrad_conv_desc* d, int mode, int* bm, int* bn);
 /* Which kernel family serves this shape: 0 = general scalar-gather (igemm_kernel<..., false>), 1 = general float4
  * (igemm_kernel<..., true>), 2 = lean loop (igemm_lean_kernel), 3 = lean loop on tiles that skip padding taps (small maps:
@@ -186,7 +187,9 @@ int contrad_conv2d_tile(const contrad_conv_desc* d, int mode, int* bm, int* bn);
  * output channels not a multiple of 64, and the 4x4 maps; with a workspace);  negative = bad descriptor.  Profiling aid.
  * Workspace assumption: this and contrad_conv2d_executed_fraction describe the plan of a call that passes a workspace of
  * contrad_conv2d_{fwd,dgrad,wgrad}_workspace_bytes.  contrad_conv2d_fwd_add / contrad_conv2d_dgrad_ws with a NULL (or
- * smaller) workspace skip paths 7 - 11 and run the direct kernels instead (contrad_conv2d_dgrad: never split-K either). */
+ * smaller) workspace skip paths 7 - 11 and run the direct kernels instead (contrad_conv2d_dgrad: never split-K either).
+ * The launchers and every plan query here (path, filter_kind, *_workspace_bytes, executed_fraction, grid_blocks,
+ * tile_order) read ONE route decision (csrc/igemm.hip: conv_route), so what they report is what a launch does. */
 int contrad_conv2d_path(const contrad_conv_desc* d, int mode);
 /* Share of the layer's nominal multiply-adds (2*N*Ho*Wo*K*C*KH*KW, the count every roofline here is quoted on, padding
  * taps included as in the reference's dense layer) that the kernel actually issues: 1 except on pixel-major tiles (path
@@ -202,7 +205,9 @@ long long contrad_conv2d_grid_blocks(const contrad_conv_desc* d, int mode, int w
  * M-tiles, out[i] = image block * pixels + pixel of the i-th M-tile (for the strided data gradient: of every parity class,
  * the pixel mirrored along the class's odd axes), chosen so that the tiles a CU is dealt -- an XCD's blocks go round-robin
  * over its 32 CUs -- carry equal work.  Returns the number of entries written, 0 when the launch uses no such table
- * (image-major tiles, border classes, more than 256 tiles), negative = bad argument.  Host logic only; lets the plan be
+ * (image-major tiles, border classes, more than 256 tiles), negative = bad argument.  For a layer the plan gives to
+ * Winograd (path 7 - 11) this is the table of the direct route a call without the filter workspace falls through to.
+ * Host logic only; lets the plan be
  * tested without a GPU (tests/test_abi_cpu.py). */
 int contrad_conv2d_tile_order(const contrad_conv_desc* d, int mode, unsigned char* out, int capacity);
 int contrad_conv2d_wgrad(const contrad_conv_desc* d, const float* x, const float* gy, float* dwp,

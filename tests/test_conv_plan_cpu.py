@@ -127,6 +127,35 @@ def test_the_gpu_matrix_reaches_every_planned_path(L):
     assert {P for (P, _, _) in declared} == set(range(12))       # (and every family of contrad_conv2d_path's list)
 
 
+def test_the_plan_queries_agree_with_one_another(L):
+    """The queries read one route decision (csrc/igemm.hip: conv_route): over the same descriptors, modes 0 and 1, the
+    transformed-filter kind is the path's family (11 reads 9's filter) and non-zero exactly on the Winograd paths, its bytes
+    are the mode's workspace, and only a path-3 plan -- or the direct route a Winograd plan falls through to without its
+    workspace -- has a tile-order table."""
+    path, kind, order = L.raw('contrad_conv2d_path'), L.raw('contrad_conv2d_filter_kind'), L.raw('contrad_conv2d_tile_order')
+    ws = (L.raw('contrad_conv2d_fwd_workspace_bytes'), L.raw('contrad_conv2d_dgrad_workspace_bytes'))
+    buf = (ctypes.c_ubyte * 256)()
+    rows = fallback = 0
+    for d in list(baseline_descs()) + list(grid_descs()):
+        for mode in (0, 1):
+            P = path(ctypes.byref(d), mode)
+            if P < 0:
+                continue
+            rows += 1
+            nb = ctypes.c_longlong(-1)
+            k = kind(ctypes.byref(d), mode, ctypes.byref(nb))
+            what = (d.N, d.H, d.W, d.C, d.K, d.KH, d.stride, d.pad, mode, P, k)
+            assert (k != 0) == (7 <= P <= 11), what
+            assert k == (0 if P < 7 else 9 if P == 11 else P), what
+            assert nb.value == (ws[mode](ctypes.byref(d)) if k else 0), what
+            n = order(ctypes.byref(d), mode, buf, 256)
+            assert n >= 0, what
+            if n > 0:
+                assert P == 3 or 7 <= P <= 11, what
+                fallback += P != 3
+    assert rows > 80000 and fallback > 0          # (the grid reaches the fall-through kind too)
+
+
 def test_the_gpu_matrix_has_guard_bands_where_the_layout_allows(L):
     """Every output has a leading dimension above its channel count (sentinel columns) unless its family needs dense rows."""
     M = _gpu_matrix()
