@@ -1,0 +1,364 @@
+// Streaming kernels of conditional Langevin sampling in latent space (cDDLS, contrad_amd/cddls.py; gfx950): everything
+// of one Langevin step that is not a convolution, plus the counter-based normal generator the step draws its noise from.
+//
+//   cddls_feature_seed_kernel      g = (g_head + c) * lrelu'(a6): the gradient entering D's trunk, from the logit head's
+//                                  data gradient and the class row of the linear-evaluation head (one broadcast row)
+//   cddls_bn_relu_bwd_eval_kernel  dx = dy * [y > 0] * gamma / sqrt(running_var + eps): eval-mode BatchNorm + ReLU backward
+//   cddls_compose_kernel           x = G(z) + eps * z2 (optionally clamped to [0, 1]: the final images)
+//   cddls_image_end_kernel         gradient entering G's last transposed conv (through 0.5 tanh + 0.5) and the z2 update
+//   cddls_latent_update_kernel     the z update with its clamp; the block that finishes last advances the step counter
+//   cddls_energy_kernel            per-sample energy (diagnostic), one block per sample, fixed summation order
+//   cddls_normal_fill_kernel       the generator alone (tests, the initial z2)
+//
+// Noise: Philox4x32-10, key = the 64-bit seed, counter = (quad index of the element, step, stream id, 0); one counter gives
+// the four normals of elements 4q .. 4q + 3 by Box-Muller (words 0, 1 -> elements 0, 1; words 2, 3 -> elements 2, 3).  A
+// draw depends on (seed, stream, step, element) only, never on the launch shape.  The step is read from device memory
+// (state[0]); state[1] is the arrival counter of cddls_latent_update_kernel, whose last block writes state[0] + 1 -- every
+// block has read the step by then, so one captured graph serves every step and replays the eager run's bits.
+//
+// All kernels: one thread per quad of elements, grid-stride, 16-byte accesses when every pointer is 16-byte aligned (the
+// quad that straddles the end and unaligned buffers take the scalar form), wave64, no LDS except the energy reduction.
+#include "../../include/contrad_hip.h"
+#include "common.h"
+
+namespace {
+
+// stream ids of the counter (include/contrad_hip.h; contrad_amd/cddls.py passes CD_STREAM_INIT's value to the fill entry)
+enum CddlsStream { CD_STREAM_Z = 0, CD_STREAM_Z2 = 1, CD_STREAM_INIT = 2 };
+
+constexpr int CD_THREADS = 256;
+constexpr int CD_MAX_BLOCKS = 2048;      // 8 blocks per CU: enough loads in flight for an HBM stream, grid-stride beyond
+
+__device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+    const unsigned n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+}
+
+// -log(u), u = ((w >> 8) + 0.5) * 2^-24 = (2x + 1) * 2^-25 in (0, 1), without rounding u: below one half 2x + 1 is a 24-bit
+// integer; above, 1 - u = (2^25 - 2x - 1) * 2^-25 is one, and log1pf keeps the small results (radius near 0) accurate.
+__device__ __forceinline__ float neg_log_uniform(unsigned w) {
+  const unsigned x = w >> 8;
+  if (x < (1u << 23)) return -logf((float)(2u * x + 1u) * 0x1p-25f);
+  return -log1pf(-(float)((1u << 25) - 2u * x - 1u) * 0x1p-25f);
+}
+
+__device__ __forceinline__ void box_muller4(const unsigned w[4], float n[4]) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float r = sqrtf(2.f * neg_log_uniform(w[2 * h]));
+    const float u = ((float)(w[2 * h + 1] >> 8) + 0.5f) * 0x1p-24f;    // the angle tolerates the rounding (2 pi 2^-25 rad)
+    float s, c;
+    sincospif(2.f * u, &s, &c);
+    n[2 * h] = r * c;
+    n[2 * h + 1] = r * s;
+  }
+}
+
+__device__ __forceinline__ void philox_words(long long quad, int step, int stream_id, long long seed, unsigned w[4]) {
+  w[0] = (unsigned)quad; w[1] = (unsigned)step; w[2] = (unsigned)stream_id; w[3] = 0u;
+  philox4x32_10(w, (unsigned)((unsigned long long)seed & 0xffffffffull), (unsigned)((unsigned long long)seed >> 32));
+}
+
+__device__ __forceinline__ void load4(const float* __restrict__ p, long long i, long long n, bool vec, float v[4]) {
+  if (vec && i + 3 < n) {
+    const float4 t = *reinterpret_cast<const float4*>(p + i);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = (i + k < n) ? p[i + k] : 0.f;
+  }
+}
+
+__device__ __forceinline__ void store4(float* __restrict__ p, long long i, long long n, bool vec, const float v[4]) {
+  if (vec && i + 3 < n) {
+    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (i + k < n) p[i + k] = v[k];
+  }
+}
+
+// the step's normals of quad q: explicit buffer (tests) or the generator
+__device__ __forceinline__ void noise4(const float* __restrict__ noise, long long q, long long n, bool vec, int step,
+                                       int stream_id, long long seed, float v[4]) {
+  if (noise) {
+    load4(noise, 4 * q, n, vec, v);
+  } else {
+    unsigned w[4];
+    philox_words(q, step, stream_id, seed, w);
+    box_muller4(w, v);
+  }
+}
+
+__global__ __launch_bounds__(CD_THREADS) void cddls_normal_fill_kernel(float* __restrict__ out,
+                                                                       unsigned* __restrict__ words, long long n,
+                                                                       long long seed, int stream_id,
+                                                                       const int* __restrict__ step_dev, int step,
+                                                                       int vec) {
+  const int st = step_dev ? step_dev[0] : step;
+  const long long nq = (n + 3) / 4;
+  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
+    unsigned w[4];
+    float v[4];
+    philox_words(q, st, stream_id, seed, w);
+    box_muller4(w, v);
+    if (out) store4(out, 4 * q, n, vec != 0, v);
+    if (words) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (4 * q + k < n) words[4 * q + k] = w[k];
+    }
+  }
+}
+
+__global__ __launch_bounds__(CD_THREADS) void cddls_feature_seed_kernel(const float* g_head,
+                                                                        const float* __restrict__ c_row,
+                                                                        const float* __restrict__ act, float* out,
+                                                                        long long N, int F, float slope) {
+  // F % 4 == 0 and 16-byte aligned rows (checked by the launcher): a quad never straddles two samples
+  const int fq = F / 4;
+  const long long nq = N * fq;
+  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
+    const int j = (int)(q % fq);
+    const float4 g = *reinterpret_cast<const float4*>(g_head + 4 * q);
+    const float4 c = *reinterpret_cast<const float4*>(c_row + 4 * j);
+    const float4 a = *reinterpret_cast<const float4*>(act + 4 * q);
+    float4 o;
+    o.x = (g.x + c.x) * (a.x > 0.f ? 1.f : slope);
+    o.y = (g.y + c.y) * (a.y > 0.f ? 1.f : slope);
+    o.z = (g.z + c.z) * (a.z > 0.f ? 1.f : slope);
+    o.w = (g.w + c.w) * (a.w > 0.f ? 1.f : slope);
+    *reinterpret_cast<float4*>(out + 4 * q) = o;
+  }
+}
+
+// y / dy: rows of stride ldy in the layout bn_relu_apply WROTE (perm_hw > 1: column c = ch * perm_hw + hw of x sits at
+// hw * (K / perm_hw) + ch); dx: rows of stride ldx in x's own column order.
+__global__ __launch_bounds__(CD_THREADS) void cddls_bn_relu_bwd_eval_kernel(const float* dy,
+                                                                            const float* __restrict__ y, float* dx,
+                                                                            long long M, int K, int ldy, int ldx,
+                                                                            const float* __restrict__ gamma,
+                                                                            const float* __restrict__ var, float eps,
+                                                                            int perm_hw, int vec) {
+  if (vec) {                        // perm_hw == 1, K % 4 == 0, both strides % 4 == 0, aligned bases
+    const int kq = K / 4;
+    const long long nq = M * kq;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
+      const long long r = q / kq;
+      const int c = (int)(q - r * kq) * 4;
+      const float4 g = *reinterpret_cast<const float4*>(dy + r * ldy + c);
+      const float4 a = *reinterpret_cast<const float4*>(y + r * ldy + c);
+      const float4 gm = *reinterpret_cast<const float4*>(gamma + c);
+      const float4 vr = *reinterpret_cast<const float4*>(var + c);
+      float4 o;
+      o.x = a.x > 0.f ? g.x * (gm.x * rsqrtf(vr.x + eps)) : 0.f;
+      o.y = a.y > 0.f ? g.y * (gm.y * rsqrtf(vr.y + eps)) : 0.f;
+      o.z = a.z > 0.f ? g.z * (gm.z * rsqrtf(vr.z + eps)) : 0.f;
+      o.w = a.w > 0.f ? g.w * (gm.w * rsqrtf(vr.w + eps)) : 0.f;
+      *reinterpret_cast<float4*>(dx + r * ldx + c) = o;
+    }
+    return;
+  }
+  const long long total = M * K;
+  const int nch = K / perm_hw;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+    const long long r = e / K;
+    const int p = (int)(e - r * K);                     // position in y's layout: consecutive lanes read consecutive floats
+    int c = p;
+    if (perm_hw > 1) {
+      const int hw = p / nch, ch = p - hw * nch;
+      c = ch * perm_hw + hw;
+    }
+    const float g = dy[r * ldy + p];
+    dx[r * ldx + c] = y[r * ldy + p] > 0.f ? g * (gamma[c] * rsqrtf(var[c] + eps)) : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(CD_THREADS) void cddls_compose_kernel(const float* __restrict__ gout,
+                                                                   const float* __restrict__ z2, float* __restrict__ x,
+                                                                   long long n, float eps, int clamp01, int vec) {
+  const long long nq = (n + 3) / 4;
+  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
+    float g[4], b[4], o[4];
+    load4(gout, 4 * q, n, vec != 0, g);
+    load4(z2, 4 * q, n, vec != 0, b);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      o[k] = fmaf(eps, b[k], g[k]);
+      if (clamp01) o[k] = fminf(fmaxf(o[k], 0.f), 1.f);
+    }
+    store4(x, 4 * q, n, vec != 0, o);
+  }
+}
+
+__global__ __launch_bounds__(CD_THREADS) void cddls_image_end_kernel(const float* __restrict__ gx,
+                                                                     const float* __restrict__ gout, float* z2,
+                                                                     float* __restrict__ g_lin, long long n, float eps,
+                                                                     float noise_scale, const float* __restrict__ noise,
+                                                                     long long seed, const int* __restrict__ state,
+                                                                     int vec) {
+  const int step = state ? state[0] : 0;
+  const float he = 0.5f * eps;
+  const long long nq = (n + 3) / 4;
+  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
+    float g[4], o[4], b[4], nz[4], gl[4];
+    load4(gx, 4 * q, n, vec != 0, g);
+    load4(gout, 4 * q, n, vec != 0, o);
+    load4(z2, 4 * q, n, vec != 0, b);
+    noise4(noise, q, n, vec != 0, step, CD_STREAM_Z2, seed, nz);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float t = 2.f * o[k] - 1.f;                       // tanh of the generator's last pre-activation
+      gl[k] = g[k] * (0.5f * (1.f - t * t));
+      const float gz2 = fmaf(eps, g[k], b[k]);                // d e / d z2 = eps * g_x + z2
+      b[k] = fmaf(noise_scale, nz[k], fmaf(-he, gz2, b[k]));
+    }
+    store4(g_lin, 4 * q, n, vec != 0, gl);
+    store4(z2, 4 * q, n, vec != 0, b);
+  }
+}
+
+__global__ __launch_bounds__(CD_THREADS) void cddls_latent_update_kernel(float* z, const float* __restrict__ gz,
+                                                                         long long n, float eps, float noise_scale,
+                                                                         const float* __restrict__ noise,
+                                                                         long long seed, int* state, int vec) {
+  const int step = state ? state[0] : 0;
+  const float he = 0.5f * eps;
+  const long long nq = (n + 3) / 4;
+  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
+    float a[4], g[4], nz[4];
+    load4(z, 4 * q, n, vec != 0, a);
+    load4(gz, 4 * q, n, vec != 0, g);
+    noise4(noise, q, n, vec != 0, step, CD_STREAM_Z, seed, nz);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float v = fmaf(noise_scale, nz[k], fmaf(-he, g[k], a[k]));
+      a[k] = fminf(fmaxf(v, -1.f), 1.f);
+    }
+    store4(z, 4 * q, n, vec != 0, a);
+  }
+  if (state == nullptr) return;
+  // every thread of this block has read state[0] (the value is in a register before the barrier); the block that draws
+  // the last ticket knows that all the others have too
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int t = __hip_atomic_fetch_add(state + 1, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == (int)gridDim.x - 1) {
+      __hip_atomic_store(state + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(state, step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// e[n] = -d[n] + <feat[n], c_row> + bias_term[0] + 0.5 |z2[n]|^2 with c_row = -lbd * w_y (trunk order), bias_term = -lbd * b_y
+__global__ __launch_bounds__(CD_THREADS) void cddls_energy_kernel(const float* __restrict__ d, int ldd,
+                                                                  const float* __restrict__ feat,
+                                                                  const float* __restrict__ c_row,
+                                                                  const float* __restrict__ bias_term,
+                                                                  const float* __restrict__ z2, float* __restrict__ e,
+                                                                  int F, long long P) {
+  __shared__ float red[16];
+  const long long n = blockIdx.x;
+  const float* f = feat + n * F;
+  const float* b = z2 + n * P;
+  float s = 0.f, q = 0.f;
+  for (int i = threadIdx.x; i < F; i += blockDim.x) s = fmaf(f[i], c_row[i], s);
+  for (long long i = threadIdx.x; i < P; i += blockDim.x) q = fmaf(b[i], b[i], q);
+  s = block_sum(s, red);
+  q = block_sum(q, red);
+  if (threadIdx.x == 0) e[n] = (s + bias_term[0] - d[n * ldd]) + 0.5f * q;
+}
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+inline int quad_grid(long long quads) {
+  long long g = (quads + CD_THREADS - 1) / CD_THREADS;
+  if (g < 1) g = 1;
+  return (int)(g > CD_MAX_BLOCKS ? CD_MAX_BLOCKS : g);
+}
+
+inline float noise_scale_of(float eps, float sigma_n) { return (float)((double)sigma_n * sqrt((double)eps)); }
+
+}  // namespace
+
+extern "C" int contrad_cddls_normal_fill(float* out, unsigned* words, long long n, long long seed, int stream_id,
+                                         const void* step_dev, int step, int grid_blocks, contrad_stream_t stream) {
+  CONTRAD_ARG((out || words) && n >= 1 && stream_id >= 0 && grid_blocks >= 0 && grid_blocks <= 65536);
+  const int grid = grid_blocks > 0 ? grid_blocks : quad_grid((n + 3) / 4);
+  hipLaunchKernelGGL(cddls_normal_fill_kernel, dim3(grid), dim3(CD_THREADS), 0, (hipStream_t)stream, out, words, n, seed,
+                     stream_id, static_cast<const int*>(step_dev), step, (int)(out == nullptr || al16(out)));
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int contrad_cddls_feature_seed(const float* g_head, const float* c_row, const float* act, float* out,
+                                          long long N, int F, float slope, contrad_stream_t stream) {
+  CONTRAD_ARG(g_head && c_row && act && out && N >= 1 && F >= 4 && (F & 3) == 0);
+  CONTRAD_ARG(al16(g_head) && al16(c_row) && al16(act) && al16(out));
+  hipLaunchKernelGGL(cddls_feature_seed_kernel, dim3(quad_grid(N * (F / 4))), dim3(CD_THREADS), 0, (hipStream_t)stream,
+                     g_head, c_row, act, out, N, F, slope);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int contrad_cddls_bn_relu_bwd_eval(const float* dy, const float* y, float* dx, long long M, int K, int ldy,
+                                              int ldx, const float* gamma, const float* running_var, float eps,
+                                              int perm_hw, contrad_stream_t stream) {
+  CONTRAD_ARG(dy && y && dx && gamma && running_var && M >= 1 && K >= 1 && ldy >= K && ldx >= K);
+  CONTRAD_ARG(perm_hw >= 1 && K % perm_hw == 0);
+  CONTRAD_ARG(perm_hw == 1 || (dx != dy && dx != y));          // the permuted form is not an in-place map
+  const int vec = perm_hw == 1 && (K & 3) == 0 && (ldy & 3) == 0 && (ldx & 3) == 0 && al16(dy) && al16(y) && al16(dx) &&
+                  al16(gamma) && al16(running_var);
+  const long long items = vec ? M * (K / 4) : M * K;
+  hipLaunchKernelGGL(cddls_bn_relu_bwd_eval_kernel, dim3(quad_grid(items)), dim3(CD_THREADS), 0, (hipStream_t)stream, dy,
+                     y, dx, M, K, ldy, ldx, gamma, running_var, eps, perm_hw, vec);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int contrad_cddls_compose(const float* gout, const float* z2, float* x, long long n, float eps, int clamp01,
+                                     contrad_stream_t stream) {
+  CONTRAD_ARG(gout && z2 && x && n >= 1);
+  hipLaunchKernelGGL(cddls_compose_kernel, dim3(quad_grid((n + 3) / 4)), dim3(CD_THREADS), 0, (hipStream_t)stream, gout,
+                     z2, x, n, eps, clamp01, (int)(al16(gout) && al16(z2) && al16(x)));
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int contrad_cddls_image_end(const float* gx, const float* gout, float* z2, float* g_lin, long long n,
+                                       float eps, float sigma_n, const float* noise, long long seed, const void* state,
+                                       contrad_stream_t stream) {
+  CONTRAD_ARG(gx && gout && z2 && g_lin && n >= 1 && eps >= 0.f);
+  const int vec = al16(gx) && al16(gout) && al16(z2) && al16(g_lin) && (noise == nullptr || al16(noise));
+  hipLaunchKernelGGL(cddls_image_end_kernel, dim3(quad_grid((n + 3) / 4)), dim3(CD_THREADS), 0, (hipStream_t)stream, gx,
+                     gout, z2, g_lin, n, eps, noise_scale_of(eps, sigma_n), noise, seed, static_cast<const int*>(state), vec);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int contrad_cddls_latent_update(float* z, const float* gz, long long n, float eps, float sigma_n,
+                                           const float* noise, long long seed, void* state, contrad_stream_t stream) {
+  CONTRAD_ARG(z && gz && n >= 1 && eps >= 0.f);
+  const int vec = al16(z) && al16(gz) && (noise == nullptr || al16(noise));
+  hipLaunchKernelGGL(cddls_latent_update_kernel, dim3(quad_grid((n + 3) / 4)), dim3(CD_THREADS), 0, (hipStream_t)stream,
+                     z, gz, n, eps, noise_scale_of(eps, sigma_n), noise, seed, static_cast<int*>(state), vec);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int contrad_cddls_energy(const float* d, int ldd, const float* feat, const float* c_row,
+                                    const float* bias_term, const float* z2, float* e, int N, int F, long long P,
+                                    contrad_stream_t stream) {
+  CONTRAD_ARG(d && feat && c_row && bias_term && z2 && e && N >= 1 && F >= 1 && P >= 1 && ldd >= 1);
+  hipLaunchKernelGGL(cddls_energy_kernel, dim3(N), dim3(CD_THREADS), 0, (hipStream_t)stream, d, ldd, feat, c_row,
+                     bias_term, z2, e, F, P);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}

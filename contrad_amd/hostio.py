@@ -106,3 +106,31 @@ class StepThrottle(object):
 
 
 THROTTLE = StepThrottle()
+
+
+# ---- image files (sample writers; no torchvision / PIL here) ----
+def to_uint8(x):
+    """Quantise [0, 1] floats as torchvision's ``save_image`` does: x * 255 + 0.5, clamped to [0, 255], truncated."""
+    return x.mul(255.0).add_(0.5).clamp_(0, 255).to(torch.uint8)
+
+
+def png_bytes(img):
+    """An 8-bit RGB PNG (one IDAT chunk, filter type 0 on every row) of a uint8 (H, W, 3) array."""
+    import struct
+    import zlib
+    import numpy as np
+    img = np.ascontiguousarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError('png_bytes: uint8 (H, W, 3) expected, got %s %s' % (img.dtype, img.shape))
+    h, w, _ = img.shape
+    raw = np.concatenate([np.zeros((h, 1), np.uint8), img.reshape(h, w * 3)], axis=1).tobytes()
+
+    def chunk(tag, data):
+        return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
+    return (b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0))
+            + chunk(b'IDAT', zlib.compress(raw, 6)) + chunk(b'IEND', b''))
+
+
+def write_png(path, img):
+    with open(path, 'wb') as f:
+        f.write(png_bytes(img))

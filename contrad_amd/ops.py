@@ -1145,3 +1145,119 @@ def linhead_wgrad_sgd(feats, dlogits, weight=None, bias=None, lr=None, grad_weig
         if bias is not None:
             torch.autograd.graph.increment_version(bias)
     return grad_weight, grad_bias
+
+
+# ---- cDDLS sampling (csrc/cddls.hip) ----
+def _flat_f32(t, name):
+    _chk(t, name)
+    if t is not None and not t.is_contiguous():
+        raise RuntimeError('contrad_hip: %s must be contiguous' % name)
+
+
+def _chk_state(state):
+    if state is not None and (state.dtype != torch.int32 or not state.is_cuda or state.numel() < 2
+                              or not state.is_contiguous()):
+        raise RuntimeError('contrad_hip: the step state must be contiguous CUDA int32 values, at least two: {step, arrival counter = 0}')
+
+
+def cddls_normal_fill(n, seed, stream_id, step=0, step_dev=None, device=None, want_words=False, out=None, grid_blocks=0):
+    """The generator's normals of (seed, stream, step) for elements 0 .. n - 1 -> (normals, raw 32-bit words as int32 or
+    None).  ``step_dev`` (int32 device tensor) overrides ``step``; ``grid_blocks`` forces the launch grid."""
+    _chk_state(step_dev)
+    if out is None:
+        out = torch.empty(n, device=device, dtype=torch.float32)
+    _flat_f32(out, 'out')
+    if out.numel() != n:
+        raise RuntimeError('contrad_hip: out must hold %d floats' % n)
+    words = torch.empty(n, device=out.device, dtype=torch.int32) if want_words else None
+    lib().call('contrad_cddls_normal_fill', _p(out), _p(words), ctypes.c_longlong(n), ctypes.c_longlong(int(seed)),
+               int(stream_id), _p(step_dev), int(step), int(grid_blocks), _stream())
+    return out, words
+
+
+def cddls_feature_seed(g_head, c_row, act, slope, out=None):
+    """(g_head + c_row) * lrelu'(act) over (N, F) rows; ``out`` may be ``g_head``."""
+    _flat_f32(g_head, 'g_head'); _flat_f32(c_row, 'c_row'); _flat_f32(act, 'act')
+    F = c_row.numel()
+    N = g_head.numel() // F
+    if g_head.numel() != N * F or act.numel() != N * F:
+        raise RuntimeError('contrad_hip: g_head and act must hold N x %d floats' % F)
+    if out is None:
+        out = torch.empty_like(g_head)
+    _flat_f32(out, 'out')
+    if out.numel() != N * F:
+        raise RuntimeError('contrad_hip: out must match g_head')
+    lib().call('contrad_cddls_feature_seed', _p(g_head), _p(c_row), _p(act), _p(out), ctypes.c_longlong(N), F,
+               float(slope), _stream())
+    return out
+
+
+def bn_relu_bwd_eval(dy2d, y2d, dx2d, gamma, running_var, eps=1e-5, perm_hw=1):
+    """Backward of the eval-mode bn_relu_apply(x2d -> y2d): ``dy2d`` in y's layout, ``dx2d`` in x's (may be dy2d when
+    perm_hw == 1)."""
+    _chk(dy2d, 'dy'); _chk(y2d, 'y'); _chk(dx2d, 'dx'); _chk(gamma, 'gamma'); _chk(running_var, 'running_var')
+    M, K = dx2d.shape
+    if tuple(dy2d.shape) != (M, K) or tuple(y2d.shape) != (M, K) or _ld(dy2d) != _ld(y2d):
+        raise RuntimeError('contrad_hip: dy and y must be (M, K) matrices sharing the leading dimension')
+    if gamma.numel() != K or running_var.numel() != K:
+        raise RuntimeError('contrad_hip: gamma and running_var must hold K floats')
+    lib().call('contrad_cddls_bn_relu_bwd_eval', _p(dy2d), _p(y2d), _p(dx2d), ctypes.c_longlong(M), K, _ld(y2d),
+               _ld(dx2d), _p(gamma), _p(running_var), float(eps), int(perm_hw), _stream())
+    return dx2d
+
+
+def cddls_compose(gout, z2, eps, out=None, clamp01=False):
+    """gout + eps * z2 (clamped to [0, 1] with ``clamp01``)."""
+    _flat_f32(gout, 'gout'); _flat_f32(z2, 'z2')
+    if out is None:
+        out = torch.empty_like(gout)
+    _flat_f32(out, 'out')
+    if z2.numel() != gout.numel() or out.numel() != gout.numel():
+        raise RuntimeError('contrad_hip: gout, z2 and out must have the same size')
+    lib().call('contrad_cddls_compose', _p(gout), _p(z2), _p(out), ctypes.c_longlong(gout.numel()), float(eps),
+               int(bool(clamp01)), _stream())
+    return out
+
+
+def cddls_image_end(gx, gout, z2, g_lin, eps, sigma_n, noise=None, seed=0, state=None):
+    """Writes ``g_lin`` (gradient at the generator's last pre-activation) and updates ``z2`` in place."""
+    for t, nm in ((gx, 'gx'), (gout, 'gout'), (z2, 'z2'), (g_lin, 'g_lin'), (noise, 'noise')):
+        _flat_f32(t, nm)
+        if t is not None and t.numel() != z2.numel():
+            raise RuntimeError('contrad_hip: %s must have the size of z2' % nm)
+    _chk_state(state)
+    if noise is None and state is None:
+        raise RuntimeError('contrad_hip: the generator needs the step state')
+    lib().call('contrad_cddls_image_end', _p(gx), _p(gout), _p(z2), _p(g_lin), ctypes.c_longlong(z2.numel()), float(eps),
+               float(sigma_n), _p(noise), ctypes.c_longlong(int(seed)), _p(state), _stream())
+    torch.autograd.graph.increment_version(z2)
+
+
+def cddls_latent_update(z, gz, eps, sigma_n, noise=None, seed=0, state=None):
+    """z <- clamp(z - eps / 2 * gz + sigma_n sqrt(eps) n, -1, 1) in place; advances ``state[0]``."""
+    for t, nm in ((z, 'z'), (gz, 'gz'), (noise, 'noise')):
+        _flat_f32(t, nm)
+        if t is not None and t.numel() != z.numel():
+            raise RuntimeError('contrad_hip: %s must have the size of z' % nm)
+    _chk_state(state)
+    if noise is None and state is None:
+        raise RuntimeError('contrad_hip: the generator needs the step state')
+    lib().call('contrad_cddls_latent_update', _p(z), _p(gz), ctypes.c_longlong(z.numel()), float(eps), float(sigma_n),
+               _p(noise), ctypes.c_longlong(int(seed)), _p(state), _stream())
+    torch.autograd.graph.increment_version(z)
+
+
+def cddls_energy(d, feat, c_row, bias_term, z2, out=None):
+    """Per-sample energy -> (N,): d (N, 1) logits, feat (N, F) in c_row's order, z2 (N, ...)."""
+    _chk(d, 'd'); _flat_f32(feat, 'feat'); _flat_f32(c_row, 'c_row'); _flat_f32(bias_term, 'bias_term'); _flat_f32(z2, 'z2')
+    N, F = d.shape[0], c_row.numel()
+    if feat.numel() != N * F or z2.numel() % N or z2.shape[0] != N:
+        raise RuntimeError('contrad_hip: feat must hold N x %d floats and z2 N samples' % F)
+    if out is None:
+        out = torch.empty(N, device=d.device, dtype=torch.float32)
+    _flat_f32(out, 'out')
+    if out.numel() != N:
+        raise RuntimeError('contrad_hip: out must hold N floats')
+    lib().call('contrad_cddls_energy', _p(d), d.stride(0) if N > 1 else 1, _p(feat), _p(c_row), _p(bias_term), _p(z2),
+               _p(out), N, F, ctypes.c_longlong(z2.numel() // N), _stream())
+    return out

@@ -589,6 +589,48 @@ int contrad_linhead_wgrad_sgd(const float* F, int ldf, const float* dlogits, int
                               const float* lr_dev, float* W, float* b, float* gradW, float* gradb,
                               contrad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * cDDLS sampling (csrc/cddls.hip): the streaming kernels of one class-conditional Langevin step in latent space
+ * (the reference's test_gan_sample_cddls.py:57-76) and its noise generator.  Flat tensors of n floats, any n; 16-byte
+ * accesses when every pointer is 16-byte aligned.  No allocation, no synchronisation.
+ *
+ * Noise: Philox4x32-10 keyed by the 64-bit seed, counter (element / 4, step, stream id, 0); the four words give the
+ * normals of elements 4q .. 4q + 3 by Box-Muller: radius sqrt(-2 ln u) from word 0 (2), angle 2 pi u from word 1 (3),
+ * u = ((word >> 8) + 0.5) 2^-24; elements 0, 2 take the cosine, 1, 3 the sine.  Stream ids: 0 the noise of z, 1 the
+ * noise of z2, 2 the initial z2.  state: two device ints {step, arrival counter (0 between launches)}.
+ * ---------------------------------------------------------------------------------------------- */
+/* out[n] (may be NULL) = the generator's normals, words[n] (may be NULL) = the raw 32-bit words they come from.  The
+ * step is step_dev[0] when step_dev != NULL, else `step`.  grid_blocks > 0 forces the grid (the draws do not depend on it). */
+int contrad_cddls_normal_fill(float* out, unsigned* words, long long n, long long seed, int stream_id,
+                              const void* step_dev, int step, int grid_blocks, contrad_stream_t stream);
+/* out[N,F] = (g_head[N,F] + c_row[F]) * (act[N,F] > 0 ? 1 : slope); F % 4 == 0, 16-byte aligned; out may be g_head. */
+int contrad_cddls_feature_seed(const float* g_head, const float* c_row, const float* act, float* out, long long N, int F,
+                               float slope, contrad_stream_t stream);
+/* Backward of contrad_bn_relu_apply in eval mode (running statistics are constants):
+ * dx[r,c] = dy[r,p(c)] * [y[r,p(c)] > 0] * gamma[c] / sqrt(running_var[c] + eps), with y / dy in the layout the apply
+ * kernel wrote (row stride ldy; perm_hw > 1: p(ch * perm_hw + hw) = hw * (K / perm_hw) + ch) and dx in x's (row stride
+ * ldx).  perm_hw == 1: dx may be dy. */
+int contrad_cddls_bn_relu_bwd_eval(const float* dy, const float* y, float* dx, long long M, int K, int ldy, int ldx,
+                                   const float* gamma, const float* running_var, float eps, int perm_hw,
+                                   contrad_stream_t stream);
+/* x = gout + eps * z2; clamp01 != 0: clamped to [0, 1] (the final images). */
+int contrad_cddls_compose(const float* gout, const float* z2, float* x, long long n, float eps, int clamp01,
+                          contrad_stream_t stream);
+/* gx = d(-(d + lbd l))/dx, gout = 0.5 tanh(.) + 0.5 the generator's output.  g_lin = gx * 0.5 (1 - t^2), t = 2 gout - 1;
+ * z2 <- z2 - eps / 2 * (eps * gx + z2) + sigma_n sqrt(eps) * n2 in place; n2 = noise[n] when noise != NULL, else stream 1
+ * of the generator at step state[0]. */
+int contrad_cddls_image_end(const float* gx, const float* gout, float* z2, float* g_lin, long long n, float eps,
+                            float sigma_n, const float* noise, long long seed, const void* state,
+                            contrad_stream_t stream);
+/* z <- clamp(z - eps / 2 * gz + sigma_n sqrt(eps) * n, -1, 1) in place (noise as above, stream 0), then state[0] += 1
+ * (state may be NULL with explicit noise). */
+int contrad_cddls_latent_update(float* z, const float* gz, long long n, float eps, float sigma_n, const float* noise,
+                                long long seed, void* state, contrad_stream_t stream);
+/* e[i] = -d[i * ldd] + <feat[i,:F], c_row> + bias_term[0] + 0.5 |z2[i,:P]|^2: the energy of sample i with
+ * c_row = -lbd * w_y (in feat's order) and bias_term = -lbd * b_y. */
+int contrad_cddls_energy(const float* d, int ldd, const float* feat, const float* c_row, const float* bias_term,
+                         const float* z2, float* e, int N, int F, long long P, contrad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
