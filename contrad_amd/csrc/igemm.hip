@@ -793,22 +793,27 @@ constexpr size_t smem_bytes(int mode) {
   return main_loop > epi ? main_loop : epi;
 }
 
-template <int MODE, int BM, int BN, bool VEC>
-int launch(const IgemmArgs& a, dim3 grid, hipStream_t stream) {
-  static bool attr_set_dev[64] = {};  // per device (one process may drive several); benign race: idempotent
-  const size_t smem = smem_bytes<BM, BN>(MODE);
+// Launch a kernel whose dynamic LDS can be above the 64 KiB default: the limit is raised once per device (one process may drive
+// several; benign race: idempotent), and a failure is returned and tried again by the next call.
+template <auto Kernel, class Args>
+int launch_large_lds(dim3 grid, int threads, size_t lds_bytes, hipStream_t stream, const Args& a) {
+  static bool attr_set_dev[64] = {};
   int dev_id = 0;
   (void)hipGetDevice(&dev_id);
   bool& attr_set = attr_set_dev[dev_id & 63];
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<MODE, BM, BN, VEC>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
-  hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, VEC>), grid, dim3(NTHREADS), smem, stream, a);
+  hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds_bytes, stream, a);
   CONTRAD_CHECK_LAUNCH();
   return 0;
+}
+
+template <int MODE, int BM, int BN, bool VEC>
+int launch(const IgemmArgs& a, dim3 grid, hipStream_t stream) {
+  return launch_large_lds<igemm_kernel<MODE, BM, BN, VEC>>(grid, NTHREADS, smem_bytes<BM, BN>(MODE), stream, a);
 }
 
 #include "igemm_lean.h"
@@ -819,448 +824,7 @@ int launch(const IgemmArgs& a, dim3 grid, hipStream_t stream) {
 #include "wino44.h"
 #include "wino44n.h"
 #include "wino23.h"
-
-// ---------------- Winograd F(2x2, 3x3) path (wino.h): 3x3 stride-1 pad-1 layers, forward and data gradient ----------------
-// Can the shape run on wino_kernel<mode> at all?  (input channels % 16, output channels % 64, power-of-two maps >= 4)
-bool wino_ok(const contrad_conv_desc* d, int mode) {
-  if (mode != MODE_FWD && mode != MODE_DGRAD) return false;
-  if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1) return false;
-  if (d->H < 4 || d->W < 4 || (d->H & (d->H - 1)) || (d->W & (d->W - 1))) return false;
-  const int cin = mode == MODE_FWD ? d->C : d->K, cout = mode == MODE_FWD ? d->K : d->C;
-  const int ldi = mode == MODE_FWD ? d->ldx : d->ldy, ldo = mode == MODE_FWD ? d->ldy : d->ldx;
-  if ((cin & 15) || (cout & 63) || (ldi & 3) || (d->ldw & 3)) return false;
-  const int th = std::min(8, d->H / 2), tw = std::min(8, d->W / 2);
-  const long long nimg = 64 / (th * tw);
-  if (nimg > 16) return false;
-  const long long lim = 1ll << 31;
-  if (nimg * d->H * d->W * std::max(ldi, ldo) * 4 >= lim) return false;     // block-relative byte offsets
-  if (16ll * cin * cout * 4 >= lim) return false;
-  return true;
-}
-
-wino::Args wino_args(const contrad_conv_desc* d, int mode) {
-  wino::Args a{};
-  a.N = d->N; a.H = d->H; a.W = d->W;
-  a.Cin = mode == MODE_FWD ? d->C : d->K;
-  a.Cout = mode == MODE_FWD ? d->K : d->C;
-  a.ldi = mode == MODE_FWD ? d->ldx : d->ldy;
-  a.ldo = mode == MODE_FWD ? d->ldy : d->ldx;
-  a.TH = std::min(8, d->H / 2); a.TW = std::min(8, d->W / 2);
-  a.sh_tw = __builtin_ctz(a.TW); a.sh_thw = __builtin_ctz(a.TH * a.TW);
-  a.NIMG = 64 / (a.TH * a.TW);
-  a.PH = d->H / (2 * a.TH); a.PW = d->W / (2 * a.TW);
-  a.NP = cdiv(d->N, a.NIMG) * a.PH * a.PW;
-  a.NKB = a.Cout / 64;
-  // raw box: with the halo (pixels outside the image load as zeros) when the image has several patches along the axis,
-  // else the image itself (the halo reads the zero pixel)
-  a.BH = a.PH > 1 ? 2 * a.TH + 2 : d->H; a.r_org = a.PH > 1 ? -1 : 0;
-  a.BW = a.PW > 1 ? 2 * a.TW + 2 : d->W; a.c_org = a.PW > 1 ? -1 : 0;
-  return a;
-}
-
-long long wino_items(const contrad_conv_desc* d, int mode) {
-  const wino::Args a = wino_args(d, mode);
-  return (long long)a.NP * a.NKB;
-}
-
-constexpr int WINO_CUS = 256;      // one persistent block per CU of the MI355X
-
-// The transformed filter U a Winograd family reads: its kind is the family's contrad_conv2d_path number (9 serves 11 too), and
-// its bytes are the workspace such a call needs (16 transform points per filter for F(2x2, 3x3), 36 for the others).
-enum { FILTER_WINO = 7, FILTER_WINO22 = 8, FILTER_WINO44 = 9, FILTER_WINO23 = 10 };
-long long filter_bytes(int kind, const contrad_conv_desc* d) {
-  return (kind == FILTER_WINO ? 16ll : 36ll) * d->C * d->K * (long long)sizeof(float);
-}
-bool wino44_planned(const contrad_conv_desc* d, int mode);     // (below: F(4x4, 3x3) goes first)
-
-// Does the plan send the layer there?  A block is a whole CU and an item (64 tiles x 64 couts x all channels) its unit of
-// work: the launch needs about a round of items, and the last round must not be mostly empty.
-bool wino_planned(const contrad_conv_desc* d, int mode) {
-  static const bool enabled = contrad_dev_on("CONTRAD_WINO");
-  if (!enabled || !wino_ok(d, mode)) return false;
-  if (wino44_planned(d, mode)) return false;       // (F(4x4, 3x3) takes the launch)
-  const long long items = wino_items(d, mode);
-  const long long rounds = cdivll(items, WINO_CUS);
-  static const long long min_items = contrad_dev_ll("CONTRAD_WINO_MIN_ITEMS", 150ll);
-  // (a single partial round: from 150 items.  Per-rank batches of the headline config on one GPU, profiles/r06_ab_plan_thresholds.txt:
-  // 200 / 150 / 90 items -> 3.12 / 2.82 / 2.89 ms per step at batch 64, 4.39 / 4.25 / 4.24 at batch 128)
-  if (items < WINO_CUS) return items >= min_items;
-  return rounds * WINO_CUS * 10 <= items * 14;
-}
-
-int wino_grid(const wino::Args& a) {
-  const int l0 = cdiv(a.NP, 8) * a.NKB;           // items of the fullest XCD
-  return 8 * std::min(WINO_CUS / 8, l0);
-}
-
-
-// ---------------- Winograd F(4x4, 3x3) path (wino44.h): the same layers as wino.h on maps of 8x8 and larger ----------------
-// (input channels % 32, output channels % 64 -- or an odd multiple of 32: wino44n.h --, power-of-two maps >= 8; 2.25 multiply-adds per
-// output instead of 4)
-bool wino44_ok(const contrad_conv_desc* d, int mode) {
-  if (mode != MODE_FWD && mode != MODE_DGRAD) return false;
-  if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1) return false;
-  // (4x4 maps: wino44n_kernel only -- a tile is an image, 32 images per item)
-  if (d->H < 4 || d->W < 4 || (d->H & (d->H - 1)) || (d->W & (d->W - 1)) || (d->W < 32 ? d->H != d->W : d->H < 16)) return false;
-  const int cin = mode == MODE_FWD ? d->C : d->K, cout = mode == MODE_FWD ? d->K : d->C;
-  const int ldi = mode == MODE_FWD ? d->ldx : d->ldy, ldo = mode == MODE_FWD ? d->ldy : d->ldx;
-  // (output channels: whole 64-wide blocks -- wino44_kernel -- or an odd number of 32-wide ones -- wino44n_kernel, wino44n.h)
-  if ((cin & 31) || (cout & 31) || (ldi & 3) || (d->ldw & 3)) return false;
-  const long long lim = 1ll << 31;
-  const long long nimg = d->W >= 32 ? 1 : d->W == 16 ? 2 : d->W == 8 ? 8 : 32;
-  if (nimg * d->H * d->W * std::max(ldi, ldo) * 4 >= lim) return false;     // block-relative byte offsets
-  if (36ll * cin * cout * 4 >= lim) return false;
-  return true;
-}
-
-// Does a launch of `items` whole-CU items fill the chip well enough?  A single round from 230 items, else a last round that is not
-// mostly empty (rounds x CUs <= 1.4 x items).
-static inline bool wino44_round_ok(long long items) {
-  static const long long min_items = contrad_dev_ll("CONTRAD_WINO44_MIN_ITEMS", 230ll);
-  if (items < WINO_CUS) return items >= min_items;
-  return cdivll(items, WINO_CUS) * WINO_CUS * 10 <= items * 14;
-}
-
-// patches (32 tiles each) of a launch: images / images per item x patches per image
-static inline long long wino44_patches(const contrad_conv_desc* d) {
-  const int TW = std::min(8, d->W / 4), TH = std::min(4, d->H / 4);
-  return (long long)cdiv(d->N, 32 / (TH * TW)) * (d->H / (4 * TH)) * (d->W / (4 * TW));
-}
-
-// wino44n_kernel (items of 32 tiles x 32 couts) instead of wino44_kernel (x 64): output channels that are not whole 64-wide blocks;
-// the 4x4 maps (1536 images x 512 couts: 768 items = three full rounds where 64-wide blocks give one and a half); and launches
-// whose 64-wide items do not fill the chip while twice as many half items do (192 images of 8 x 8 x 512: 192 -> 384 items, 0.30 ->
-// 0.24 ms; of 16 x 16 x 128: 0.095 -> 0.079 ms -- with enough items the 64-wide blocks are 10 - 25 % faster: one exchange and one
-// transform of V per 64 couts instead of per 32, profiles/r06_ab_wino44n_plan.txt)
-static inline bool wino44_n32(const contrad_conv_desc* d, int mode) {
-  static const bool all = contrad_dev_off_by_default("CONTRAD_WINO44N_ALL");      // (dev: every shape on it)
-  static const bool fill = contrad_dev_on("CONTRAD_WINO44N_FILL");  // (dev: the third rule off)
-  const int cout = mode == MODE_FWD ? d->K : d->C;
-  if ((cout & 63) != 0 || d->W == 4 || all) return true;
-  const long long items64 = wino44_patches(d) * (cout / 64);
-  return fill && !wino44_round_ok(items64) && wino44_round_ok(2 * items64);
-}
-
-wino44::Args wino44_args(const contrad_conv_desc* d, int mode) {
-  wino44::Args a{};
-  a.N = d->N; a.H = d->H; a.W = d->W;
-  a.Cin = mode == MODE_FWD ? d->C : d->K;
-  a.Cout = mode == MODE_FWD ? d->K : d->C;
-  a.ldi = mode == MODE_FWD ? d->ldx : d->ldy;
-  a.ldo = mode == MODE_FWD ? d->ldy : d->ldx;
-  a.TW = std::min(8, d->W / 4); a.TH = std::min(4, d->H / 4);      // 4x4-pixel tiles per image part of an item: 4 x 8, 4 x 4 (16x16 maps), 2 x 2 (8x8), 1 (4x4)
-  a.sh_tw = __builtin_ctz(a.TW); a.sh_thw = __builtin_ctz(a.TH * a.TW);
-  a.NIMG = 32 / (a.TH * a.TW);
-  a.PH = d->H / (4 * a.TH); a.PW = d->W / (4 * a.TW);
-  a.NP = cdiv(d->N, a.NIMG) * a.PH * a.PW;
-  a.n32 = wino44_n32(d, mode) ? 1 : 0;
-  a.NKB = a.n32 ? a.Cout / 32 : a.Cout / 64;      // 32-wide cout blocks: the items of wino44n_kernel
-  a.BH = 4 * a.TH + 2; a.BW = 4 * a.TW + 2;       // raw box: always with the halo
-  return a;
-}
-
-long long wino44_items(const contrad_conv_desc* d, int mode) {
-  const wino44::Args a = wino44_args(d, mode);
-  return (long long)a.NP * a.NKB;
-}
-
-// An item is 512 output pixels x 64 (32) couts x all channels on a whole CU: twice wino.h's.  The plan takes F(4x4, 3x3) when the
-// launch has a full round of them and its last round is not mostly empty; else the layer falls through to wino_planned.
-bool wino44_planned(const contrad_conv_desc* d, int mode) {
-  static const bool enabled = contrad_dev_on("CONTRAD_WINO44");
-  static const bool enabled2 = contrad_dev_on("CONTRAD_WINO");
-  if (!enabled || !enabled2 || !wino44_ok(d, mode)) return false;
-  static const bool enabled_n = contrad_dev_on("CONTRAD_WINO44N");
-  if (!enabled_n && wino44_n32(d, mode)) return false;       // (32-wide cout blocks: wino44n.h)
-  return wino44_round_ok(wino44_items(d, mode));
-}
-
-int wino44_grid(const wino44::Args& a) {
-  const int l0 = cdiv(a.NP, 8) * a.NKB;           // items of the fullest XCD
-  return 8 * std::min(WINO_CUS / 8, l0);
-}
-
-template <int MODE, int BOXW>
-int launch_wino44_inst(const wino44::Args& a, hipStream_t stream) {
-  static const hipError_t attr = hipFuncSetAttribute((const void*)wino44::wino44_kernel<MODE, BOXW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     wino44::LDS_DWORDS * 4);
-  if (attr != hipSuccess) return (int)attr;
-  hipLaunchKernelGGL((wino44::wino44_kernel<MODE, BOXW>), dim3(wino44_grid(a)), dim3(512), wino44::LDS_DWORDS * 4, stream, a);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
-}
-
-template <int MODE, int BOXW>
-int launch_wino44n_inst(const wino44::Args& a, hipStream_t stream) {
-  static const hipError_t attr = hipFuncSetAttribute((const void*)wino44n::wino44n_kernel<MODE, BOXW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     wino44::LDS_DWORDS * 4);
-  if (attr != hipSuccess) return (int)attr;
-  hipLaunchKernelGGL((wino44n::wino44n_kernel<MODE, BOXW>), dim3(wino44_grid(a)), dim3(512), wino44::LDS_DWORDS * 4, stream, a);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
-}
-
-template <int MODE>
-int launch_wino44(const contrad_conv_desc* d, const float* in, const float* wp, const float* bias, const float* ref,
-                  float* out, float slope, float gain, float* U, hipStream_t stream, const float* Uprep = nullptr) {
-  wino44::Args a = wino44_args(d, MODE);
-  a.x = in; a.U = Uprep ? Uprep : U; a.y = out; a.bias = bias; a.ref = ref; a.slope = slope; a.gain = gain;
-  const int quads = (a.Cin / 4) * a.Cout;
-  if (!Uprep) hipLaunchKernelGGL(wino44::wino44_filter_kernel<MODE>, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
-  CONTRAD_CHECK_LAUNCH();
-  if (a.n32)
-    return a.BW == 34 ? launch_wino44n_inst<MODE, 34>(a, stream) : a.BW == 18 ? launch_wino44n_inst<MODE, 18>(a, stream)
-           : a.BW == 10 ? launch_wino44n_inst<MODE, 10>(a, stream) : launch_wino44n_inst<MODE, 6>(a, stream);
-  return a.BW == 34 ? launch_wino44_inst<MODE, 34>(a, stream) : a.BW == 18 ? launch_wino44_inst<MODE, 18>(a, stream) : launch_wino44_inst<MODE, 10>(a, stream);
-}
-
-// ---------------- Winograd F(2x2, 2x2) path (wino22.h): 4x4 stride-2 pad-1 layers, forward and data gradient ----------------
-bool wino22_ok(const contrad_conv_desc* d, int mode) {
-  if (mode != MODE_FWD && mode != MODE_DGRAD) return false;
-  if (d->KH != 4 || d->KW != 4 || d->stride != 2 || d->pad != 1) return false;
-  if ((d->H & 1) || (d->W & 1) || d->Ho * 2 != d->H || d->Wo * 2 != d->W) return false;
-  auto grid_ok = [](int g) { return g == 4 || g == 8 || g == 16; };
-  if (!grid_ok(d->Ho) || !grid_ok(d->Wo)) return false;
-  const int cin = mode == MODE_FWD ? d->C : d->K, cout = mode == MODE_FWD ? d->K : d->C;
-  const int ldi = mode == MODE_FWD ? d->ldx : d->ldy;
-  if ((cin & (mode == MODE_FWD ? 7 : 15)) || (cout & 63) || (ldi & 3) || (d->ldw & 3)) return false;
-  const long long nimg = wino22::TB / ((d->Ho / 2) * (d->Wo / 2));
-  const long long lim = 1ll << 31;
-  if (nimg * d->H * d->W * std::max(d->ldx, d->ldy) * 4 >= lim) return false;
-  if (4ll * 9 * cin * cout * 4 >= lim) return false;
-  return true;
-}
-
-wino22::Args wino22_args(const contrad_conv_desc* d, int mode) {
-  wino22::Args a{};
-  const bool dg = mode == MODE_DGRAD;
-  a.N = d->N; a.dgrad = dg ? 1 : 0;
-  a.Hi = dg ? d->Ho : d->H; a.Wi = dg ? d->Wo : d->W;
-  a.Hout = dg ? d->H : d->Ho; a.Wout = dg ? d->W : d->Wo;
-  a.Cin = dg ? d->K : d->C; a.Cout = dg ? d->C : d->K;
-  a.ldi = dg ? d->ldy : d->ldx; a.ldo = dg ? d->ldx : d->ldy;
-  a.GH = d->Ho; a.GW = d->Wo;
-  const int tw = a.GW / 2, thw = (a.GH / 2) * tw;
-  a.sh_tw = __builtin_ctz(tw); a.sh_thw = __builtin_ctz(thw);
-  a.NIMG = wino22::TB / thw;
-  a.NTB = cdiv(d->N, a.NIMG);
-  a.NKB = a.Cout / 64;
-  return a;
-}
-
-long long wino22_items(const contrad_conv_desc* d, int mode) {
-  const wino22::Args a = wino22_args(d, mode);
-  return (long long)a.NTB * a.NKB * (mode == MODE_DGRAD ? 4 : 1);
-}
-
-bool wino22_planned(const contrad_conv_desc* d, int mode) {
-  static const bool enabled = contrad_dev_on("CONTRAD_WINO22");
-  if (!enabled || !wino22_ok(d, mode)) return false;
-  const long long items = wino22_items(d, mode);
-  const long long rounds = cdivll(items, WINO_CUS);
-  // (1.78x fewer multiply-adds, not 2.25x: a last round that is a quarter empty already loses to the direct kernels -- forward of
-  // 256 -> 512 channels at 1536 images, 384 items: 0.622 ms against 0.558, profiles/r06_ab_wino22_layers.txt)
-  static const long long min_items = contrad_dev_ll("CONTRAD_WINO22_MIN_ITEMS", 150ll);
-  if (items < WINO_CUS) return items >= min_items;
-  return rounds * WINO_CUS * 100 <= items * 125;
-}
-
-int wino22_grid(const wino22::Args& a) { return 8 * std::min(WINO_CUS / 8, cdiv(a.NTB, 8) * a.NKB * (a.dgrad ? 4 : 1)); }
-
-template <int MODE, int NRAW>
-int launch_wino22_inst(const wino22::Args& a, int blocks, hipStream_t stream) {
-  static const hipError_t attr = hipFuncSetAttribute((const void*)wino22::wino22_kernel<MODE, NRAW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     wino22::LDS_DWORDS * 4);
-  if (attr != hipSuccess) return (int)attr;
-  hipLaunchKernelGGL((wino22::wino22_kernel<MODE, NRAW>), dim3(blocks), dim3(512), wino22::LDS_DWORDS * 4, stream, a);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
-}
-
-template <int MODE>
-int launch_wino22(const contrad_conv_desc* d, const float* in, const float* wp, const float* bias, const float* ref,
-                  float* out, float slope, float gain, float* U, hipStream_t stream, const float* Uprep = nullptr) {
-  wino22::Args a = wino22_args(d, MODE);
-  a.x = in; a.U = Uprep ? Uprep : U; a.y = out; a.bias = bias; a.ref = ref; a.slope = slope; a.gain = gain;
-  const int quads = 4 * (a.Cin / 4) * a.Cout;
-  if (!Uprep) hipLaunchKernelGGL(wino22::wino22_filter_kernel<MODE>, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
-  CONTRAD_CHECK_LAUNCH();
-  const int blocks = wino22_grid(a);
-  const int items = 2 * a.NIMG * (a.GH + 1) * (a.GW + 1);      // raw box pieces per chunk (pixel x k-quad)
-  const int nraw = cdiv(items, 256);
-  if (nraw <= 5) return launch_wino22_inst<MODE, 5>(a, blocks, stream);
-  if (nraw == 6) return launch_wino22_inst<MODE, 6>(a, blocks, stream);
-  return launch_wino22_inst<MODE, 7>(a, blocks, stream);
-}
-
-// ---------------- F(2x2, 2x2) on the phases of the 3x3 stride-2 pad-0 layers (wino23.h): StyleGAN2's blurred conv2, forward ----------------
-// (input (2 Ho + 1) x (2 Wo + 1), power-of-two output grids >= 4, input channels % 16, output channels % 64; 25 of the dense
-// layer's 36 multiply-adds)
-bool wino23_ok(const contrad_conv_desc* d, int mode) {
-  if (mode != MODE_FWD) return false;
-  if (d->KH != 3 || d->KW != 3 || d->stride != 2 || d->pad != 0) return false;
-  if (d->H != 2 * d->Ho + 1 || d->W != 2 * d->Wo + 1) return false;
-  if (d->Ho < 4 || d->Wo < 4 || (d->Ho & (d->Ho - 1)) || (d->Wo & (d->Wo - 1))) return false;
-  if (d->Wo >= 32 ? d->Ho < 16 : d->Ho != d->Wo) return false;
-  if ((d->C & 15) || (d->K & 63) || (d->ldx & 3) || (d->ldw & 3)) return false;
-  const long long nimg = d->Wo >= 32 ? 1 : 128 / ((d->Ho / 2) * (d->Wo / 2));
-  const long long lim = 1ll << 31;
-  if (nimg * d->H * d->W * std::max(d->ldx, d->ldy) * 4 >= lim) return false;
-  if (4ll * 9 * d->C * d->K * 4 >= lim) return false;
-  return true;
-}
-
-wino23::Args wino23_args(const contrad_conv_desc* d) {
-  wino23::Args a{};
-  a.N = d->N; a.Hi = d->H; a.Wi = d->W; a.GH = d->Ho; a.GW = d->Wo;
-  a.Cin = d->C; a.Cout = d->K; a.ldi = d->ldx; a.ldo = d->ldy;
-  a.TW = d->Wo >= 32 ? 16 : d->Wo / 2; a.TH = d->Wo >= 32 ? 8 : d->Ho / 2;      // patches of 8 x 16 tiles, or whole images
-  a.sh_tw = __builtin_ctz(a.TW); a.sh_thw = __builtin_ctz(a.TH * a.TW);
-  a.NIMG = wino23::TB / (a.TH * a.TW);
-  a.PH = d->Ho / (2 * a.TH); a.PW = d->Wo / (2 * a.TW);
-  a.NP = cdiv(d->N, a.NIMG) * a.PH * a.PW;
-  a.NKB = a.Cout / 64;
-  return a;
-}
-
-bool wino23_planned(const contrad_conv_desc* d, int mode) {
-  static const bool enabled = contrad_dev_on("CONTRAD_WINO23");
-  if (!enabled || !wino23_ok(d, mode)) return false;
-  const wino23::Args a = wino23_args(d);
-  const long long items = (long long)a.NP * a.NKB;
-  if (items < WINO_CUS) return items >= 230;
-  return cdivll(items, WINO_CUS) * WINO_CUS * 10 <= items * 14;
-}
-
-int wino23_grid(const wino23::Args& a) { return 8 * std::min(WINO_CUS / 8, cdiv(a.NP, 8) * a.NKB); }
-
-template <int NRAW>
-int launch_wino23_inst(const wino23::Args& a, hipStream_t stream) {
-  static const hipError_t attr = hipFuncSetAttribute((const void*)wino23::wino23_kernel<NRAW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     wino23::LDS_DWORDS * 4);
-  if (attr != hipSuccess) return (int)attr;
-  hipLaunchKernelGGL((wino23::wino23_kernel<NRAW>), dim3(wino23_grid(a)), dim3(512), wino23::LDS_DWORDS * 4, stream, a);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
-}
-
-int launch_wino23(const contrad_conv_desc* d, const float* in, const float* wp, const float* bias, const float* ref,
-                  float* out, float slope, float gain, float* U, hipStream_t stream, const float* Uprep = nullptr) {
-  wino23::Args a = wino23_args(d);
-  a.x = in; a.U = Uprep ? Uprep : U; a.y = out; a.bias = bias; a.ref = ref; a.slope = slope; a.gain = gain;
-  const int quads = 4 * (a.Cin / 4) * a.Cout;
-  if (!Uprep) hipLaunchKernelGGL(wino23::wino23_filter_kernel, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
-  CONTRAD_CHECK_LAUNCH();
-  const int nraw = cdiv(2 * a.NIMG * (2 * a.TH + 1) * (2 * a.TW + 1), 256);
-  if (nraw <= 5) return launch_wino23_inst<5>(a, stream);
-  if (nraw == 6) return launch_wino23_inst<6>(a, stream);
-  return launch_wino23_inst<7>(a, stream);
-}
-
-// ---- weight gradient of the 4x4 stride-2 layers on F(2x2, 2x2) (wino22_wgrad_kernel) ----
-bool wino22_wgrad_ok(const contrad_conv_desc* d) {
-  if (d->KH != 4 || d->KW != 4 || d->stride != 2 || d->pad != 1) return false;
-  if (d->Ho * 2 != d->H || d->Wo * 2 != d->W) return false;
-  auto grid_ok = [](int g) { return g == 4 || g == 8 || g == 16; };
-  if (!grid_ok(d->Ho) || !grid_ok(d->Wo)) return false;
-  if ((d->C != 64 && (d->C & 127)) || (d->K & 63) || (d->ldx & 3) || (d->ldy & 3)) return false;
-  if (2ll * d->H * d->W * std::max(d->ldx, d->ldy) * 4 >= (1ll << 31)) return false;
-  return true;
-}
-
-wino22::WArgs wino22_wgrad_args(const contrad_conv_desc* d) {
-  wino22::WArgs a{};
-  a.N = d->N; a.H = d->H; a.W = d->W; a.C = d->C; a.K = d->K; a.ldx = d->ldx; a.ldy = d->ldy; a.GH = d->Ho; a.GW = d->Wo;
-  a.CTW = std::min(4, a.GW / 2);
-  a.CTH = std::min(8 / a.CTW, a.GH / 2);
-  a.CNIMG = 8 / (a.CTH * a.CTW);
-  a.sh_ctw = __builtin_ctz(a.CTW); a.sh_cthw = __builtin_ctz(a.CTH * a.CTW);
-  a.QH = a.GH / (2 * a.CTH); a.QW = a.GW / (2 * a.CTW);
-  a.Q = cdiv(d->N, a.CNIMG) * a.QH * a.QW;
-  a.RBN = 4 * d->C / 128; a.KB = d->K / 64;
-  a.CPB = std::min(d->C, 128); a.sh_cpb = __builtin_ctz(a.CPB);
-  const int splits = std::max(1, std::min(a.Q, WINO_CUS / (a.RBN * a.KB)));
-  a.qps = cdiv(a.Q, splits);
-  return a;
-}
-int wino22_wgrad_splits(const wino22::WArgs& a) { return cdiv(a.Q, a.qps); }
-int wino22_wgrad_grid(const wino22::WArgs& a) { return a.RBN * a.KB * wino22_wgrad_splits(a); }
-
-bool wino22_wgrad_planned(const contrad_conv_desc* d) {
-  static const bool enabled = contrad_dev_on("CONTRAD_WINO22_WGRAD");
-  static const bool enabled2 = contrad_dev_on("CONTRAD_WINO22");
-  if (!enabled || !enabled2 || !wino22_wgrad_ok(d)) return false;
-  const wino22::WArgs a = wino22_wgrad_args(d);
-  const long long blocks = wino22_wgrad_grid(a);
-  static const int min_qps = contrad_dev_int("CONTRAD_WINO_MIN_QPS", 16);
-  return a.qps >= min_qps && blocks * 10 >= WINO_CUS * 7 && blocks <= WINO_CUS;
-}
-
-long long wino22_wgrad_workspace_bytes(const contrad_conv_desc* d) {
-  const wino22::WArgs a = wino22_wgrad_args(d);
-  return (long long)wino22_wgrad_splits(a) * (16ll * d->C + 1) * d->K * (long long)sizeof(float);
-}
-
-// ---- weight gradient on the Winograd kernel (wino_wgrad_kernel): C % 64, K % 64 ----
-bool wino_wgrad_ok(const contrad_conv_desc* d) {
-  if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1) return false;
-  if (d->H < 4 || d->W < 4 || (d->H & (d->H - 1)) || (d->W & (d->W - 1))) return false;
-  if ((d->C & 63) || (d->K & 63) || (d->ldx & 3) || (d->ldy & 3)) return false;
-  const long long lim = 1ll << 31;
-  if (2ll * d->H * d->W * std::max(d->ldx, d->ldy) * 4 >= lim) return false;     // chunk-relative byte offsets (<= 2 images)
-  return true;
-}
-
-wino::WArgs wino_wgrad_args(const contrad_conv_desc* d) {
-  wino::WArgs a{};
-  a.N = d->N; a.H = d->H; a.W = d->W; a.C = d->C; a.K = d->K; a.ldx = d->ldx; a.ldy = d->ldy;
-  a.CTW = std::min(4, d->W / 2);
-  a.CTH = std::min(8 / a.CTW, d->H / 2);
-  a.CNIMG = 8 / (a.CTH * a.CTW);
-  a.sh_ctw = __builtin_ctz(a.CTW); a.sh_cthw = __builtin_ctz(a.CTH * a.CTW);
-  a.QH = d->H / (2 * a.CTH); a.QW = d->W / (2 * a.CTW);
-  a.Q = cdiv(d->N, a.CNIMG) * a.QH * a.QW;
-  a.CB = d->C / 64; a.KB = d->K / 64;
-  const int splits = std::max(1, std::min(a.Q, WINO_CUS / (a.CB * a.KB)));
-  a.qps = cdiv(a.Q, splits);
-  a.BH = a.QH > 1 ? 2 * a.CTH + 2 : d->H; a.r_org = a.QH > 1 ? -1 : 0;
-  a.BW = a.QW > 1 ? 2 * a.CTW + 2 : d->W; a.c_org = a.QW > 1 ? -1 : 0;
-  return a;
-}
-int wino_wgrad_splits(const wino::WArgs& a) { return cdiv(a.Q, a.qps); }
-int wino_wgrad_grid(const wino::WArgs& a) { return a.CB * a.KB * wino_wgrad_splits(a); }
-
-// planned when every block gets a contraction long enough to pay for its prologue and its 4x4 -> 3x3 epilogue
-bool wino_wgrad_planned(const contrad_conv_desc* d) {
-  static const bool enabled = contrad_dev_on("CONTRAD_WINO_WGRAD");
-  static const bool enabled2 = contrad_dev_on("CONTRAD_WINO");
-  if (!enabled || !enabled2 || !wino_wgrad_ok(d)) return false;
-  const wino::WArgs a = wino_wgrad_args(d);
-  const long long blocks = wino_wgrad_grid(a);
-  static const int min_qps = contrad_dev_int("CONTRAD_WINO_MIN_QPS", 16);
-  return a.qps >= min_qps && blocks * 10 >= WINO_CUS * 7 && blocks <= WINO_CUS;
-}
-
-long long wino_wgrad_workspace_bytes(const contrad_conv_desc* d) {
-  const wino::WArgs a = wino_wgrad_args(d);
-  return (long long)wino_wgrad_splits(a) * (9ll * d->C + 1) * d->K * (long long)sizeof(float);
-}
-
-template <int MODE>
-int launch_wino(const contrad_conv_desc* d, const float* in, const float* wp, const float* bias, const float* ref,
-                float* out, float slope, float gain, float* U, hipStream_t stream, const float* Uprep = nullptr) {
-  static const hipError_t attr = hipFuncSetAttribute((const void*)wino::wino_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     wino::LDS_DWORDS * 4);
-  if (attr != hipSuccess) return (int)attr;
-  wino::Args a = wino_args(d, MODE);
-  a.x = in; a.U = Uprep ? Uprep : U; a.y = out; a.bias = bias; a.ref = ref; a.slope = slope; a.gain = gain;
-  const int quads = (a.Cin / 4) * a.Cout;
-  if (!Uprep) hipLaunchKernelGGL(wino::wino_filter_kernel<MODE>, dim3(cdiv(quads, 256)), dim3(256), 0, stream, wp, U, d->C, d->K, d->ldw);
-  CONTRAD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(wino::wino_kernel<MODE>, dim3(wino_grid(a)), dim3(512), wino::LDS_DWORDS * 4, stream, a);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
-}
+#include "wino_host.h"
 
 // ---------------- every transformed filter of a network in one launch (contrad_conv2d_filter_prep) ----------------
 // Block b serves the job j with block_start[j] <= b < block_start[j + 1]; its threads do what the threads of the job's own
@@ -1282,40 +846,11 @@ __global__ __launch_bounds__(256) void filter_prep_kernel(const contrad_filter_b
   }
 }
 
-// threads of a job's transform (one per four input channels x one output channel [x phase]); 0 = unknown kind / mode
-long long filter_threads(int kind, int mode, int C, int K) {
-  if (mode != MODE_FWD && mode != MODE_DGRAD) return 0;
-  const long long quads = (long long)((mode == MODE_FWD ? C : K) / 4) * (mode == MODE_FWD ? K : C);
-  if (kind == FILTER_WINO || kind == FILTER_WINO44) return quads;
-  if (kind == FILTER_WINO22) return 4 * quads;
-  if (kind == FILTER_WINO23) return mode == MODE_FWD ? 4 * quads : 0;
-  return 0;
-}
-
-// Was `u` made for the path this call is about to take?  (host check: kind, mode, shape and the weight it was made from)
-inline bool filter_fits(const contrad_filter_job* u, int kind, int mode, const contrad_conv_desc* d, const float* wp) {
-  return u && u->U && u->kind == kind && u->mode == mode && u->C == d->C && u->K == d->K && u->ldw == d->ldw && u->wp == wp &&
-         ((uintptr_t)u->U & 15) == 0;
-}
-
 template <int MODE, int BM, int BN, bool BAL>
 int launch_lean_inst(const IgemmArgs& a, dim3 grid, hipStream_t stream) {
-  static bool attr_set_dev[64] = {};  // per device (one process may drive several); benign race: idempotent
-  constexpr size_t smem = lean_smem_bytes<MODE, BM, BN>();
-  int dev_id = 0;
-  (void)hipGetDevice(&dev_id);
-  bool& attr_set = attr_set_dev[dev_id & 63];
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_lean_kernel<MODE, BM, BN, BAL>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   IgemmArgs b = a;
   b.ny = (int)grid.y;
-  hipLaunchKernelGGL((igemm_lean_kernel<MODE, BM, BN, BAL>), dim3(grid.x * grid.y), dim3(NTHREADS), smem, stream, b);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
+  return launch_large_lds<igemm_lean_kernel<MODE, BM, BN, BAL>>(dim3(grid.x * grid.y), NTHREADS, lean_smem_bytes<MODE, BM, BN>(), stream, b);
 }
 
 template <int MODE, int BM, int BN>
@@ -2030,34 +1565,6 @@ int launch_wgrad_reduce(const float* ws, float* dwp, int Kg, int K, int ldw, int
   return 0;
 }
 
-int launch_wino22_wgrad(const contrad_conv_desc* d, const float* x, const float* gy, float* dwp, float* dbias,
-                        float* workspace, hipStream_t stream) {
-  static const hipError_t attr = hipFuncSetAttribute((const void*)wino22::wino22_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     wino22::W_LDS_DWORDS * 4);
-  if (attr != hipSuccess) return (int)attr;
-  wino22::WArgs a = wino22_wgrad_args(d);
-  const int splits = wino22_wgrad_splits(a);
-  a.x = x; a.gy = gy; a.ws = workspace;
-  a.bias_ws = dbias ? workspace + (size_t)splits * 16 * d->C * d->K : nullptr;
-  hipLaunchKernelGGL(wino22::wino22_wgrad_kernel, dim3(wino22_wgrad_grid(a)), dim3(512), wino22::W_LDS_DWORDS * 4, stream, a);
-  CONTRAD_CHECK_LAUNCH();
-  return launch_wgrad_reduce(workspace, dwp, 16 * d->C, d->K, d->ldw, splits, a.bias_ws, dbias, stream);
-}
-
-int launch_wino_wgrad(const contrad_conv_desc* d, const float* x, const float* gy, float* dwp, float* dbias,
-                      float* workspace, hipStream_t stream) {
-  static const hipError_t attr = hipFuncSetAttribute((const void*)wino::wino_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     wino::W_LDS_DWORDS * 4);
-  if (attr != hipSuccess) return (int)attr;
-  wino::WArgs a = wino_wgrad_args(d);
-  const int splits = wino_wgrad_splits(a);
-  a.x = x; a.gy = gy; a.ws = workspace;
-  a.bias_ws = dbias ? workspace + (size_t)splits * 9 * d->C * d->K : nullptr;
-  hipLaunchKernelGGL(wino::wino_wgrad_kernel, dim3(wino_wgrad_grid(a)), dim3(512), wino::W_LDS_DWORDS * 4, stream, a);
-  CONTRAD_CHECK_LAUNCH();
-  return launch_wgrad_reduce(workspace, dwp, 9 * d->C, d->K, d->ldw, splits, a.bias_ws, dbias, stream);
-}
-
 // The Winograd launch of filter kind `kind`, forward or data gradient.  U is the workspace, filled here by the family's filter
 // kernel, or the caller's prepared filter `u` when that was made for exactly this call (filter_fits).
 template <int MODE>
@@ -2065,11 +1572,9 @@ int launch_wino_kind(int kind, const contrad_conv_desc* d, const float* in, cons
                      float* out, float slope, float gain, float* workspace, const contrad_filter_job* u, hipStream_t stream) {
   CONTRAD_ARG(aligned16(in, wp, workspace));
   const float* U = filter_fits(u, kind, MODE, d, wp) ? u->U : nullptr;
-  if (kind == FILTER_WINO44) return launch_wino44<MODE>(d, in, wp, bias, ref, out, slope, gain, workspace, stream, U);
-  if (kind == FILTER_WINO) return launch_wino<MODE>(d, in, wp, bias, ref, out, slope, gain, workspace, stream, U);
-  if (kind == FILTER_WINO22) return launch_wino22<MODE>(d, in, wp, bias, ref, out, slope, gain, workspace, stream, U);
-  if (kind == FILTER_WINO23 && MODE == MODE_FWD) return launch_wino23(d, in, wp, bias, ref, out, slope, gain, workspace, stream, U);
-  return -22;
+  const WinoFamily* f = wino_family(kind);
+  CONTRAD_ARG(f && f->launch[MODE]);
+  return f->launch[MODE](d, in, wp, bias, ref, out, slope, gain, workspace, stream, U);
 }
 
 // ---------------- the route: which kernel family serves (d, mode), with what workspace and what igemm plan ----------------
@@ -2079,6 +1584,9 @@ enum Family {
   FAM_WGRAD_C32 = 4, FAM_FWD_K1 = 5, FAM_CONV_C32 = 6,
   FAM_WINO = 7, FAM_WINO22 = 8, FAM_WINO44 = 9, FAM_WINO23 = 10, FAM_WINO44N = 11
 };
+
+// the table row of a route's family (FAM_WINO44N: the 32-wide blocks of kind 9), nullptr for the other families
+inline const WinoFamily* wino_family_of(int family) { return wino_family(family == FAM_WINO44N ? FILTER_WINO44 : family); }
 
 struct Route {
   int family;                   // Family
@@ -2118,8 +1626,8 @@ Route igemm_route(const contrad_conv_desc* d, int mode, bool may_split) {
 Route conv_route(const contrad_conv_desc* d, int mode, bool has_workspace, long long workspace_bytes = 1ll << 62) {
   Route r{};
   if (mode == MODE_WGRAD) {
-    if (wino_wgrad_planned(d)) { r.family = FAM_WINO; r.workspace_bytes = wino_wgrad_workspace_bytes(d); return r; }
-    if (wino22_wgrad_planned(d)) { r.family = FAM_WINO22; r.workspace_bytes = wino22_wgrad_workspace_bytes(d); return r; }
+    if (wgrad_planned<WinoWgrad>(d)) { r.family = FAM_WINO; r.workspace_bytes = wgrad_workspace_bytes<WinoWgrad>(d); return r; }
+    if (wgrad_planned<Wino22Wgrad>(d)) { r.family = FAM_WINO22; r.workspace_bytes = wgrad_workspace_bytes<Wino22Wgrad>(d); return r; }
     if (wgrad_c32_ok(d)) {      // one partial per block, summed like split-K slabs
       r.family = FAM_WGRAD_C32;
       r.workspace_bytes = (long long)wgrad_c32_blocks(d) * ((long long)d->KH * d->KW * d->C + 1) * d->K * (long long)sizeof(float);
@@ -2127,10 +1635,9 @@ Route conv_route(const contrad_conv_desc* d, int mode, bool has_workspace, long 
     }
     return igemm_route(d, mode, true);
   }
-  if (wino44_planned(d, mode)) { r.family = wino44_n32(d, mode) ? FAM_WINO44N : FAM_WINO44; r.filter_kind = FILTER_WINO44; }
-  else if (wino_planned(d, mode)) r.family = r.filter_kind = FILTER_WINO;
-  else if (wino22_planned(d, mode)) r.family = r.filter_kind = FILTER_WINO22;
-  else if (wino23_planned(d, mode)) r.family = r.filter_kind = FILTER_WINO23;      // (forward only: wino23_ok)
+  for (const WinoFamily& f : WINO_FAMILIES)      // (the first family that plans the layer takes it)
+    if (f.planned(d, mode)) { r.family = r.filter_kind = f.kind; break; }
+  if (r.filter_kind == FILTER_WINO44 && Wino44::n32(d, mode)) r.family = FAM_WINO44N;
   long long filter_need = 0;
   if (r.filter_kind) {
     r.workspace_bytes = filter_need = filter_bytes(r.filter_kind, d);
@@ -2279,9 +1786,8 @@ extern "C" int contrad_conv2d_fwd_add_u(const contrad_conv_desc* d, const float*
   // (alignment is an argument error above, so the dispatch is exactly the route: what contrad_conv2d_path / _grid_blocks report)
   const Route r = conv_route(d, MODE_FWD, workspace != nullptr, workspace_bytes);
   hipStream_t s = (hipStream_t)stream;
+  if (r.filter_kind) return launch_wino_kind<MODE_FWD>(r.filter_kind, d, x, wp, bias, addend, y, slope, gain, workspace, u, s);
   switch (r.family) {
-    case FAM_WINO: case FAM_WINO22: case FAM_WINO44: case FAM_WINO23: case FAM_WINO44N:
-      return launch_wino_kind<MODE_FWD>(r.filter_kind, d, x, wp, bias, addend, y, slope, gain, workspace, u, s);
     case FAM_CONV_C32:
       return launch_conv_c32<MODE_FWD>(d, x, wp, y, bias, addend, nullptr, slope, gain, s);
     case FAM_FWD_K1:
@@ -2337,9 +1843,9 @@ extern "C" int contrad_conv2d_dgrad_ws_u(const contrad_conv_desc* d, const float
   if (vec_ok(d, MODE_DGRAD)) CONTRAD_ARG(aligned16(gy, wp, dx) && aligned16(act_ref, nullptr, nullptr));
   const Route r = conv_route(d, MODE_DGRAD, workspace != nullptr, workspace_bytes);
   hipStream_t s = (hipStream_t)stream;
+  // (Winograd: the filter mirrored; wino22: one item per dx phase)
+  if (r.filter_kind) return launch_wino_kind<MODE_DGRAD>(r.filter_kind, d, gy, wp, nullptr, act_ref, dx, slope, gain, workspace, u, s);
   switch (r.family) {
-    case FAM_WINO: case FAM_WINO22: case FAM_WINO44: case FAM_WINO44N:      // the filter mirrored; wino22: one item per dx phase
-      return launch_wino_kind<MODE_DGRAD>(r.filter_kind, d, gy, wp, nullptr, act_ref, dx, slope, gain, workspace, u, s);
     case FAM_CONV_C32:      // the same weight-stationary kernel with the filter mirrored
       return launch_conv_c32<MODE_DGRAD>(d, gy, wp, dx, nullptr, nullptr, act_ref, slope, gain, s);
     default: break;      // the igemm engine
@@ -2405,13 +1911,15 @@ extern "C" int contrad_conv2d_filter_prep(const contrad_filter_batch* b, contrad
   return 0;
 }
 
-extern "C" int contrad_conv2d_wino_ok(const contrad_conv_desc* d, int mode) {
-  if (check_desc(d)) return -22;
-  if (mode == MODE_WGRAD) return (wino_wgrad_ok(d) || wino22_wgrad_ok(d)) ? 1 : 0;
-  return (wino_ok(d, mode) || wino22_ok(d, mode) || wino23_ok(d, mode)) ? 1 : 0;
+namespace {
+// the family contrad_conv2d_wino forces for (d, mode): the one whose shapes these are (F(4x4, 3x3) shares F(2x2, 3x3)'s and has
+// its own entry point, contrad_conv2d_wino44); 0 exactly when contrad_conv2d_wino_ok says 0
+int forced_wino_kind(const contrad_conv_desc* d, int mode) {
+  for (const WinoFamily& f : WINO_FAMILIES)
+    if (f.kind != FILTER_WINO44 && f.ok(d, mode)) return f.kind;
+  return 0;
 }
 
-namespace {
 // The forced Winograd entry points: kind from the family's *_ok, the caller's checks, no prepared filter.
 int launch_wino_forced(int kind, const contrad_conv_desc* d, int mode, const float* in, const float* wp, const float* bias,
                        const float* ref, float* out, float slope, float gain, float* workspace, long long workspace_bytes,
@@ -2420,16 +1928,18 @@ int launch_wino_forced(int kind, const contrad_conv_desc* d, int mode, const flo
   if (mode == MODE_FWD) return launch_wino_kind<MODE_FWD>(kind, d, in, wp, bias, ref, out, slope, gain, workspace, nullptr, stream);
   return launch_wino_kind<MODE_DGRAD>(kind, d, in, wp, nullptr, ref, out, slope, gain, workspace, nullptr, stream);
 }
-
-// the family contrad_conv2d_wino forces for (d, mode): 0 exactly when contrad_conv2d_wino_ok says 0
-int forced_wino_kind(const contrad_conv_desc* d, int mode) {
-  return wino22_ok(d, mode) ? FILTER_WINO22 : wino23_ok(d, mode) ? FILTER_WINO23 : wino_ok(d, mode) ? FILTER_WINO : 0;
-}
 }  // namespace
+
+extern "C" int contrad_conv2d_wino_ok(const contrad_conv_desc* d, int mode) {
+  if (check_desc(d)) return -22;
+  if (mode == MODE_WGRAD) return (WinoWgrad::ok(d) || Wino22Wgrad::ok(d)) ? 1 : 0;
+  return forced_wino_kind(d, mode) ? 1 : 0;
+}
 
 extern "C" long long contrad_conv2d_wino_workspace_bytes(const contrad_conv_desc* d, int mode) {
   if (check_desc(d) || mode < 0 || mode > 2) return -22;
-  if (mode == MODE_WGRAD) return wino_wgrad_ok(d) ? wino_wgrad_workspace_bytes(d) : wino22_wgrad_ok(d) ? wino22_wgrad_workspace_bytes(d) : -22;
+  if (mode == MODE_WGRAD)
+    return WinoWgrad::ok(d) ? wgrad_workspace_bytes<WinoWgrad>(d) : Wino22Wgrad::ok(d) ? wgrad_workspace_bytes<Wino22Wgrad>(d) : -22;
   const int kind = forced_wino_kind(d, mode);
   return kind ? filter_bytes(kind, d) : -22;
 }
@@ -2440,12 +1950,12 @@ extern "C" int contrad_conv2d_wino_wgrad(const contrad_conv_desc* d, const float
   int rc = check_desc(d);
   if (rc) return rc;
   CONTRAD_ARG(x && gy && dwp && workspace && aligned16(x, gy, workspace));
-  if (wino22_wgrad_ok(d)) {
-    CONTRAD_ARG(workspace_bytes >= wino22_wgrad_workspace_bytes(d));
-    return launch_wino22_wgrad(d, x, gy, dwp, dbias, workspace, (hipStream_t)stream);
+  if (Wino22Wgrad::ok(d)) {
+    CONTRAD_ARG(workspace_bytes >= wgrad_workspace_bytes<Wino22Wgrad>(d));
+    return launch_wgrad<Wino22Wgrad>(d, x, gy, dwp, dbias, workspace, (hipStream_t)stream);
   }
-  CONTRAD_ARG(wino_wgrad_ok(d) && workspace_bytes >= wino_wgrad_workspace_bytes(d));
-  return launch_wino_wgrad(d, x, gy, dwp, dbias, workspace, (hipStream_t)stream);
+  CONTRAD_ARG(WinoWgrad::ok(d) && workspace_bytes >= wgrad_workspace_bytes<WinoWgrad>(d));
+  return launch_wgrad<WinoWgrad>(d, x, gy, dwp, dbias, workspace, (hipStream_t)stream);
 }
 
 // 4x4 stride 2: F(2x2, 2x2) on the phases (wino22.h); 3x3 stride 2 pad 0, forward only: the same with the zero planes skipped
@@ -2462,12 +1972,12 @@ extern "C" int contrad_conv2d_wino(const contrad_conv_desc* d, int mode, const f
 
 extern "C" int contrad_conv2d_wino44_ok(const contrad_conv_desc* d, int mode) {
   if (check_desc(d)) return -22;
-  return wino44_ok(d, mode) ? 1 : 0;
+  return Wino44::ok(d, mode) ? 1 : 0;
 }
 
 extern "C" long long contrad_conv2d_wino44_workspace_bytes(const contrad_conv_desc* d) {
   if (check_desc(d)) return -22;
-  if (!wino44_ok(d, MODE_FWD) && !wino44_ok(d, MODE_DGRAD)) return -22;     // (neither mode runs: no workspace to size)
+  if (!Wino44::ok(d, MODE_FWD) && !Wino44::ok(d, MODE_DGRAD)) return -22;     // (neither mode runs: no workspace to size)
   return filter_bytes(FILTER_WINO44, d);
 }
 
@@ -2478,7 +1988,7 @@ extern "C" int contrad_conv2d_wino44(const contrad_conv_desc* d, int mode, const
   if (rc) return rc;
   CONTRAD_ARG(in && wp && out && workspace && (mode == MODE_FWD || mode == MODE_DGRAD));
   CONTRAD_ARG(aligned16(ref, nullptr, nullptr));
-  return launch_wino_forced(wino44_ok(d, mode) ? FILTER_WINO44 : 0, d, mode, in, wp, bias, ref, out, slope, gain, workspace,
+  return launch_wino_forced(Wino44::ok(d, mode) ? FILTER_WINO44 : 0, d, mode, in, wp, bias, ref, out, slope, gain, workspace,
                             workspace_bytes, (hipStream_t)stream);
 }
 
@@ -2499,26 +2009,19 @@ extern "C" int contrad_conv2d_path(const contrad_conv_desc* d, int mode) {
 
 extern "C" double contrad_conv2d_executed_fraction(const contrad_conv_desc* d, int mode) {
   if (check_desc(d) || mode < 0 || mode > 2) return -22.0;
-  switch (conv_route(d, mode, true).family) {
-    case FAM_WINO44: case FAM_WINO44N: return 0.25;      // 36 transform-domain multiply-adds per 4x4 tile instead of 144
-    case FAM_WINO: return 4.0 / 9.0;                     // 16 transform-domain multiply-adds per 2x2 tile instead of 36
-    case FAM_WINO22: return 9.0 / 16.0;                  // four phases x 9 per 2x2 tile instead of 64
-    case FAM_WINO23: return 25.0 / 36.0;                 // 9 + 6 + 6 + 4 planes of the four phases per 2x2 tile instead of 36
-    case FAM_LEAN_SKIP: return mode == MODE_DGRAD ? dgrad_valid_tap_fraction(d) : fwd_valid_tap_fraction(d);
-    default: return 1.0;
-  }
+  const int family = conv_route(d, mode, true).family;
+  if (const WinoFamily* f = wino_family_of(family)) return f->executed;      // (the weight gradients' too: the same transforms)
+  if (family == FAM_LEAN_SKIP) return mode == MODE_DGRAD ? dgrad_valid_tap_fraction(d) : fwd_valid_tap_fraction(d);
+  return 1.0;
 }
 
 extern "C" long long contrad_conv2d_grid_blocks(const contrad_conv_desc* d, int mode, int with_workspace) {
   if (check_desc(d) || mode < 0 || mode > 2) return -22;
   const Route r = conv_route(d, mode, with_workspace != 0);
-  switch (r.family) {      // the special families: their own grid helpers (Winograd: 512 threads each)
-    case FAM_WINO:
-      return mode == MODE_WGRAD ? wino_wgrad_grid(wino_wgrad_args(d)) : wino_grid(wino_args(d, mode));
-    case FAM_WINO22:
-      return mode == MODE_WGRAD ? wino22_wgrad_grid(wino22_wgrad_args(d)) : wino22_grid(wino22_args(d, mode));
-    case FAM_WINO44: case FAM_WINO44N: return wino44_grid(wino44_args(d, mode));
-    case FAM_WINO23: return wino23_grid(wino23_args(d));
+  if (mode == MODE_WGRAD && r.family == FAM_WINO) return wgrad_grid<WinoWgrad>(WinoWgrad::args(d));
+  if (mode == MODE_WGRAD && r.family == FAM_WINO22) return wgrad_grid<Wino22Wgrad>(Wino22Wgrad::args(d));
+  if (const WinoFamily* f = wino_family_of(r.family)) return f->grid(d, mode);
+  switch (r.family) {      // the other special families: their own grid helpers
     case FAM_WGRAD_C32: return wgrad_c32_blocks(d);
     case FAM_CONV_C32: return conv_c32_blocks(d);
     case FAM_FWD_K1: return cdivll((long long)d->N * d->Ho * d->Wo, 4);
@@ -2562,8 +2065,8 @@ extern "C" int contrad_conv2d_wgrad(const contrad_conv_desc* d, const float* x, 
   hipStream_t s = (hipStream_t)stream;
   const int Kg = d->KH * d->KW * d->C;
   switch (r.family) {
-    case FAM_WINO: return launch_wino_wgrad(d, x, gy, dwp, dbias, workspace, s);        // wino.h, F(3x3, 2x2)
-    case FAM_WINO22: return launch_wino22_wgrad(d, x, gy, dwp, dbias, workspace, s);    // wino22.h
+    case FAM_WINO: return launch_wgrad<WinoWgrad>(d, x, gy, dwp, dbias, workspace, s);        // wino.h, F(3x3, 2x2)
+    case FAM_WINO22: return launch_wgrad<Wino22Wgrad>(d, x, gy, dwp, dbias, workspace, s);    // wino22.h
     case FAM_WGRAD_C32: {   // (C = K = 32: vec_ok holds, so the operands were checked for 16-byte alignment above)
       // accumulator-stationary kernel for the 32 -> 32 channel 3x3 layers (wgrad_c32.h): one partial per block, summed
       // by the same fixed-order reduce as the split-K slabs

@@ -4,7 +4,7 @@ layers and the shape grid of tests/test_conv_plan_cpu.py, from the public plan q
     python tools/plan_table.py OUT.tsv            # the library contrad_amd loads (CONTRAD_HIP_LIB=<path> for another build)
 
 Two builds plan alike exactly when their tables are the same bytes; the last line printed is `rows sha256 library`.  Behind
-profiles/conv_route_identity.txt (dev-library switches such as CONTRAD_WINO=0 go into the environment of the call).
+profiles/conv_route_identity.txt and profiles/wino_host_identity.txt (dev-library switches such as CONTRAD_WINO=0 go into the environment of the call).
 """
 import ctypes
 import hashlib
@@ -18,7 +18,8 @@ sys.path.insert(0, ROOT)
 from contrad_amd import _lib  # noqa: E402
 
 COLUMNS = ('N H W C ldx Ho Wo K ldy KH KW stride pad ldw mode path bm bn workspace_bytes grid_ws grid_nows '
-           'executed_fraction filter_kind filter_bytes order_len order_hash').split()
+           'executed_fraction filter_kind filter_bytes order_len order_hash '
+           'wino_ok wino_workspace_bytes wino44_ok wino44_workspace_bytes').split()
 _WS = ('contrad_conv2d_fwd_workspace_bytes', 'contrad_conv2d_dgrad_workspace_bytes', 'contrad_conv2d_wgrad_workspace_bytes')
 
 
@@ -33,6 +34,9 @@ def rows(L):
     path, tile, grid = L.raw('contrad_conv2d_path'), L.raw('contrad_conv2d_tile'), L.raw('contrad_conv2d_grid_blocks')
     frac, kind, order = (L.raw('contrad_conv2d_executed_fraction'), L.raw('contrad_conv2d_filter_kind'),
                          L.raw('contrad_conv2d_tile_order'))
+    # the forced entry points' own queries (they answer for shapes the plan sends elsewhere, too)
+    wok, wws, w44ok, w44ws = (L.raw('contrad_conv2d_wino_ok'), L.raw('contrad_conv2d_wino_workspace_bytes'),
+                              L.raw('contrad_conv2d_wino44_ok'), L.raw('contrad_conv2d_wino44_workspace_bytes'))
     buf = (ctypes.c_ubyte * 256)()
     for d in _plan_cases():
         p = ctypes.byref(d)
@@ -47,7 +51,7 @@ def rows(L):
             oh = hashlib.sha256(bytes(buf[:n])).hexdigest()[:16] if n > 0 else '-'
             yield [getattr(d, f) for f, _ in d._fields_] + [
                 mode, P, bm.value, bn.value, L.raw(_WS[mode])(p), grid(p, mode, 1), grid(p, mode, 0),
-                repr(frac(p, mode)), fk, nb.value, n, oh]
+                repr(frac(p, mode)), fk, nb.value, n, oh, wok(p, mode), wws(p, mode), w44ok(p, mode), w44ws(p)]
 
 
 def main(out):
