@@ -5,6 +5,11 @@ The reference composes ~25 PyTorch ops per call (two grid_samples, HSV round tri
 parameters are drawn on the HOST in the reference's exact RNG order (numpy global RNG for geometry / op order /
 blur sigma, torch CPU generator for masks and colour factors -- SURVEY.md 8a row A7), shipped as one small
 (B, 16) tensor, and a single fused HIP kernel does crop+flip+jitter+gray (plus a separable blur for *_hq).
+
+The augmentations of the baseline training modes follow the same split -- ``sample()`` on the host in the reference's draw
+order, ``apply()`` on the device, an autograd Function when the input requires grad: ``none``, ``hflip`` / ``hfrt``
+(augment/spatial.py:14-40,70-93: an index map and its adjoint gather) and ``diffaug`` (third_party/diffaug.py: one fused
+launch per direction on CIFAR-sized images); kernels in csrc/baseline_aug.hip, DESIGN.md section 12.
 """
 import math
 
@@ -16,7 +21,8 @@ from .. import ops
 from ..hostio import upload
 from ..config import configurable, get_bindings
 
-__all__ = ['get_augment', 'SimCLRAugment', 'simclr', 'simclr_hq', 'simclr_hq_cutout']
+__all__ = ['get_augment', 'SimCLRAugment', 'simclr', 'simclr_hq', 'simclr_hq_cutout', 'NoAugment', 'HorizontalFlipLayer',
+           'HorizontalFlipRandomCrop', 'DiffAugLayer', 'diffaug']
 
 
 def _jitter_range(value, center=1.0, clip_first_on_zero=True):
@@ -209,10 +215,177 @@ def simclr_hq_cutout():
                          cutout_length=get_bindings('CutOut')['length'], **_kwargs_from_bindings())
 
 
+class NoAugment(nn.Module):
+    """augment/__init__.py:31-37: the identity (``--aug=none``)."""
+
+    def forward(self, input):
+        return input
+
+
+class _HfrtFn(torch.autograd.Function):
+    """Flip + integer-shift index map with reflection; the backward is its adjoint gather (csrc/baseline_aug.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, Pd, max_pixels):
+        ctx.save_for_backward(Pd)
+        ctx.max_pixels = max_pixels
+        return ops.hfrt(x, Pd, max_pixels)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        Pd, = ctx.saved_tensors
+        return ops.hfrt(g.contiguous(), Pd, ctx.max_pixels, adjoint=True), None, None
+
+
+class _FlipShift(nn.Module):
+    """What hfrt and hflip share: the device part of a flip + whole-pixel shift (ops.hfrt) with ``self.max_pixels``;
+    subclasses draw the parameter rows (``sample``) and say which image sizes they take (``check_size``)."""
+
+    max_pixels = 0
+
+    def check_size(self, H, W):
+        raise NotImplementedError
+
+    def apply(self, inputs, P):
+        """Deterministic device part."""
+        self.check_size(inputs.shape[2], inputs.shape[3])
+        Pd = upload(P, inputs.device)
+        if inputs.requires_grad and torch.is_grad_enabled():
+            return _HfrtFn.apply(inputs.contiguous().float(), Pd, self.max_pixels)
+        return ops.hfrt(inputs.detach().contiguous().float(), Pd, self.max_pixels)
+
+    def forward(self, input):
+        if not input.is_cuda:
+            raise RuntimeError('contrad_amd augmentation runs on the MI355X HIP path only (no CPU fallback)')
+        return self.apply(input, self.sample(input.shape[0]))
+
+
+class HorizontalFlipRandomCrop(_FlipShift):
+    """augment/spatial.py:14-40 (``--aug=hfrt``): random horizontal flip and a shift by whole pixels in [-max_pixels,
+    max_pixels] on both axes, nearest-neighbour sampling with reflection padding.  The reference's normalised shift
+    k / (width / 2) is exactly k pixels when the images are width x width, so the layer is an index map; other sizes and
+    padding modes are refused."""
+
+    def __init__(self, max_pixels=None, width=None, padding_mode=None):
+        super().__init__()
+        b = get_bindings('HorizontalFlipRandomCrop') if None in (max_pixels, width, padding_mode) else {}
+        self.max_pixels = int(b['max_pixels'] if max_pixels is None else max_pixels)
+        self.width = int(b['width'] if width is None else width)
+        self.padding_mode = b['padding_mode'] if padding_mode is None else padding_mode
+        if self.padding_mode != 'reflection':
+            raise NotImplementedError("HorizontalFlipRandomCrop: padding_mode '%s' (only 'reflection', the reference's "
+                                      "configured value, is an index map)" % self.padding_mode)
+        if not 0 <= self.max_pixels < self.width:
+            raise ValueError('HorizontalFlipRandomCrop: max_pixels must be in [0, width)')
+
+    def sample(self, B):
+        """(B, HFRT_NPARAM) CPU block {sign, kx, ky, 0} from the torch CPU generator in the reference's order: the flip
+        signs, then the (B, 2) shifts, column 0 = x (spatial.py:30-32)."""
+        P = torch.zeros(B, ops.HFRT_NPARAM)
+        P[:, 0] = torch.bernoulli(torch.ones(B) * 0.5) * 2 - 1
+        P[:, 1:3] = torch.randint(-self.max_pixels, self.max_pixels + 1, (B, 2)).float()
+        return P
+
+    def check_size(self, H, W):
+        if H != self.width or W != self.width:
+            raise RuntimeError('HorizontalFlipRandomCrop(width=%d) got %dx%d images: the shifts are whole pixels only '
+                               'on width x width images' % (self.width, H, W))
+
+
+class HorizontalFlipLayer(_FlipShift):
+    """augment/spatial.py:70-93 (``--aug=hflip``): the flip alone -- the same kernel with max_pixels = 0.  Draws the flip
+    signs only."""
+
+    def sample(self, B):
+        P = torch.zeros(B, ops.HFRT_NPARAM)
+        P[:, 0] = torch.bernoulli(torch.ones(B) * 0.5) * 2 - 1
+        return P
+
+    def check_size(self, H, W):
+        if H != W:
+            raise RuntimeError('HorizontalFlipLayer: square images (the hfrt kernel with max_pixels = 0)')
+
+
+class _DiffAugFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, Pd, bits):
+        ctx.save_for_backward(Pd)
+        ctx.bits = bits
+        return ops.diffaug(x, Pd, bits)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        Pd, = ctx.saved_tensors
+        return ops.diffaug(g.contiguous(), Pd, ctx.bits, backward=True), None, None
+
+
+class DiffAugLayer(nn.Module):
+    """augment/__init__.py:136-142 + third_party/diffaug.py: DiffAugment with a policy out of color, translation, cutout
+    (in this order), forward and backward in one fused launch each on CIFAR-sized images."""
+
+    def __init__(self, policy=""):
+        super().__init__()
+        self.policy = policy
+        self.bits = ops.diffaug_policy_bits(policy) if policy else 0
+
+    def sample(self, B, dim2, dim3):
+        """(B, DIFFAUG_NPARAM) CPU block {b, s, c, tx, ty, ox, oy, 0} from the torch CPU generator in the reference's order
+        (diffaug.py:24-60): three float32 rand(B,1,1,1) for the colour stage, randint tx, ty, randint ox, oy; stages
+        outside the policy draw nothing."""
+        P = torch.zeros(B, ops.DIFFAUG_NPARAM)
+        if self.bits & 1:
+            P[:, 0] = (torch.rand(B, 1, 1, 1) - 0.5).view(B)
+            P[:, 1] = (torch.rand(B, 1, 1, 1) * 2).view(B)
+            P[:, 2] = (torch.rand(B, 1, 1, 1) + 0.5).view(B)
+        if self.bits & 2:
+            sx, sy = int(dim2 * 0.125 + 0.5), int(dim3 * 0.125 + 0.5)
+            P[:, 3] = torch.randint(-sx, sx + 1, size=[B, 1, 1]).view(B).float()
+            P[:, 4] = torch.randint(-sy, sy + 1, size=[B, 1, 1]).view(B).float()
+        if self.bits & 4:
+            cx, cy = int(dim2 * 0.5 + 0.5), int(dim3 * 0.5 + 0.5)
+            P[:, 5] = torch.randint(0, dim2 + (1 - cx % 2), size=[B, 1, 1]).view(B).float()
+            P[:, 6] = torch.randint(0, dim3 + (1 - cy % 2), size=[B, 1, 1]).view(B).float()
+        return P
+
+    def apply(self, inputs, P):
+        """Deterministic device part."""
+        if not self.bits:
+            return inputs
+        Pd = upload(P, inputs.device)
+        if inputs.requires_grad and torch.is_grad_enabled():
+            return _DiffAugFn.apply(inputs.contiguous().float(), Pd, self.bits)
+        return ops.diffaug(inputs.detach().contiguous().float(), Pd, self.bits)
+
+    def forward(self, inputs):
+        if not self.bits:                     # DiffAugment(policy=''): the identity
+            return inputs
+        if not inputs.is_cuda:
+            raise RuntimeError('contrad_amd augmentation runs on the MI355X HIP path only (no CPU fallback)')
+        B, _, d2, d3 = inputs.shape
+        return self.apply(inputs, self.sample(B, d2, d3))
+
+
+def diffaug(policy='color,cutout'):
+    return DiffAugLayer(policy=policy)                   # augment/__init__.py:144-145: the factory's policy is color,cutout
+
+
 @configurable('augment')
-def get_augment(mode='none', **kwargs):
-    """Same entry point as augment.get_augment (augment/__init__.py:13-28) for the modes on the hot path."""
-    mapping = {'simclr': simclr, 'simclr_hq': simclr_hq, 'simclr_hq_cutout': simclr_hq_cutout}
+def get_augment(mode='none', diffaug_policy=None, **kwargs):
+    """Same entry point as augment.get_augment (augment/__init__.py:13-28): the SimCLR pipelines of the ContraD hot path and
+    the augmentations of the baseline modes (none, hflip, hfrt, diffaug).
+
+    ``diffaug`` is switched on by the configuration: it needs the binding ``augment.diffaug_policy`` (configs/gan/diffaug/
+    c10_diffaug.gin sets the reference's ``"color,cutout"``); without it the mode raises, as every mode outside the
+    configured path does."""
+    mapping = {'simclr': simclr, 'simclr_hq': simclr_hq, 'simclr_hq_cutout': simclr_hq_cutout, 'none': NoAugment,
+               'hflip': HorizontalFlipLayer, 'hfrt': HorizontalFlipRandomCrop}
+    if mode == 'diffaug':
+        if diffaug_policy is None:
+            raise NotImplementedError("augmentation mode 'diffaug' needs the gin binding augment.diffaug_policy "
+                                      "(configs/gan/diffaug/c10_diffaug.gin binds \"color,cutout\")")
+        return diffaug(diffaug_policy)
     if mode not in mapping:
-        raise NotImplementedError("augmentation mode '%s' is outside the ContraD hot path (SURVEY.md 2 row 6)" % mode)
+        raise NotImplementedError("augmentation mode '%s' is not implemented on this path (SURVEY.md 2 row 6)" % mode)
     return mapping[mode]()

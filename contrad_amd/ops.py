@@ -1261,3 +1261,89 @@ def cddls_energy(d, feat, c_row, bias_term, z2, out=None):
     lib().call('contrad_cddls_energy', _p(d), d.stride(0) if N > 1 else 1, _p(feat), _p(c_row), _p(bias_term), _p(z2),
                _p(out), N, F, ctypes.c_longlong(z2.numel() // N), _stream())
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# baseline training modes (csrc/baseline_aug.hip): hfrt / hflip, DiffAugment, consistency, (2N,1) GAN loss
+# --------------------------------------------------------------------------------------------------
+HFRT_NPARAM = 4
+DIFFAUG_NPARAM = 8
+DIFFAUG_STAGES = ('color', 'translation', 'cutout')       # policy bits 1, 2, 4: the order they are applied in
+
+
+def diffaug_policy_bits(policy):
+    """'color,cutout' -> 5.  Stages must come in the order the kernel applies them (the reference's factory order)."""
+    names = [p for p in policy.split(',') if p] if isinstance(policy, str) else list(policy)
+    idx = [DIFFAUG_STAGES.index(p) if p in DIFFAUG_STAGES else -1 for p in names]
+    if not idx or -1 in idx or idx != sorted(set(idx)):
+        raise NotImplementedError("DiffAugment policy '%s': a non-empty subset of %s in this order"
+                                  % (policy, ','.join(DIFFAUG_STAGES)))
+    return sum(1 << i for i in idx)
+
+
+def _chk_images_params(x, params, nparam, name):
+    _chk(x, 'x'); _chk(params, 'params')
+    if x.dim() != 4 or not x.is_contiguous() or tuple(params.shape) != (x.shape[0], nparam) or not params.is_contiguous() \
+            or params.device != x.device:
+        raise RuntimeError('contrad_hip: %s needs contiguous NCHW input and (B,%d) params on its device' % (name, nparam))
+
+
+def hfrt(x, params, max_pixels, adjoint=False, out=None):
+    """HorizontalFlipRandomCrop as an index map (adjoint=True: its transpose on a gradient).  x NCHW (B,C,W,W), params
+    (B, HFRT_NPARAM) = {sign, kx, ky, -} on the same device."""
+    _chk_images_params(x, params, HFRT_NPARAM, 'hfrt')
+    B, C, H, W = x.shape
+    if H != W or not 0 <= int(max_pixels) < W:
+        raise RuntimeError('contrad_hip: hfrt needs square images and max_pixels < width (got %dx%d, %d)' % (H, W, max_pixels))
+    if out is None:
+        out = torch.empty_like(x)
+    _chk_out(out, x, 'hfrt')
+    lib().call('contrad_hfrt', _p(x), _p(out), _p(params), B, C, H, W, int(max_pixels), int(bool(adjoint)), _stream())
+    return out
+
+
+def diffaug(x, params, policy_bits, backward=False, out=None):
+    """DiffAugment forward (backward=True: d loss / d x from x = d loss / d y).  x NCHW (B,3,H,W), params (B, DIFFAUG_NPARAM)
+    = {b, s, c, tx, ty, ox, oy, -} on the same device."""
+    _chk_images_params(x, params, DIFFAUG_NPARAM, 'diffaug')
+    B, C, H, W = x.shape
+    if C != 3:
+        raise RuntimeError('contrad_hip: diffaug is defined for RGB images')
+    if not 0 < int(policy_bits) < 8:
+        raise RuntimeError('contrad_hip: diffaug policy bits must be in 1..7')
+    if out is None:
+        out = torch.empty_like(x)
+    _chk_out(out, x, 'diffaug')
+    nbytes = lib().raw('contrad_diffaug_workspace_bytes')(B, H, W)
+    if nbytes < 0:
+        raise RuntimeError('contrad_hip: diffaug: unsupported image size %dx%d' % (H, W))
+    ws = _workspace(nbytes, x.device)
+    lib().call('contrad_diffaug', _p(x), _p(out), _p(params), B, H, W, int(policy_bits), int(bool(backward)), _p(ws),
+               ctypes.c_longlong(ws.numel() * 4), _stream())
+    return out
+
+
+def consistency(a, b, n0, n1, lbd0, lbd1):
+    """lbd0 mean_{[0,n0)} (a-b)^2 + lbd1 mean_{[n0,n0+n1)} (a-b)^2 on logit columns a, b (n0+n1, 1) -> (out (1,), grad_a, grad_b)."""
+    _chk(a, 'a'); _chk(b, 'b')
+    n = int(n0) + int(n1)
+    if a.dim() != 2 or b.dim() != 2 or a.shape != (n, 1) or b.shape != (n, 1) or n0 <= 0 or n1 < 0 or a.device != b.device:
+        raise RuntimeError('contrad_hip: consistency needs two (%d, 1) logit columns on one device' % n)
+    out = torch.empty(1, device=a.device, dtype=torch.float32)
+    ga = torch.empty((n, 1), device=a.device, dtype=torch.float32)
+    gb = torch.empty((n, 1), device=a.device, dtype=torch.float32)
+    lib().call('contrad_consistency', _p(a), max(a.stride(0), 1), _p(b), max(b.stride(0), 1), int(n0), int(n1), float(lbd0),
+               float(lbd1), _p(out), _p(ga), _p(gb), _stream())
+    return out, ga, gb
+
+
+def gan_d_loss_2n(logits, N, kind):
+    """logits (2N,1), reals first -> (out3 = [loss, mean d_real, mean d_gen], grad (2N,1))."""
+    _chk(logits, 'logits')
+    if logits.dim() != 2 or tuple(logits.shape) != (2 * N, 1):
+        raise RuntimeError('contrad_hip: gan_d_loss_2n needs (2N, 1) logits')
+    out = torch.empty(3, device=logits.device, dtype=torch.float32)
+    grad = torch.empty((2 * N, 1), device=logits.device, dtype=torch.float32)
+    lib().call('contrad_gan_d_loss_2n', _p(logits), max(logits.stride(0), 1), N, GAN_LOSS_KINDS[kind], _p(out), _p(grad),
+               _stream())
+    return out, grad

@@ -24,7 +24,7 @@ from .engine import GradAllReducer, GraphedDStep, GraphedGStep, OverlappedGradRe
 from .hostio import THROTTLE
 from .models.gan import get_architecture
 from .optim import FusedAdam
-from .training.gan import setup
+from .training.gan import BASELINE_MODES, setup
 
 IMAGE_SIZES = {'cifar10': (32, 32, 3), 'cifar100': (32, 32, 3), 'cifar10_hflip': (32, 32, 3)}
 
@@ -33,9 +33,11 @@ def parse_args(argv=None):
     parser = ArgumentParser(description='Training script: ContraD on MI355X (one process per GPU).')
     parser.add_argument('gin_config', type=str, help='Path to the gin configuration file')
     parser.add_argument('architecture', type=str, help='Architecture')
-    parser.add_argument('--mode', default='std', type=str, help='Training mode (only contrad is on this path)')
-    parser.add_argument('--penalty', default='none', type=str)
-    parser.add_argument('--aug', default='none', type=str, help='Augmentation (simclr | simclr_hq)')
+    parser.add_argument('--mode', default='std', type=str, help='Training mode (contrad | simclr_only | std | aug | aug_both)')
+    parser.add_argument('--penalty', default='none', type=str, help='none | cr | bcr (std / aug / aug_both)')
+    parser.add_argument('--aug', default='none', type=str, help='Augmentation (simclr | simclr_hq | simclr_hq_cutout | none | hflip | hfrt | diffaug; diffaug needs a gin '
+                             'file that binds augment.diffaug_policy = "color,cutout", as configs/gan/diffaug/c10_diffaug.gin '
+                             'does: with any other file it raises NotImplementedError until the line is added)')
     parser.add_argument('--use_warmup', action='store_true', help='Use warmup strategy on LR')
     parser.add_argument('--temp', default=0.1, type=float)
     parser.add_argument('--lbd_a', default=1.0, type=float)
@@ -203,6 +205,10 @@ def main(argv=None):
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
+    if world > 1 and P.mode in BASELINE_MODES:
+        raise NotImplementedError("--mode=%s runs on one GPU (WORLD_SIZE=%d): the gradient exchange inside D's backward assumes "
+                                  "one discriminator call per step, and the baseline modes (%s) with cr / bcr make two"
+                                  % (P.mode, world, ', '.join(BASELINE_MODES)))
     torch.cuda.set_device(local_rank)
     dev = torch.device('cuda', local_rank)
     if world > 1:

@@ -449,6 +449,48 @@ int contrad_gaussian_blur_masked_bwd(const float* grad_out, float* tmp, float* g
                                      contrad_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Baseline training modes (csrc/baseline_aug.hip): the augmentations of `--aug=hfrt|hflip|diffaug`, the consistency
+ * penalties of `--penalty=cr|bcr` and the GAN term of training/gan/{std,aug,aug_both}.py.  Images are NCHW fp32
+ * contiguous, x != y.  No float atomics: every sum has a fixed order; the backward passes are gathers over pre-images.
+ * ---------------------------------------------------------------------------------------------- */
+/* HorizontalFlipRandomCrop (augment/spatial.py:14-40; HorizontalFlipLayer :70-93 = max_pixels 0): nearest-neighbour
+ * sampling of a flip + integer-shift affine grid with reflection padding, i.e. the index map
+ *   y[n,c,i,j] = x[n,c,refl(i + ky), refl((sign > 0 ? j : W-1-j) + kx)],  refl(t) = t < 0 ? -t-1 : (t >= n ? 2n-1-t : t).
+ * params[B][CONTRAD_HFRT_NPARAM] = {flip sign (+1 / -1), kx, ky, unused}, kx and ky integers in [-max_pixels, max_pixels].
+ * Needs H == W (the reference's shifts are whole pixels only then) and max_pixels < W; -22 otherwise.
+ * adjoint != 0: x is d loss / d y, y becomes d loss / d x; every input pixel sums the at most 2 x 2 outputs that read it,
+ * rows outer and columns inner, each axis in the order direct, reflected below 0, reflected past n-1. */
+#define CONTRAD_HFRT_NPARAM 4
+int contrad_hfrt(const float* x, float* y, const float* params, int B, int C, int H, int W, int max_pixels,
+                 int adjoint, contrad_stream_t stream);
+/* DiffAugment (third_party/diffaug.py) on RGB images, `policy` = bit 1 color | bit 2 translation | bit 4 cutout, applied
+ * in this order (the order of the reference's factory, augment/__init__.py:144-145).
+ * params[B][CONTRAD_DIFFAUG_NPARAM] = {b, s, c, tx, ty, ox, oy, unused}: b = rand - 0.5 (brightness), s = 2 rand
+ * (saturation), c = rand + 0.5 (contrast); tx, ty integer shifts along H, W in [-int(H/8 + .5), int(H/8 + .5)] (W likewise);
+ * ox, oy the cutout offsets along H, W.  Entries of stages outside the policy are not read.
+ *   u = 2x - 1;  u1 = u + b;  u2 = (u1 - p) s + p, p = mean over the channels of u1;  u3 = (u2 - M) c + M,
+ *   M = mean_chw(u2) = mean_chw(u) + b (saturation keeps each pixel's channel mean): ONE per-sample mean of the input;
+ *   translation: output (i, j) reads (i + tx, j + ty), 0 outside;  cutout: rows clamp(ox - ch/2 + [0, ch), 0, H-1) x columns
+ *   likewise are set to 0, ch = int(H/2 + .5);  y = 0.5 u4 + 0.5 (cut and shifted-out pixels are exactly 0.5).
+ * backward != 0: x is d loss / d y and y becomes d loss / d x = 2 gu1, with g3 = 0.5 g masked and un-translated,
+ *   gu2 = c g3 + (1 - c) mean_chw(g3), gu1 = s gu2 + (1 - s) mean_c(gu2) (without bit 1: g3 itself).
+ * Images of at most 16 KiB (3 x H x W floats; CIFAR) run in one workgroup per image from LDS; larger ones take a
+ * partial-sum launch and an apply launch with the workspace of the query. */
+#define CONTRAD_DIFFAUG_NPARAM 8
+long long contrad_diffaug_workspace_bytes(int B, int H, int W);
+int contrad_diffaug(const float* x, float* y, const float* params, int B, int H, int W, int policy, int backward,
+                    float* workspace, long long workspace_bytes, contrad_stream_t stream);
+/* Consistency term (penalty.py:45-58) of two logit vectors a, b (element strides lda, ldb):
+ * out1[0] = lbd0 mean_{i < n0} (a_i - b_i)^2 + lbd1 mean_{n0 <= i < n0 + n1} (a_i - b_i)^2, grad_a / grad_b [n0 + n1] dense
+ * = d out / d a, d out / d b.  CR: n1 = 0; bCR: the reals and the fakes of the (2N,1) layout with their two weights. */
+int contrad_consistency(const float* a, int lda, const float* b, int ldb, int n0, int n1, float lbd0, float lbd1,
+                        float* out1, float* grad_a, float* grad_b, contrad_stream_t stream);
+/* contrad_gan_d_loss for the (2N,1) layout of training/gan/{std,aug,aug_both}.py: reals logits[0, N), fakes [N, 2N);
+ * kinds and out3 as there, grad[2N]. */
+int contrad_gan_d_loss_2n(const float* logits, int ld, int N, int kind, float* out3, float* grad,
+                          contrad_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The reference's two native ops (models/gan/stylegan2/op/), same tensor contracts.
  * ---------------------------------------------------------------------------------------------- */
 /* upfirdn2d_op.upfirdn2d (op/upfirdn2d.cpp:12-23): input [major,in_h,in_w,minor] -> out [major,out_h,out_w,minor],
