@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .captured import EagerFirst, capture
 from .hostio import THROTTLE, to_uint8, write_png
 from .models.gan.sndcgan import _D_CONVS, _SLOPE, _flat_views
 
@@ -91,7 +92,7 @@ class CDDLSSampler(object):
         self.G, self.D, self.n, self.dev = G, D, int(n), dev
         self.lbd, self.eps, self.sigma_n, self.seed = float(lbd), float(eps), float(sigma_n), int(seed)
         self.use_graph, self.want_energy = bool(graph), bool(energy)
-        self.graph, self.seen, self._scratch = None, 0, {}
+        self.graph, self.first, self._scratch = None, EagerFirst(), {}
         self.hb, self.wb = D.s_hb, D.s_wb
         self.feat, self.dh = 512 * self.hb * self.wb, D.d_hidden
         self.weight, self.bias = weight.detach(), bias.detach()
@@ -267,17 +268,11 @@ class CDDLSSampler(object):
         (eager only)."""
         if self.cls is None:
             raise RuntimeError('set_class() first')
-        explicit = noise is not None or noise2 is not None
-        if explicit or not self.use_graph or self.seen < 1:
-            self.seen += 0 if explicit else 1
+        explicit = noise is not None or noise2 is not None           # such a step neither counts as the eager one nor captures
+        if not self.use_graph or not self.first.may_capture(counts=not explicit):
             return self._body(noise, noise2)
         if self.graph is None:
-            from .engine import _quiesce_before_capture
-            mode = _quiesce_before_capture(self.D)
-            self.graph = torch.cuda.CUDAGraph()
-            with ops.private_workspace(self._scratch), torch.cuda.graph(self.graph, capture_error_mode=mode):
-                self._body()
-            torch.cuda.synchronize()
+            self.graph, _ = capture(self._body, (self.D,), self._scratch)
         self.graph.replay()
 
     def images(self):

@@ -12,8 +12,8 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import ops as _ops
-from .hostio import THROTTLE
+from .captured import CapturedTrainStep, EagerFirst
+from .hostio import THROTTLE, upload_into
 
 
 # Test hook: run every collective code path on a 1-rank process group (set by bench.py --force-dist / tests).
@@ -253,134 +253,14 @@ def d_step_stylegan2_contrad(P, G, D, opt_D, options, images, step, reducer=None
     return d_loss, aux
 
 
-def _quiesce_before_capture(*modules):
-    """Called right before a stream capture; returns the ``capture_error_mode`` to capture with.
-
-    With a process group, every EAGER collective issued so far is still listed in ProcessGroupNCCL's watchdog thread until
-    that thread has seen it complete (it polls every 100 ms).  The capture pulls RCCL's own stream into capture mode, and
-    under the default 'global' capture mode ``hipEventQuery`` from ANY thread is then refused ("operation not permitted on
-    an event last recorded in a capturing stream") -- the watchdog rethrows and the whole job aborts.  Seen once in nine
-    runs of tests/dist_graph_worker.py, on a cold box where the watchdog had not drained yet.  Deterministic part: with a
-    process group the capture runs in 'thread_local' mode, in which only THIS thread's calls are policed, so the watchdog
-    thread may keep polling whatever it still holds.  Belt and braces: the device is drained first and the watchdog gets a
-    moment to retire the eager works (there is no API to wait for that)."""
-    for m in modules:                       # no autograd graph of an eager step may stay referenced across the capture
-        if hasattr(m, 'drop_pack_cache'):
-            m.drop_pack_cache()
-    torch.cuda.synchronize()
-    if dist.is_available() and dist.is_initialized():
-        import time
-        time.sleep(1.0)          # (ADVICE r4: the full second stays until thread_local mode is proven on W > 1 hardware)
-        torch.cuda.synchronize()
-        return 'thread_local'
-    return 'global'
-
-
 # ----------------------------------------------------------------------------------------------------------
-# the SNDCGAN D-step as one hipGraph
+# static inputs of the captured steps
 # ----------------------------------------------------------------------------------------------------------
-class GraphedDStep(object):
-    """``d_step`` (train_gan.py:153-163) captured ONCE into a hipGraph and replayed every iteration.
-
-    One D-step is ~120 kernel launches; enqueued from Python they cost ~2.8 ms of host time -- hidden behind 17.7 ms of
-    GPU work at batch 512, but most of the 3.5 ms step one rank of an 8-GPU job runs at batch 64 (DESIGN.md section 6).
-    Replaying a captured graph takes the host out: per step it only draws the random numbers (latents, augmentation
-    parameters -- on the host, in the reference's RNG order, exactly as the eager path), hands them over into STATIC
-    device tensors, refreshes three Adam scalars, and launches the graph.  What had to move from launch arguments into
-    device memory for that: the colour-op order of the augmentation (column 15 of the parameter block) and Adam's
-    step-dependent scalars (``contrad_adam_step_dev``).
-
-    With a process group (one rank of a data-parallel job, train_gan.py:230-318) the collectives are captured WITH the
-    step: G's SyncBN statistics all-reduce, the packed embedding all-gather inside the loss and the per-layer gradient
-    all-reduces the fused backward overlaps with itself (OverlappedGradReducer: RCCL's own stream forks from and joins the
-    capture stream through events, which a stream capture records as graph edges); Adam's 1/W travels in the device
-    scalars.  A per-rank batch of 64 is ~3.4 ms of GPU work against ~2.8 ms of Python launch time in the eager path
-    (DESIGN.md section 6) -- this is what takes the host off that critical path.  Every rank must replay the same graph
-    the same number of times (as every rank must issue the same eager collectives).
-    """
-
-    def __init__(self, P, G, D, opt_D, options, images, warmup=3):
-        from .augment import SimCLRAugment
-        from . import ops
-        self.P, self.G, self.D, self.opt, self.options = P, G, D, opt_D, options
-        self.aug = P.augment_fn
-        if not isinstance(self.aug, SimCLRAugment) or self.aug.p_blur is not None:
-            raise NotImplementedError('GraphedDStep: the simclr pipeline')
-        self.dist = dist_on()
-        self.reducer = None
-        if self.dist and getattr(D, '_grad_comm', None) is None:
-            self.reducer = GradAllReducer(D.parameters())       # flat collectives after the backward
-        self.images = images.clone()                    # static input: load_images() hands over a new real batch
-        N = images.size(0)
-        dev = images.device
-        self.N = N
-        for _ in range(warmup if len(opt_D.state) else max(warmup, 1)):     # optimizer state, workspaces, pools
-            d_step(P, G, D, opt_D, options, images, self.reducer)
-        self.z = torch.zeros(N, G.nz, device=dev)
-        self.params = torch.zeros(3 * N, ops.AUG_NPARAM, device=dev)
-        self.hyper = torch.ones(3, device=dev)
-        torch.cuda.synchronize()          # (capture records launches, it does not run them: the inputs stay untouched)
-        G.invalidate_cache()              # the step re-packs G's weights itself: G moves between D-steps in training
-        self.graph = torch.cuda.CUDAGraph()
-        self._scratch = {}           # this graph's own conv scratch (ops.private_workspace)
-        mode = _quiesce_before_capture(self.D)
-        if _ops.SEQUENCE is not None:
-            _ops.SEQUENCE.append('capture')          # (bench.py --shape-table: the launch order of the captured step follows)
-        with _ops.private_workspace(self._scratch), torch.cuda.graph(self.graph, capture_error_mode=mode):
-            self.d_loss, self.aux = self._body()
-        G.invalidate_cache()              # (what the capture allocated is filled by the first replay, not now)
-        torch.cuda.synchronize()
-
-    def load_images(self, images):
-        self.images.copy_(images)
-
-    def _refresh_inputs(self):
-        from .hostio import upload_into
-        G, N = self.G, self.N
-        z = torch.empty(N, G.nz).uniform_(-1, 1)                        # G.sample_latent's draw (sndcgan.py:50-52)
-        Pm, cf, _ = self.aug.sample(3 * N, self.images.shape[2], self.images.shape[3])
-        Pm[:, 15] = float(cf)
-        # pulled straight into the static tensors (was: pulls into temporaries, a cat of the pieces, a copy)
-        upload_into(z, self.z)
-        upload_into(Pm, self.params)
-        world = dist.get_world_size() if self.dist else 1
-        upload_into(torch.tensor([self.opt.hyper_values(1.0 / world)], dtype=torch.float32), self.hyper.view(1, 3))
-
-    def _body(self):
-        from . import ops
-        from .training.gan.contrad import _ContraDContrastive, _GanDLoss
-        P, G, D, N = self.P, self.G, self.D, self.N
-        with torch.no_grad():
-            gen = G(self.z)
-            cat = torch.cat([self.images, self.images, gen], dim=0)
-            aug = ops.simclr_augment(cat, self.params, -1, self.aug.r_c is not None)
-        d_all, aux = D(aug, sg_linear=True, projection=True, projection2=True)
-        simclr, sup = _ContraDContrastive.apply(aux['projection'], aux['projection2'], N, P.temp,
-                                                bool(P.distributed) and self.dist)
-        gan, d_real, d_gen = _GanDLoss.apply(d_all, N, self.options['loss'])
-        d_loss = simclr + P.lbd_a * sup
-        self.opt.zero_grad(set_to_none=True)
-        (d_loss + gan).backward()
-        if self.reducer is not None:
-            self.reducer()                      # (the overlapped reducer exchanged inside the backward already)
-        self.opt.step_captured(self.hyper)
-        # detached: the step's autograd graph must not outlive the capture (its AccumulateGrad nodes are tied to the
-        # capture stream; an eager backward later on would have to synchronise with it)
-        return d_loss.detach(), {'penalty': gan.detach(), 'd_real': d_real.detach(), 'd_gen': d_gen.detach()}
-
-    def __call__(self):
-        THROTTLE.begin()
-        self._refresh_inputs()
-        self.graph.replay()
-        THROTTLE.end()
-        return self.d_loss, self.aux
-
-
 class _StaticAugment(object):
     """Stand-in for ``P.augment_fn`` inside a captured step: the k-th call of a step applies the k-th parameter block.
     ``refresh()`` draws every block on the host with the pipeline's own sampler, in call order (the reference's RNG
-    order), and hands it into static device memory; the colour-op order travels in column 15, the Gaussian taps of
-    simclr_hq in a static kernel tensor."""
+    order), and hands it into static device memory; the colour-op order travels in column 15 (SimCLRAugment.sample
+    writes it), the Gaussian taps of simclr_hq in a static kernel tensor."""
 
     def __init__(self, aug, sizes, H, W, device):
         from . import ops
@@ -391,13 +271,12 @@ class _StaticAugment(object):
         self.k = 0
 
     def refresh(self):
-        from .hostio import upload
         for i, n in enumerate(self.sizes):
             Pm, _cf, sigma = self.aug.sample(n, self.H, self.W)
-            self.blocks[i].copy_(upload(Pm, self.dev))
+            upload_into(Pm, self.blocks[i])
             if self.taps is not None:
                 _r, g = self.aug.blur_kernel(self.H, sigma)
-                self.taps[i].copy_(upload(g.view(1, -1), self.dev).view(-1))
+                upload_into(g.view(1, -1), self.taps[i].view(1, -1))
 
     supports_out = True          # (``out=``: the last stage writes into the caller's buffer, see SimCLRAugment.apply)
 
@@ -439,19 +318,90 @@ class _StaticSG2Inputs(object):
 
     def refresh(self):
         """Generator.draw_inputs' draws, in its order, into the static tensors: one device normal_(), then the CPU draws."""
-        from .hostio import upload
         G, N = self.G, self.N
         self.flat.normal_()
         if self.mixing:
             nomix = torch.rand(N) >= self.style_mix
             mix_layer = torch.randint(G.n_latent, (N,)).masked_fill(nomix, G.n_latent)
-            self.mix_layer.copy_(upload(mix_layer.float().view(-1, 1), self.dev).view(-1))
+            upload_into(mix_layer.float().view(-1, 1), self.mix_layer.view(-1, 1))
 
     def forward(self):
         return self.G(**self.kw)
 
 
-class GraphedSG2DStep(object):
+def _with_augment(P, augment_fn):
+    """A copy of the run's namespace whose ``augment_fn`` is the captured step's static stand-in."""
+    import argparse
+    Pg = argparse.Namespace(**vars(P))
+    Pg.augment_fn = augment_fn
+    return Pg
+
+
+# ----------------------------------------------------------------------------------------------------------
+# the discriminator steps as captured hipGraphs (protocol and replay: captured.py)
+# ----------------------------------------------------------------------------------------------------------
+class GraphedDStep(CapturedTrainStep):
+    """``d_step`` (train_gan.py:153-163) captured ONCE into a hipGraph and replayed every iteration.
+
+    One D-step is ~120 kernel launches; enqueued from Python they cost ~2.8 ms of host time -- hidden behind 17.7 ms of
+    GPU work at batch 512, but most of the 3.5 ms step one rank of an 8-GPU job runs at batch 64 (DESIGN.md section 6).
+    Replaying a captured graph takes the host out: per step it only draws the random numbers (latents, augmentation
+    parameters -- on the host, in the reference's RNG order, exactly as the eager path), hands them over into STATIC
+    device tensors, refreshes three Adam scalars, and launches the graph.  What had to move from launch arguments into
+    device memory for that: the colour-op order of the augmentation (column 15 of the parameter block) and Adam's
+    step-dependent scalars (``contrad_adam_step_dev``).
+
+    With a process group (one rank of a data-parallel job, train_gan.py:230-318) the collectives are captured WITH the
+    step: G's SyncBN statistics all-reduce, the packed embedding all-gather inside the loss and the per-layer gradient
+    all-reduces the fused backward overlaps with itself (OverlappedGradReducer: RCCL's own stream forks from and joins the
+    capture stream through events, which a stream capture records as graph edges); Adam's 1/W travels in the device
+    scalars.  A per-rank batch of 64 is ~3.4 ms of GPU work against ~2.8 ms of Python launch time in the eager path
+    (DESIGN.md section 6) -- this is what takes the host off that critical path.  Every rank must replay the same graph
+    the same number of times (as every rank must issue the same eager collectives).
+    """
+
+    def __init__(self, P, G, D, opt_D, options, images, warmup=3):
+        from .augment import SimCLRAugment
+        self.P, self.G, self.D, self.options = P, G, D, options
+        self.aug = P.augment_fn
+        if not isinstance(self.aug, SimCLRAugment) or self.aug.p_blur is not None:
+            raise NotImplementedError('GraphedDStep: the simclr pipeline')
+        on = dist_on()
+        flat = on and getattr(D, '_grad_comm', None) is None        # else: exchanged inside the backward (overlapped)
+        super().__init__(opt_D, GradAllReducer(D.parameters()) if flat else None, on, images.device)
+        self.images = images.clone()                    # static input: load_images() hands over a new real batch
+        self.N = N = images.size(0)
+        for _ in range(warmup if len(opt_D.state) else max(warmup, 1)):     # optimizer state, workspaces, pools
+            d_step(P, G, D, opt_D, options, images, self.reducer)
+        self.z = torch.zeros(N, G.nz, device=images.device)
+        self.saug = _StaticAugment(self.aug, [3 * N], images.shape[2], images.shape[3], images.device)
+        self._capture(quiesce=(D,), repack=(G,))        # G moves between D-steps in training: the step re-packs its weights
+
+    def load_images(self, images):
+        self.images.copy_(images)
+
+    def _refresh_inputs(self):
+        z = torch.empty(self.N, self.G.nz).uniform_(-1, 1)              # G.sample_latent's draw (sndcgan.py:50-52)
+        upload_into(z, self.z)
+        self.saug.refresh()                                             # (drawn after z, as the eager step)
+
+    def _body(self):
+        from . import ops
+        from .training.gan.contrad import _ContraDContrastive, _GanDLoss
+        P, G, D, N = self.P, self.G, self.D, self.N
+        with torch.no_grad():
+            gen = G(self.z)
+            cat = torch.cat([self.images, self.images, gen], dim=0)
+            aug = ops.simclr_augment(cat, self.saug.blocks[0], -1, self.aug.r_c is not None)
+        d_all, aux = D(aug, sg_linear=True, projection=True, projection2=True)
+        simclr, sup = _ContraDContrastive.apply(aux['projection'], aux['projection2'], N, P.temp,
+                                                bool(P.distributed) and self.dist)
+        gan, d_real, d_gen = _GanDLoss.apply(d_all, N, self.options['loss'])
+        d_loss = simclr + P.lbd_a * sup
+        return self._finish(d_loss + gan, (d_loss, {'penalty': gan, 'd_real': d_real, 'd_gen': d_gen}))
+
+
+class GraphedSG2DStep(CapturedTrainStep):
     """The StyleGAN2 D-steps (``d_step_stylegan2`` / ``d_step_stylegan2_contrad``) as ONE captured hipGraph.
 
     These steps are 500-800 launches of mostly small kernels (the R1 double backward alone builds ~300 nodes); enqueued
@@ -463,52 +413,34 @@ class GraphedSG2DStep(object):
     With lazy R1 (``d_reg_every`` > 1) the graph holds the plain step and the R1 steps run eagerly."""
 
     def __init__(self, P, G, D, opt_D, options, images, contrad_script, style_mix=0.9, warmup=2):
-        import argparse
-        self.dist = dist_on()       # one rank of a data-parallel job: the embedding all-gather (inside the loss) and the
-        self.reducer = None         # gradient all-reduces (from the backward's hooks and / or after it) are captured
-        if self.dist:
+        on = dist_on()              # one rank of a data-parallel job: the embedding all-gather (inside the loss) and the
+        reducer = None              # gradient all-reduces (from the backward's hooks and / or after it) are captured
+        if on:
             rest = D.overlap_rest() if getattr(D, '_pack_comm', None) is not None else None
-            self.reducer = GradAllReducer(rest if rest is not None else D.parameters())
-        self.P, self.G, self.D, self.opt, self.options, self.images = P, G, D, opt_D, options, images.clone()
+            reducer = GradAllReducer(rest if rest is not None else D.parameters())
+        super().__init__(opt_D, reducer, on, images.device)
+        self.P, self.G, self.D, self.options, self.images = P, G, D, options, images.clone()
         self.contrad_script, self.style_mix = contrad_script, style_mix
         self.eager = d_step_stylegan2_contrad if contrad_script else d_step_stylegan2
-        N, dev = images.size(0), images.device
-        self.N = N
+        self.N = N = images.size(0)
         self.r1_in_graph = P.lbd_r1 > 0 and P.d_reg_every == 1
         for s in range(1, (warmup if len(opt_D.state) else max(warmup, 1)) + 1):     # optimizer state, workspaces
             self.eager(P, G, D, opt_D, options, images, s if P.d_reg_every == 1 else 1, self.reducer, style_mix)
-        H, W = images.shape[2], images.shape[3]
         sizes = ([N, 2 * N] if contrad_script else [3 * N]) + ([N] if self.r1_in_graph else [])
-        self.saug = _StaticAugment(P.augment_fn, sizes, H, W, dev)
-        self.Pg = argparse.Namespace(**vars(P))
-        self.Pg.augment_fn = self.saug
-        self.gin = _StaticSG2Inputs(G, N, dev, style_mix)
-        self.hyper = torch.ones(3, device=dev)
-        torch.cuda.synchronize()
-        G.invalidate_cache()              # as GraphedDStep: the packed tables are rebuilt inside the step
-        self.graph = torch.cuda.CUDAGraph()
-        self._scratch = {}           # this graph's own conv scratch (ops.private_workspace)
-        mode = _quiesce_before_capture(self.D)
-        if _ops.SEQUENCE is not None:
-            _ops.SEQUENCE.append('capture')          # (bench.py --shape-table: the launch order of the captured step follows)
-        with _ops.private_workspace(self._scratch), torch.cuda.graph(self.graph, capture_error_mode=mode):
-            self.d_loss, self.aux = self._body()
-        G.invalidate_cache()
-        torch.cuda.synchronize()
+        self.saug = _StaticAugment(P.augment_fn, sizes, images.shape[2], images.shape[3], images.device)
+        self.Pg = _with_augment(P, self.saug)
+        self.gin = _StaticSG2Inputs(G, N, images.device, style_mix)
+        self._capture(quiesce=(D,), repack=(G,))        # as GraphedDStep: the packed tables are rebuilt inside the step
 
     def load_images(self, images):
         self.images.copy_(images)
 
-    def _refresh(self):
-        from .hostio import upload
-        dev = self.images.device
+    def _refresh_inputs(self):
         self.gin.refresh()
         self.saug.refresh()
-        world = dist.get_world_size() if self.dist else 1
-        self.hyper.copy_(upload(torch.tensor([self.opt.hyper_values(1.0 / world)], dtype=torch.float32), dev).view(3))
 
     def _body(self):
-        P, G, D = self.Pg, self.G, self.D
+        P, D = self.Pg, self.D
         self.saug.k = 0
         with torch.no_grad():
             gen = self.gin.forward()
@@ -521,115 +453,73 @@ class GraphedSG2DStep(object):
             r1 = r1_loss(D, self.images, self.saug)
             loss = torch.add(loss, r1, alpha=(0.5 * P.lbd_r1) * P.d_reg_every)     # (as the eager step)
             aux['r1'] = r1
-        self.opt.zero_grad(set_to_none=True)
-        loss.backward()
-        if self.reducer is not None:
-            self.reducer()
-        self.opt.step_captured(self.hyper)
-        return d_loss.detach(), {k: v.detach() for k, v in aux.items()}     # (see GraphedDStep._body)
+        return self._finish(loss, (d_loss, aux))
 
     def __call__(self, step):
         P = self.P
         if P.lbd_r1 > 0 and P.d_reg_every > 1 and step % P.d_reg_every == 0:      # lazy-R1 step: eager
             return self.eager(P, self.G, self.D, self.opt, self.options, self.images, step, self.reducer, self.style_mix)
-        THROTTLE.begin()
-        self._refresh()
-        self.graph.replay()
-        THROTTLE.end()
-        return self.d_loss, self.aux
+        return super().__call__()
 
 
 # ----------------------------------------------------------------------------------------------------------
 # the generator steps as captured hipGraphs (the other half of a training iteration)
 # ----------------------------------------------------------------------------------------------------------
-def _hyper_upload(opt, hyper):
-    from .hostio import upload
-    world = dist.get_world_size() if dist_on() else 1              # Adam's 1/W of the data-parallel mean
-    hyper.copy_(upload(torch.tensor([opt.hyper_values(1.0 / world)], dtype=torch.float32), hyper.device).view(3))
-
-
-class GraphedGStep(object):
-    """The SNDCGAN generator step (train_gan.py:170-179: fakes WITH gradient -> ``loss_G_fn`` = D(augment(G(z))) ->
-    backward through D, the augmentation and G -> Adam on G) as one captured hipGraph.  The caller has set
-    ``set_grad(G, True); set_grad(D, False)`` and both networks to train mode, and ``opt_G`` holds state (one eager step
-    has run).  Per replay the host draws the latents and the augmentation block in the eager order."""
+class _GraphedGeneratorStep(CapturedTrainStep):
+    """What the two generator steps share.  The caller has set ``set_grad(G, True); set_grad(D, False)`` and both
+    networks to train mode, and ``opt_G`` holds state (one eager step has run).  With a process group SyncBN's statistics
+    exchange and G's gradient all-reduce are captured with the step."""
 
     def __init__(self, P, G, D, opt_G, options, N, H, W):
-        import argparse
-        from . import ops
+        on = dist_on()
+        if not len(opt_G.state):
+            raise RuntimeError('%s: capture after the first eager generator step (Adam state)' % type(self).__name__)
+        dev = next(G.parameters()).device
+        super().__init__(opt_G, GradAllReducer(G.parameters()) if on else None, on, dev)
+        self.P, self.G, self.D, self.options, self.N = P, G, D, options, N
+        self.saug = _StaticAugment(P.augment_fn, [N], H, W, dev)
+
+
+class GraphedGStep(_GraphedGeneratorStep):
+    """The SNDCGAN generator step (train_gan.py:170-179: fakes WITH gradient -> ``loss_G_fn`` = D(augment(G(z))) ->
+    backward through D, the augmentation and G -> Adam on G) as one captured hipGraph.  Per replay the host draws the
+    latents and the augmentation block in the eager order."""
+
+    def __init__(self, P, G, D, opt_G, options, N, H, W):
         from .augment import SimCLRAugment
         if not isinstance(P.augment_fn, SimCLRAugment):
             raise NotImplementedError('GraphedGStep: simclr-family pipeline')
-        self.dist = dist_on()      # data-parallel rank: SyncBN's statistics exchange and G's gradient all-reduce are captured
-        self.reducer = GradAllReducer(G.parameters()) if self.dist else None
-        if not len(opt_G.state):
-            raise RuntimeError('GraphedGStep: capture after the first eager generator step (Adam state)')
-        self.P, self.G, self.D, self.opt, self.options, self.N = P, G, D, opt_G, options, N
-        dev = next(G.parameters()).device
-        self.saug = _StaticAugment(P.augment_fn, [N], H, W, dev)
-        self.Pg = argparse.Namespace(**vars(P))
-        self.Pg.augment_fn = self.saug
-        self.z = torch.zeros(N, G.nz, device=dev)
-        self.hyper = torch.ones(3, device=dev)
-        torch.cuda.synchronize()
-        G.invalidate_cache()
-        self.graph = torch.cuda.CUDAGraph()
-        self._scratch = {}           # this graph's own conv scratch (ops.private_workspace)
-        mode = _quiesce_before_capture(self.D)
-        if _ops.SEQUENCE is not None:
-            _ops.SEQUENCE.append('capture')          # (bench.py --shape-table: the launch order of the captured step follows)
-        with _ops.private_workspace(self._scratch), torch.cuda.graph(self.graph, capture_error_mode=mode):
-            self.g_loss = self._body()
-        G.invalidate_cache()
-        torch.cuda.synchronize()
+        super().__init__(P, G, D, opt_G, options, N, H, W)
+        self.Pg = _with_augment(P, self.saug)
+        self.z = torch.zeros(N, G.nz, device=self.hyper.device)
+        self._capture(quiesce=(D,), repack=(G,))
+
+    def _refresh_inputs(self):
+        z = torch.empty(self.N, self.G.nz).uniform_(-1, 1)             # G.sample_latent's draw (sndcgan.py:50-52)
+        upload_into(z, self.z)
+        self.saug.refresh()
 
     def _body(self):
         self.saug.k = 0
         gen = self.G(self.z)
         g_loss = self.Pg.train_fn["G"](self.Pg, self.D, self.options, None, gen)
-        self.opt.zero_grad(set_to_none=True)
-        g_loss.backward()
-        if self.reducer is not None:
-            self.reducer()
-        self.opt.step_captured(self.hyper)
-        return g_loss.detach()
-
-    def __call__(self):
-        from .hostio import upload
-        THROTTLE.begin()
-        z = torch.empty(self.N, self.G.nz).uniform_(-1, 1)             # G.sample_latent's draw (sndcgan.py:50-52)
-        self.z.copy_(upload(z, self.z.device))
-        self.saug.refresh()
-        _hyper_upload(self.opt, self.hyper)
-        self.graph.replay()
-        THROTTLE.end()
-        return self.g_loss
+        return self._finish(g_loss, g_loss)
 
 
-class GraphedSG2GStep(object):
+class GraphedSG2GStep(_GraphedGeneratorStep):
     """The StyleGAN2 generator step of train_stylegan2_contraD.py:138-146,207 (D with ``sg_linear=False`` and both
     projections on the augmented fakes, non-saturating loss) as one captured hipGraph; same contract as GraphedGStep."""
 
     def __init__(self, P, G, D, opt_G, options, N, H, W, style_mix=0.9):
-        self.dist = dist_on()
-        self.reducer = GradAllReducer(G.parameters()) if self.dist else None
-        if not len(opt_G.state):
-            raise RuntimeError('GraphedSG2GStep: capture after the first eager generator step (Adam state)')
-        self.P, self.G, self.D, self.opt, self.options, self.N = P, G, D, opt_G, options, N
-        dev = next(G.parameters()).device
-        self.saug = _StaticAugment(P.augment_fn, [N], H, W, dev)
-        self.gin = _StaticSG2Inputs(G, N, dev, style_mix)
-        self.hyper = torch.ones(3, device=dev)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        self._scratch = {}           # this graph's own conv scratch (ops.private_workspace)
-        mode = _quiesce_before_capture(self.D)
-        if _ops.SEQUENCE is not None:
-            _ops.SEQUENCE.append('capture')          # (bench.py --shape-table: the launch order of the captured step follows)
-        with _ops.private_workspace(self._scratch), torch.cuda.graph(self.graph, capture_error_mode=mode):
-            self.g_loss = self._body()
-        G.invalidate_cache()
-        torch.cuda.synchronize()
+        super().__init__(P, G, D, opt_G, options, N, H, W)
+        self.gin = _StaticSG2Inputs(G, N, self.hyper.device, style_mix)
+        # (the forward with gradient builds its tables inside the autograd graph and never reads G's cache: invalidating
+        # it around this capture changes nothing, so the four steps capture alike)
+        self._capture(quiesce=(D,), repack=(G,))
+
+    def _refresh_inputs(self):
+        self.gin.refresh()
+        self.saug.refresh()
 
     def _body(self):
         from .training.gan.contrad import _GanGLoss
@@ -637,18 +527,36 @@ class GraphedSG2GStep(object):
         gen = self.gin.forward()
         d_gen, _aux = self.D(self.saug(gen), sg_linear=False, projection=True, projection2=True)
         g_loss = _GanGLoss.apply(d_gen, 'nonsat')
-        self.opt.zero_grad(set_to_none=True)
-        g_loss.backward()
-        if self.reducer is not None:
-            self.reducer()
-        self.opt.step_captured(self.hyper)
-        return g_loss.detach()
+        return self._finish(g_loss, g_loss)
 
-    def __call__(self):
-        THROTTLE.begin()
-        self.gin.refresh()
-        self.saug.refresh()
-        _hyper_upload(self.opt, self.hyper)
-        self.graph.replay()
-        THROTTLE.end()
-        return self.g_loss
+
+class GraphedCritic(object):
+    """``--graph`` of the train scripts: the D-step and the generator step of an iteration, each replayed from its own
+    captured graph.  Each is captured lazily, at its first occurrence the eager-first rule admits (captured.EagerFirst:
+    from the second iteration of the process on); until then ``__call__`` / ``generator`` return None and the caller
+    runs the step eagerly.  Every replay consumes exactly the host random numbers the eager iteration would, so a run with
+    ``--graph`` writes bitwise the checkpoints of a run without (tests/test_graph_gpu.py).  ``make_d(P, G, D, opt_D,
+    options, images)`` / ``make_g(P, G, D, opt_G, options, N, H, W)`` build the steps; ``not_contrad``: the error text for
+    any other ``P.mode`` (one %s)."""
+
+    def __init__(self, make_d, make_g, not_contrad):
+        self.make_d, self.make_g, self.not_contrad = make_d, make_g, not_contrad
+        self.step = self.gstep = None
+        self.first_d, self.first_g = EagerFirst(), EagerFirst()
+
+    def generator(self, P, opt, G, D, opt_G, images):
+        if self.gstep is None:
+            if not self.first_g.may_capture(opt_G):
+                return None
+            self.gstep = self.make_g(P, G, D, opt_G, opt, images.size(0), images.size(2), images.size(3))
+        return self.gstep()
+
+    def __call__(self, P, opt, G, D, opt_D, images, *step):
+        if self.step is None:
+            if not self.first_d.may_capture(opt_D):
+                return None
+            if P.mode != 'contrad':
+                raise NotImplementedError(self.not_contrad % P.mode)
+            self.step = self.make_d(P, G, D, opt_D, opt, images)
+        self.step.load_images(images)
+        return self.step(*step)

@@ -29,8 +29,9 @@ import torch
 
 from . import config, ops
 from .augment import SimCLRAugment
+from .captured import EagerFirst, capture
 from .evaluate.classifier import new_meters, summarize, test_classifier
-from .hostio import THROTTLE, upload
+from .hostio import THROTTLE, upload, upload_into
 from .models.gan import get_architecture
 from .models.gan.base import LinearWrapper
 
@@ -133,7 +134,7 @@ class HeadStep(object):
         self.params = torch.zeros(n, ops.AUG_NPARAM, device=dev)
         self.dlogits = torch.zeros(n, D.linear.out_features, device=dev)
         self.meters, self.lr = meters, lr_dev
-        self.graph, self.seen, self._scratch = None, 0, {}
+        self.graph, self.first, self._scratch = None, EagerFirst(), {}
 
     def _body(self):
         head = self.D.linear
@@ -147,19 +148,12 @@ class HeadStep(object):
     def __call__(self, x_u8, y_dev, idx):
         _to_float_nchw(x_u8, idx, self.images)
         self.labels.copy_(y_dev.index_select(0, idx))
-        P, cf, _ = self.aug.sample(self.n, self.images.shape[2], self.images.shape[3])
-        P[:, 15] = float(cf)
-        self.params.copy_(upload(P, self.images.device))
-        if not self.use_graph or self.seen < 1:
-            self.seen += 1
+        P, _cf, _ = self.aug.sample(self.n, self.images.shape[2], self.images.shape[3])     # (column 15: the colour-op order)
+        upload_into(P, self.params)
+        if not self.use_graph or not self.first.may_capture():
             return self._body()
         if self.graph is None:
-            from .engine import _quiesce_before_capture
-            mode = _quiesce_before_capture(self.D)
-            self.graph = torch.cuda.CUDAGraph()
-            with ops.private_workspace(self._scratch), torch.cuda.graph(self.graph, capture_error_mode=mode):
-                self._body()
-            torch.cuda.synchronize()
+            self.graph, _ = capture(self._body, (self.D,), self._scratch)
         self.graph.replay()
 
 

@@ -9,6 +9,7 @@ of the reference (:227) is dropped (the all-reduce already synchronises); FID / 
 of scope -- losses are logged to stdout / log.txt.  Datasets: ``--synthetic`` (default when
 torchvision is absent) feeds uniform-random CIFAR-shaped batches; otherwise torchvision CIFAR-10/100 as the reference.
 """
+import functools
 import os
 import time
 from argparse import ArgumentParser
@@ -18,7 +19,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import config
+from . import config, engine
 from .augment import get_augment
 from .engine import GradAllReducer, GraphedDStep, GraphedGStep, OverlappedGradReducer, sample_generator, set_grad
 from .hostio import THROTTLE
@@ -112,47 +113,13 @@ def _dataset_loader(name, batch, rank, world, workers):
         sampler.set_epoch(epoch)
 
 
-class GraphedCritic(object):
+class GraphedCritic(engine.GraphedCritic):
     """``--graph``: the critic iteration of ``train_step`` replayed from ONE captured hipGraph (engine.GraphedDStep) and
-    the generator step from a second one (engine.GraphedGStep).  Each is captured lazily at its first occurrence AFTER
-    its optimizer holds state (i.e. from the second iteration on); every
-    replay consumes exactly the host random numbers the eager iteration would, so a run with ``--graph`` produces
-    bitwise the checkpoints of a run without (tests/test_graph_gpu.py)."""
+    the generator step from a second one (engine.GraphedGStep)."""
 
     def __init__(self):
-        self.step = None
-        self.gstep = None
-        self.eager_d = self.eager_g = 0       # eager steps seen IN THIS PROCESS (see _may_capture)
-
-    @staticmethod
-    def _may_capture(seen, optimizer):
-        """Capture only after one eager step has run in this process AND the optimizer holds state.  The state alone is
-        not enough: after ``--resume`` it is non-empty at once, but the first step of a fresh process still does
-        first-use host work that must not land inside a stream capture (blocking host -> device copies of cached
-        constants, first-time workspace allocations, kernel module loads)."""
-        return seen >= 1 and len(optimizer.state) > 0
-
-    def generator(self, P, opt, G, D, opt_G, images):
-        """The generator step of the iteration from its own captured graph (engine.GraphedGStep); None while it has to
-        run eagerly (first iteration of the process)."""
-        if self.gstep is None:
-            if not self._may_capture(self.eager_g, opt_G):
-                self.eager_g += 1
-                return None
-            self.gstep = GraphedGStep(P, G, D, opt_G, opt, images.size(0), images.size(2), images.size(3))
-        return self.gstep()
-
-    def __call__(self, P, opt, G, D, opt_D, images):
-        if self.step is None:
-            if not self._may_capture(self.eager_d, opt_D):
-                self.eager_d += 1
-                return None                       # first iteration of this process: eager
-            if P.mode != 'contrad':
-                raise NotImplementedError("--graph captures the ContraD critic iteration (--mode contrad), not '%s'"
-                                          % P.mode)
-            self.step = GraphedDStep(P, G, D, opt_D, opt, images, warmup=0)
-        self.step.load_images(images)
-        return self.step()
+        super().__init__(functools.partial(GraphedDStep, warmup=0), GraphedGStep,
+                         "--graph captures the ContraD critic iteration (--mode contrad), not '%s'")
 
 
 def train_step(P, opt, G, D, opt_G, opt_D, loader, step, reducers, graphed=None):

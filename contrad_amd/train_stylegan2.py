@@ -17,6 +17,7 @@ ONE packed RCCL all-gather inside the loss, parameter gradients in flat all-redu
 global loss of the DataParallel formulation, without the per-step parameter broadcast.
 FID / GIF / tensorboard side paths are out of scope.
 """
+import functools
 import os
 import time
 from argparse import ArgumentParser
@@ -26,7 +27,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import config, ops
+from . import config, engine, ops
 from .augment import get_augment
 from .engine import (GradAllReducer, GraphedSG2DStep, GraphedSG2GStep, _sg2_fakes, loss_D_fn_separate, r1_loss, set_grad,
                      setup_grad_exchange)
@@ -150,44 +151,15 @@ def _opt_step(opt, reducer):
 CONTRAD_SCRIPT_STYLE_MIX = 0.9
 
 
-class GraphedCritic(object):
+class GraphedCritic(engine.GraphedCritic):
     """``--graph`` for train_stylegan2_contraD.py: its D-step (fresh fakes, two D calls, lazy R1) is exactly
-    engine.d_step_stylegan2_contrad, so it is replayed from engine.GraphedSG2DStep -- captured at the first D-step after
-    the optimizer holds state; the lazy-R1 steps run eagerly inside it.  Same random numbers as the eager iteration."""
+    engine.d_step_stylegan2_contrad, so it is replayed from engine.GraphedSG2DStep (the lazy-R1 steps run eagerly inside
+    it), and its generator step from engine.GraphedSG2GStep."""
 
     def __init__(self):
-        self.step = None
-        self.gstep = None
-        self.eager_d = self.eager_g = 0       # eager steps seen IN THIS PROCESS
-
-    @staticmethod
-    def _may_capture(seen, optimizer):
-        """One eager step in this process AND optimizer state (after ``--resume`` the state exists at once, but a fresh
-        process's first step does first-use host work -- constant uploads, workspace allocation, module loads -- that
-        must not fall inside a stream capture)."""
-        return seen >= 1 and len(optimizer.state) > 0
-
-    def generator(self, P, opt, G, D, opt_G, images):
-        """The generator step from its own captured graph (engine.GraphedSG2GStep); None while it runs eagerly."""
-        if self.gstep is None:
-            if not self._may_capture(self.eager_g, opt_G):
-                self.eager_g += 1
-                return None
-            self.gstep = GraphedSG2GStep(P, G, D, opt_G, opt, images.size(0), images.size(2), images.size(3),
-                                         style_mix=CONTRAD_SCRIPT_STYLE_MIX)
-        return self.gstep()
-
-    def __call__(self, P, opt, G, D, opt_D, images, step):
-        if self.step is None:
-            if not self._may_capture(self.eager_d, opt_D):
-                self.eager_d += 1
-                return None
-            if P.mode != 'contrad':
-                raise NotImplementedError("--graph captures the ContraD D-step (--mode contrad), not '%s'" % P.mode)
-            self.step = GraphedSG2DStep(P, G, D, opt_D, opt, images, contrad_script=True, style_mix=CONTRAD_SCRIPT_STYLE_MIX,
-                                        warmup=0)
-        self.step.load_images(images)
-        return self.step(step)
+        super().__init__(functools.partial(GraphedSG2DStep, contrad_script=True, style_mix=CONTRAD_SCRIPT_STYLE_MIX, warmup=0),
+                         functools.partial(GraphedSG2GStep, style_mix=CONTRAD_SCRIPT_STYLE_MIX),
+                         "--graph captures the ContraD D-step (--mode contrad), not '%s'")
 
 
 def train_iteration(P, opt, G, D, g_ema, opt_G, opt_D, loader, step, reducers, contrad_script, graphed=None):

@@ -112,6 +112,85 @@ def test_stylegan2_graph_replay_equals_eager_steps(contrad_script, every):
         assert torch.equal(a, p.detach())
 
 
+def _generator_step_runs(build, eager_step, make_graphed):
+    """2 eager generator steps, then 3 more -- eager, or replayed from the graph captured after the second -- from the same
+    seeds -> [(losses, G's parameters, extra tensors of ``build``)] of the two runs."""
+    from contrad_amd.engine import set_grad
+    runs = []
+    for graph in (False, True):
+        P, G, D, opt_G, extra = build()
+        set_grad(G, True); set_grad(D, False)
+        torch.manual_seed(9); np.random.seed(9); torch.cuda.manual_seed(9)
+        losses = [eager_step(P, G, D, opt_G).item() for _ in range(2)]
+        gs = make_graphed(P, G, D, opt_G) if graph else None
+        for _ in range(3):
+            losses.append((gs() if graph else eager_step(P, G, D, opt_G)).item())
+        runs.append((losses, [p.detach().clone() for p in G.parameters()], [t.clone() for t in extra(G)]))
+    return runs
+
+
+def _assert_same_generator_runs(runs):
+    (le, pe, xe), (lg, pg, xg) = runs
+    assert lg == le
+    assert len(pe) == len(pg) and all(torch.equal(a, b) for a, b in zip(pe, pg))
+    assert len(xe) == len(xg) and all(torch.equal(a, b) for a, b in zip(xe, xg))
+
+
+def test_generator_graph_replay_equals_eager_steps():
+    """GraphedGStep (SNDCGAN, N = 16, 32 x 32): losses, G's parameters and G's BatchNorm running mean, bitwise."""
+    from contrad_amd.engine import GraphedGStep
+    from contrad_amd.optim import FusedAdam
+    N = 16
+
+    def build():
+        P, G, D, _opt_D, _x = _setup(N)
+        return P, G, D, FusedAdam(G.parameters(), lr=2e-4, betas=(0.5, 0.999)), lambda G: [G.norm_init.running_mean]
+
+    def eager_step(P, G, D, opt_G):
+        g_loss = P.train_fn['G'](P, D, {'loss': 'nonsat'}, None, G(G.sample_latent(N)))
+        opt_G.zero_grad()
+        g_loss.backward()
+        opt_G.step()
+        return g_loss.detach()
+
+    _assert_same_generator_runs(_generator_step_runs(
+        build, eager_step, lambda P, G, D, opt_G: GraphedGStep(P, G, D, opt_G, {'loss': 'nonsat'}, N, 32, 32)))
+
+
+def test_stylegan2_generator_graph_replay_equals_eager_steps():
+    """GraphedSG2GStep (StyleGAN2, N = 8, 32 x 32, style_mix 0.9: the mixing draws are consumed): losses and G's
+    parameters, bitwise."""
+    from contrad_amd.augment import SimCLRAugment
+    from contrad_amd.engine import GraphedSG2GStep
+    from contrad_amd.models.gan import get_architecture
+    from contrad_amd.optim import FusedAdam
+    from contrad_amd.train_stylegan2 import loss_G_nonsat, sample_generator
+    from contrad_amd.training.gan import setup
+    N, style_mix = 8, 0.9
+
+    def build():
+        torch.manual_seed(0); np.random.seed(0)
+        G, D = get_architecture('stylegan2', (32, 32, 3))
+        G, D = G.to(DEV).train(), D.to(DEV).train()
+        P = setup(argparse.Namespace(mode='contrad', aug='simclr', temp=0.1, lbd_a=1.0, distributed=False, lbd_r1=0.1,
+                                     d_reg_every=1))
+        P.augment_fn = SimCLRAugment(scale=(0.2, 1.0))
+        return P, G, D, FusedAdam(G.parameters(), lr=2e-3, betas=(0.0, 0.99)), lambda G: []
+
+    def eager_step(P, G, D, opt_G):
+        gen = sample_generator(G, N, style_mix=style_mix, enable_grad=True)
+        d_gen, _aux = D(P.augment_fn(gen), sg_linear=False, projection=True, projection2=True)
+        g_loss = loss_G_nonsat(d_gen)
+        opt_G.zero_grad()
+        g_loss.backward()
+        opt_G.step()
+        return g_loss.detach()
+
+    _assert_same_generator_runs(_generator_step_runs(
+        build, eager_step,
+        lambda P, G, D, opt_G: GraphedSG2GStep(P, G, D, opt_G, {'loss': 'nonsat'}, N, 32, 32, style_mix=style_mix)))
+
+
 def _state(logdir, names):
     return {n: torch.load(os.path.join(logdir, n), map_location='cpu') for n in names}
 
@@ -175,7 +254,7 @@ def _fresh_process(script, args):
 @pytest.mark.parametrize('family', ['sndcgan', 'stylegan2'])
 def test_resume_with_graph_in_a_fresh_process(tmp_path, family):
     """--resume + --graph: the optimizer state exists from the first iteration, the process is cold.  The capture has to
-    wait for one eager iteration of THIS process (GraphedCritic._may_capture); the resumed run with --graph writes
+    wait for one eager iteration of THIS process (captured.EagerFirst); the resumed run with --graph writes
     bitwise the checkpoints of the resumed eager run."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     if family == 'sndcgan':

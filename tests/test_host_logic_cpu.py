@@ -185,3 +185,118 @@ def test_train_gan_accepts_every_flag_of_the_reference_cli():
                     '--evaluate_every', '2000', '--save_every', '100000', '--comment', 'x', '--workers', '0',
                     '--world-size', '1', '--rank', '0', '--port', '40404'])
     assert a.mode == 'contrad' and a.no_fid and a.no_gif and a.n_eval_avg == 3 and a.world_size == 1 and a.rank == 0
+
+
+class _FakeOptimizer(object):
+    def __init__(self, with_state):
+        self.state = {'p': {'step': 3}} if with_state else {}
+
+
+def test_eager_first_gate():
+    """captured.EagerFirst alone: the first use of a process is eager; the second captures only once the optimizer holds
+    state; a resumed run (state from the start) still runs one eager step first; uses with ``counts=False`` (cDDLS with
+    explicit noise) neither count nor capture."""
+    from contrad_amd.captured import EagerFirst
+    g = EagerFirst()                                     # no optimizer (lineval head, cDDLS)
+    assert [g.may_capture() for _ in range(3)] == [False, True, True]
+
+    g, opt = EagerFirst(), _FakeOptimizer(False)         # fresh run: the state appears with the first eager step
+    assert not g.may_capture(opt)
+    assert not g.may_capture(opt)                        # second use, but the optimizer is still empty
+    opt.state['p'] = {'step': 1}
+    assert g.may_capture(opt) and g.may_capture(opt)
+
+    g, opt = EagerFirst(), _FakeOptimizer(True)          # --resume: state at once, cold process
+    assert [g.may_capture(opt) for _ in range(3)] == [False, True, True]
+
+    g = EagerFirst()                                     # explicit-noise steps
+    assert not g.may_capture(counts=False) and not g.may_capture(counts=False) and g.eager == 0
+    assert not g.may_capture()                           # the first counted use is still the eager one
+    assert not g.may_capture(counts=False)               # ... and an explicit step never captures
+    assert g.may_capture() and g.eager == 1
+
+
+def test_graphed_critic_builds_each_step_once_behind_the_gate():
+    """engine.GraphedCritic with stand-in factories: None (eager) in the first iteration, then one step object per
+    half, fed the new real batch; any mode but contrad raises the script's own text; the step argument is passed on."""
+    import argparse
+    from contrad_amd.engine import GraphedCritic
+    built = []
+
+    class Step(object):
+        def __init__(self, kind, *args):
+            built.append((kind, args))
+            self.loaded = []
+
+        def load_images(self, images):
+            self.loaded.append(images)
+
+        def __call__(self, *step):
+            return ('replayed',) + step
+
+    critic = GraphedCritic(lambda *a: Step('d', *a), lambda *a: Step('g', *a), "not '%s'")
+    P, opt_D, opt_G = argparse.Namespace(mode='contrad'), _FakeOptimizer(True), _FakeOptimizer(False)
+    images = torch.zeros(4, 3, 8, 16)
+    assert critic(P, 'opt', 'G', 'D', opt_D, images, 1) is None and critic.generator(P, 'opt', 'G', 'D', opt_G, images) is None
+    opt_G.state['p'] = {'step': 1}
+    assert critic(P, 'opt', 'G', 'D', opt_D, images, 2) == ('replayed', 2)
+    assert critic(P, 'opt', 'G', 'D', opt_D, images) == ('replayed',)
+    assert critic.generator(P, 'opt', 'G', 'D', opt_G, images) == ('replayed',)
+    assert critic.generator(P, 'opt', 'G', 'D', opt_G, images) == ('replayed',)
+    assert built == [('d', (P, 'G', 'D', opt_D, 'opt', images)), ('g', (P, 'G', 'D', opt_G, 'opt', 4, 8, 16))]
+    assert len(critic.step.loaded) == 2
+
+    other = GraphedCritic(lambda *a: Step('d', *a), lambda *a: Step('g', *a), "not '%s'")
+    Pb = argparse.Namespace(mode='std')
+    assert other(Pb, 'opt', 'G', 'D', opt_D, images) is None
+    with pytest.raises(NotImplementedError, match="not 'std'"):
+        other(Pb, 'opt', 'G', 'D', opt_D, images)
+
+
+def test_captured_train_step_protocol_on_the_host(monkeypatch):
+    """captured.CapturedTrainStep with the capture and the throttle replaced by recorders: the packed weights are dropped
+    before and after the capture, the body's tail runs zero_grad -> backward -> reducer -> Adam and returns detached results,
+    and a replay is throttle, inputs, the Adam scalars EXACTLY once (hyper_values advances the step count), graph."""
+    from contrad_amd import captured
+    log = []
+
+    class Recorder(object):
+        def __init__(self, *names):
+            for n in names:
+                setattr(self, n, lambda *a, _n=n, **k: log.append(_n))
+
+    def fake_capture(body, modules, scratch):
+        log.append(('capture', tuple(modules)))
+        return Recorder('replay'), body()
+    monkeypatch.setattr(captured, 'capture', fake_capture)
+    monkeypatch.setattr(captured, 'THROTTLE', Recorder('begin', 'end'))
+
+    class Opt(Recorder):
+        steps = 0
+
+        def hyper_values(self, grad_scale):
+            self.steps += 1
+            return [0.5 * self.steps, 0.25, grad_scale]
+
+    class Step(captured.CapturedTrainStep):
+        def __init__(self):
+            super().__init__(Opt('zero_grad', 'step_captured'), lambda: log.append('reducer'), False, 'cpu')
+            self.w = torch.ones(2, requires_grad=True)
+            self._capture(quiesce=('D',), repack=(Recorder('invalidate_cache'),))
+
+        def _refresh_inputs(self):
+            log.append('inputs')
+
+        def _body(self):
+            loss = (self.w * 2).sum()
+            return self._finish(loss, (loss, {'twice': loss * 2}))
+
+    step = Step()
+    assert log == ['invalidate_cache', ('capture', ('D',)), 'zero_grad', 'reducer', 'step_captured', 'invalidate_cache']
+    assert torch.equal(step.w.grad, torch.full((2,), 2.0))
+    del log[:]
+    for k in (1, 2):
+        d_loss, aux = step()
+        assert not d_loss.requires_grad and not aux['twice'].requires_grad and (d_loss.item(), aux['twice'].item()) == (4.0, 8.0)
+        assert step.opt.steps == k and step.hyper.tolist() == [0.5 * k, 0.25, 1.0]
+    assert log == ['begin', 'inputs', 'replay', 'end'] * 2
