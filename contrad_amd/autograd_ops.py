@@ -11,8 +11,8 @@ The convolution family is closed under differentiation (each op is bilinear in i
 
 and so is the RGB family (RgbConvFn / RgbDgradFn / RgbWgradFn).  Activations are NHWC; ``wp`` is the packed GEMM
 weight produced by PackWeightsFn (whose backward is UnpackWeightsFn and vice versa).
-The SNDCGAN discriminator does NOT use these (it is one fused node, models/gan/sndcgan.py); the StyleGAN2
-discriminator does.
+The SNDCGAN discriminator is one fused node (models/gan/sndcgan.py) and uses these only in its second-order form
+(``D.second_order()``, the gradient penalty); D_SNResNet18 and the StyleGAN2 discriminator are composed from them.
 """
 import math
 
@@ -661,12 +661,15 @@ class SnPackWeightsFn(Function):
     autograd, applied to every Conv2d / Linear of a discriminator: sndcgan.py:111-118, snresnet.py:59-66): ONE batched
     launch runs the power iteration of every layer (train mode; ``weight_u`` / ``weight_v`` updated in place), computes
     sigma = u^T W v and writes W / sigma in the packed GEMM layout; the backward maps the packed gradients to
-    d loss / d weight_orig = G / sigma - (<G, W> / sigma^2) u v^T with the u, v of THIS forward.  First-order."""
+    d loss / d weight_orig = G / sigma - (<G, W> / sigma^2) u v^T with the u, v of THIS forward.  First-order.
+    An entry of ``mods`` may be ``(module, (K, C, T))``: the weight is read as that (K, C, T) view (SnSpec's ``view_kct`` --
+    a Linear over NCHW-flattened features packed as the T-tap "conv" on their NHWC form)."""
 
     @staticmethod
     def forward(ctx, mods, training, *ws):
         dev = ws[0].device
-        specs = [ops.SnSpec(w, m.weight_u, m.weight_v) for m, w in zip(mods, ws)]
+        mods = [m if isinstance(m, tuple) else (m, None) for m in mods]
+        specs = [ops.SnSpec(w, m.weight_u, m.weight_v, view_kct=kct) for (m, kct), w in zip(mods, ws)]
         ldws = [ops.round_up(sp.K, 4) for sp in specs]
         outs = [_packed_buffer((sp.T * sp.C, ld), sp.K, dev) for sp, ld in zip(specs, ldws)]
         offs, n = ops.sn_scratch_floats(specs)

@@ -5,11 +5,15 @@ the batched spectral-norm weight prep, the fused RGB first conv, six implicit-GE
 GEMMs; the backward chains dgrad (with the producer's LeakyReLU derivative fused in its epilogue), wgrad, bias
 column sums and the batched spectral-norm weight gradient.  Activations are NHWC internally; inputs/outputs
 keep the reference's NCHW / (B, features) contract, state-dict names match the reference.
+Inside ``D.second_order()`` the same network runs composed from the any-order nodes of contrad_amd.autograd_ops
+instead (``_run_composed``): the form whose input gradient can itself be differentiated (the gradient penalty).
 
 ``G_SNDCGAN`` (sndcgan.py:13-66) implements the no-grad forward used inside the discriminator step
 (train_gan.py:155-156): linear -> BatchNorm(batch stats, SyncBN across ranks) -> ReLU -> 3 x [transposed conv
 (= conv dgrad kernel) -> BatchNorm -> ReLU] -> transposed conv + tanh -> 0.5x+0.5.
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 import torch.distributed as dist
@@ -298,9 +302,66 @@ class D_SNDCGAN(BaseDiscriminator):
             out += [m.weight_orig, m.bias]
         return out
 
+    @contextlib.contextmanager
+    def second_order(self):
+        """Inside this block every call runs the composed form (``_run_composed``), whose backward can be differentiated
+        again.  An explicit opt-in: outside it every call -- the generator step included, whose inputs require grad --
+        takes the fused node, which is faster and is what the captured steps record.  The composed form has no
+        ``finetuning=True`` mode (a first-order use): inside the block that flag raises NotImplementedError."""
+        saved, self._second_order = getattr(self, '_second_order', False), True
+        try:
+            yield self
+        finally:
+            self._second_order = saved
+
+    def _sn_modules(self):
+        """The 13 spectral-norm modules in _DPlan's order, the first head layers with their NHWC 'conv' view."""
+        T_head = self.s_hb * self.s_wb
+        convs = [self.main[2 * i] for i in range(7)]
+        heads1 = [self._head().l1, self.projection[0], self.projection2[0]]
+        heads2 = [self._head().l2, self.projection[2], self.projection2[2]]
+        return convs + [(m, (self.d_hidden, 512, T_head)) for m in heads1] + heads2
+
+    def _run_composed(self, inputs, sg_linear, finetuning, want_features):
+        """The network of _DFunction out of the any-order nodes (D_SNResNet18._run is the template): one batched
+        spectral-norm launch over the same 13 modules (same parameters, same u / v buffers, one power iteration per call in
+        train mode), bias + LeakyReLU in the conv epilogues, the heads as 1x1 convs on the NHWC-flat features.  All three
+        heads are evaluated, as in the reference's BaseDiscriminator.forward."""
+        if finetuning:
+            raise NotImplementedError('D_SNDCGAN.second_order(): finetuning=True is a first-order mode')
+        mods = self._sn_modules()
+        plain = [m[0] if isinstance(m, tuple) else m for m in mods]
+        wp = A.SnPackWeightsFn.apply(mods, self.training, *[m.weight_orig for m in plain])
+        images = inputs.contiguous().float()
+        B = images.shape[0]
+        dh, dp = self.d_hidden, self.d_project
+        acts = []
+        x = A.RgbConvBiasActFn.apply(images, wp[0], plain[0].bias, 64, (3, 2.0, -1.0), _SLOPE, 1.0)
+        acts.append(x)
+        for i in range(1, 7):
+            ci, co, k, s, p = _D_CONVS[i]
+            x = A.ConvBiasActFn.apply(x, wp[i], plain[i].bias, (co, k, k, s, p), _SLOPE, 1.0)
+            acts.append(x)
+        f4 = x.reshape(B, 1, 1, self.n_features)          # NHWC-flat: the packed rows (tap * 512 + c) index exactly this
+        fd = f4.detach() if sg_linear else f4
+
+        def lin(i, t, K, slope):
+            return A.ConvBiasActFn.apply(t, wp[i], plain[i].bias, (K, 1, 1, 1, 0), slope, 1.0)
+
+        h_l, h_p, h_p2 = lin(7, fd, dh, _SLOPE), lin(8, f4, dh, _SLOPE), lin(9, f4, dh, _SLOPE)
+        if getattr(self, '_record_activations', False):    # test hook, in _DFunction's format
+            self._last_activations = ([a.detach() for a in acts], torch.cat([h_l, h_p, h_p2], dim=3).detach())
+        logits = lin(10, h_l, 1, 1.0).view(B, 1)
+        proj = lin(11, h_p, dp, 1.0).view(B, dp)
+        proj2 = lin(12, h_p2, dp, 1.0).view(B, dp)
+        feats = x.permute(0, 3, 1, 2).reshape(B, -1) if want_features else None
+        return logits, proj, proj2, feats
+
     def _run(self, inputs, sg_linear, finetuning, want_features):
         if not inputs.is_cuda:
             raise RuntimeError('contrad_amd.D_SNDCGAN runs on the MI355X HIP path only (no CPU fallback)')
+        if getattr(self, '_second_order', False):
+            return self._run_composed(inputs, sg_linear, finetuning, want_features)
         if finetuning:
             # reference: features in eval mode under no_grad (base.py:114-119): no trunk gradient, no power iteration
             # in the trunk (handled inside the node); the heads still train

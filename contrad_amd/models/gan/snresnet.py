@@ -7,6 +7,8 @@ Composed from the differentiable HIP nodes of contrad_amd.autograd_ops: all 20 c
 batched spectral-norm launch (SnPackWeightsFn), bias + LeakyReLU sit in the conv epilogues, activations are NHWC.
 State-dict names and order match the reference.
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -60,6 +62,11 @@ class D_SNResNet18(BaseDiscriminator):
         for m in root.modules():
             if isinstance(m, SNParams):
                 _default_init(m)
+
+    def second_order(self):
+        """Capability marker shared with D_SNDCGAN.second_order(): this network is composed from the any-order nodes
+        already, so there is nothing to switch."""
+        return contextlib.nullcontext(self)
 
     def _sn_modules(self):
         mods = [self.conv1]

@@ -1347,3 +1347,48 @@ def gan_d_loss_2n(logits, N, kind):
     lib().call('contrad_gan_d_loss_2n', _p(logits), max(logits.stride(0), 1), N, GAN_LOSS_KINDS[kind], _p(out), _p(grad),
                _stream())
     return out, grad
+
+
+# --------------------------------------------------------------------------------------------------
+# gradient penalty (csrc/gp.hip): interpolation between two batches, lbd * mean (||grad_n|| - 1)^2 and its cotangent
+# --------------------------------------------------------------------------------------------------
+def _chk_nchw(t, name, like=None):
+    _chk(t, name)
+    if t.dim() != 4 or not t.is_contiguous() or t.numel() == 0 or (like is not None and (
+            t.shape != like.shape or t.device != like.device)):
+        raise RuntimeError('contrad_hip: %s must be a contiguous non-empty NCHW tensor%s' %
+                           (name, '' if like is None else ' of shape %s on %s' % (tuple(like.shape), like.device)))
+
+
+def gp_interpolate(x, g, alpha, out=None):
+    """xhat[n] = alpha[n] * x[n] + (1 - alpha[n]) * g[n]; x, g NCHW (N,C,H,W), alpha (N,) on the same device.  Rows with
+    alpha 1 / 0 are x / g bit for bit."""
+    _chk_nchw(x, 'x'); _chk_nchw(g, 'g', x); _chk(alpha, 'alpha')
+    N = x.shape[0]
+    if tuple(alpha.shape) != (N,) or not alpha.is_contiguous() or alpha.device != x.device:
+        raise RuntimeError('contrad_hip: gp_interpolate needs alpha of shape (%d,) on the images\' device' % N)
+    if out is None:
+        out = torch.empty_like(x)
+    _chk_out(out, x, 'gp_interpolate')
+    lib().call('contrad_gp_interpolate', _p(x), _p(g), _p(alpha), _p(out), N, ctypes.c_longlong(x.numel() // N), _stream())
+    return out
+
+
+def gp_penalty(grad, lbd, cot=None):
+    """grad NCHW (N,C,H,W) -> (out (1,) = lbd * mean_n (||grad_n||_2 - 1)^2, norms (N,), cot = d out / d grad; cot_n = 0 on a
+    zero row)."""
+    _chk_nchw(grad, 'grad')
+    N = grad.shape[0]
+    L = grad.numel() // N
+    if cot is None:
+        cot = torch.empty_like(grad)
+    _chk_out(cot, grad, 'gp_penalty')
+    nbytes = lib().raw('contrad_gp_penalty_workspace_bytes')(N, ctypes.c_longlong(L))
+    if nbytes < 0:
+        raise RuntimeError('contrad_hip: gp_penalty: unsupported size %d x %d' % (N, L))
+    ws = _workspace(nbytes, grad.device)
+    out = torch.empty(1, device=grad.device, dtype=torch.float32)
+    norms = torch.empty(N, device=grad.device, dtype=torch.float32)
+    lib().call('contrad_gp_penalty', _p(grad), _p(norms), _p(out), _p(cot), N, ctypes.c_longlong(L), float(lbd), _p(ws),
+               ctypes.c_longlong(ws.numel() * 4), _stream())
+    return out, norms, cot

@@ -4,12 +4,20 @@
 batch, as the reference does (penalty.py:45-58).  The two calls are not merged into one batch: in train mode every call
 advances the spectral-norm power iteration, and the second call has to see the ``u`` / ``v`` the first one left.  The
 squared-difference term and both of its gradients come from one launch (csrc/baseline_aug.hip: consistency_kernel).
+
+``gp`` (WGAN-GP's gradient penalty) is a further D call, on the interpolated batch and on the discriminator's second-order
+form (``D.second_order()``): its input gradient is taken with ``create_graph=True`` and the penalty's backward runs the
+double backward of the any-order node family into ``weight_orig`` (csrc/gp.hip: the interpolation, the penalty and its
+cotangent).
 """
 import inspect
 
 import torch
+from torch.autograd.function import once_differentiable
 
+from . import autograd_ops as A
 from . import ops
+from .hostio import upload
 
 
 class _Consistency(torch.autograd.Function):
@@ -37,9 +45,41 @@ def no_penalty(images):
     return torch.zeros(1, device=images.device)
 
 
+class _GradientPenalty(torch.autograd.Function):
+    """lbd * mean_n (||grad_n||_2 - 1)^2 on an (N, C, H, W) input gradient; value, norms and the cotangent d out / d grad
+    from one call (csrc/gp.hip), the backward scales the saved cotangent."""
+
+    @staticmethod
+    def forward(ctx, grad, lbd):
+        out, _norms, cot = ops.gp_penalty(grad.contiguous().float(), lbd)
+        ctx.save_for_backward(cot)
+        return out[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        cot, = ctx.saved_tensors
+        return cot * g, None
+
+
 def gradient_penalty(D, images, gen_images, lbd):
-    raise NotImplementedError("penalty 'gp' (penalty.py:16-42) differentiates the input gradient of D: it needs the "
-                              "second-order path through the SNDCGAN trunk, which this build has for StyleGAN2's R1 only")
+    """penalty.py:16-42.  ``alpha`` is drawn on the host where the reference draws it (torch.rand(N, 1, 1, 1), CPU
+    generator) and handed over as an (N,) block; D(xhat) is one more discriminator call in the caller's mode, i.e. one
+    more power iteration in train mode."""
+    second_order = getattr(D, 'second_order', None)
+    if second_order is None:
+        raise NotImplementedError("penalty 'gp' (penalty.py:16-42) differentiates the input gradient of D: it needs a "
+                                  "second-order path through the discriminator, which %s does not offer (no "
+                                  "second_order())" % type(D).__name__)
+    N = images.size(0)
+    alpha = upload(torch.rand(N, 1, 1, 1).view(N), images.device)
+    xhat = ops.gp_interpolate(images.detach().contiguous().float(), gen_images.detach().contiguous().float(), alpha)
+    xhat.requires_grad_()
+    with second_order():
+        d = D(xhat)
+    with A.input_grad_only():       # this backward is asked for d / d xhat only: skip the parameter gradients
+        grad, = torch.autograd.grad(outputs=d.sum(), inputs=xhat, create_graph=True, retain_graph=True)
+    return _GradientPenalty.apply(grad, float(lbd))
 
 
 def consistency(D, P, images, d_real, lbd):

@@ -35,7 +35,7 @@ def parse_args(argv=None):
     parser.add_argument('gin_config', type=str, help='Path to the gin configuration file')
     parser.add_argument('architecture', type=str, help='Architecture')
     parser.add_argument('--mode', default='std', type=str, help='Training mode (contrad | simclr_only | std | aug | aug_both)')
-    parser.add_argument('--penalty', default='none', type=str, help='none | cr | bcr (std / aug / aug_both)')
+    parser.add_argument('--penalty', default='none', type=str, help='none | cr | bcr | gp (std / aug / aug_both)')
     parser.add_argument('--aug', default='none', type=str, help='Augmentation (simclr | simclr_hq | simclr_hq_cutout | none | hflip | hfrt | diffaug; diffaug needs a gin '
                              'file that binds augment.diffaug_policy = "color,cutout", as configs/gan/diffaug/c10_diffaug.gin '
                              'does: with any other file it raises NotImplementedError until the line is added)')

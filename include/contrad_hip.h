@@ -673,6 +673,23 @@ int contrad_cddls_latent_update(float* z, const float* gz, long long n, float ep
 int contrad_cddls_energy(const float* d, int ldd, const float* feat, const float* c_row, const float* bias_term,
                          const float* z2, float* e, int N, int F, long long P, contrad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Gradient penalty (csrc/gp.hip): the two device-side pieces of --penalty=gp (the reference's penalty.py:16-42).
+ * Rows of chw = C*H*W floats of (N, C, H, W) fp32 NCHW tensors; 16-byte accesses at every 16-byte aligned address (scalar
+ * head and tail of a row otherwise).  No float atomics: every sum has a fixed order, results are bitwise repeatable.
+ * ---------------------------------------------------------------------------------------------- */
+/* xhat[n] = alpha[n] * x[n] + (1 - alpha[n]) * g[n], alpha (N,) on the device.  A row with alpha == 1 is x[n] and a row
+ * with alpha == 0 is g[n], bit for bit.  xhat must be neither x nor g. */
+int contrad_gp_interpolate(const float* x, const float* g, const float* alpha, float* xhat, int N, long long chw,
+                           contrad_stream_t stream);
+/* Bytes of the workspace of contrad_gp_penalty (16 for rows of at most 16 KiB, which take one workgroup each with the row
+ * staged in LDS; the partial sums of the two-launch form otherwise); < 0 on bad arguments. */
+long long contrad_gp_penalty_workspace_bytes(int N, long long chw);
+/* norms[n] = ||grad_n||_2, out1[0] = lbd * mean_n (norms[n] - 1)^2, cot[n] = lbd * 2 (norms[n] - 1) / (N * norms[n]) *
+ * grad_n = d out1 / d grad; a row with norms[n] == 0 gets cot_n == 0.  cot must not be grad. */
+int contrad_gp_penalty(const float* grad, float* norms, float* out1, float* cot, int N, long long chw, float lbd,
+                       float* workspace, long long workspace_bytes, contrad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
