@@ -1392,3 +1392,40 @@ def gp_penalty(grad, lbd, cot=None):
     lib().call('contrad_gp_penalty', _p(grad), _p(norms), _p(out), _p(cot), N, ctypes.c_longlong(L), float(lbd), _p(ws),
                ctypes.c_longlong(ws.numel() * 4), _stream())
     return out, norms, cot
+
+
+# --------------------------------------------------------------------------------------------------
+# real-image batches (csrc/data.hip): gather by index, flip, NHWC uint8 -> NCHW float / 255 in one launch
+# --------------------------------------------------------------------------------------------------
+GATHER_MAX_N = 1 << 24          # the index column of the parameter block is fp32: exact below 2^24
+
+
+def gather_u8_nchw(src_u8, params, H, W, out=None):
+    """out[b, c, i, j] = src_u8[idx_b, i, (flip_b ? W-1-j : j), c] / 255 (bit-equal to ToTensor).  src_u8 uint8 (n, H, W, 3),
+    params fp32 (B, 2) rows {index, flip} on the same device; an index outside [0, n) is clamped.  ``out``: a contiguous
+    fp32 (B, 3, H, W) tensor to write into (e.g. a captured step's static batch), else a new one."""
+    if not torch.is_tensor(src_u8) or not src_u8.is_cuda or src_u8.dtype != torch.uint8:
+        raise RuntimeError('contrad_hip: gather_u8_nchw: src must be a CUDA uint8 tensor (got %s, %s)' % (
+            getattr(src_u8, 'device', None), getattr(src_u8, 'dtype', type(src_u8))))
+    H, W = int(H), int(W)
+    if src_u8.dim() != 4 or tuple(src_u8.shape[1:]) != (H, W, 3) or not src_u8.is_contiguous() or src_u8.shape[0] == 0 \
+            or H <= 0 or W <= 0:
+        raise RuntimeError('contrad_hip: gather_u8_nchw: src must be a contiguous non-empty (n, %d, %d, 3) tensor, got %s' % (
+            H, W, tuple(src_u8.shape)))
+    n = src_u8.shape[0]
+    if n >= GATHER_MAX_N:
+        raise NotImplementedError('gather_u8_nchw hands the indices over as floats: fewer than 2^24 images (got %d)' % n)
+    _chk(params, 'params')
+    if params.dim() != 2 or params.shape[1] != 2 or params.shape[0] == 0 or not params.is_contiguous() \
+            or params.device != src_u8.device:
+        raise RuntimeError('contrad_hip: gather_u8_nchw: params must be a contiguous non-empty (B, 2) tensor on %s, got %s on %s'
+                           % (src_u8.device, tuple(params.shape), params.device))
+    B = params.shape[0]
+    if out is None:
+        out = torch.empty((B, 3, H, W), device=src_u8.device, dtype=torch.float32)
+    _chk(out, 'out')
+    if tuple(out.shape) != (B, 3, H, W) or not out.is_contiguous() or out.device != src_u8.device:
+        raise RuntimeError('contrad_hip: gather_u8_nchw: out must be a contiguous (%d, 3, %d, %d) tensor on %s' % (
+            B, H, W, src_u8.device))
+    lib().call('contrad_gather_u8_nchw', _p(src_u8), _p(params), _p(out), B, n, H, W, _stream())
+    return out

@@ -6,8 +6,10 @@ ordering (train_gan.py:141-179: warm-up, set_grad toggling, D-step, G-step), sam
 Differences by design: data parallelism is ``contrad_amd.engine`` (packed RCCL embedding all-gather inside the loss,
 flat gradient all-reduce folded into the fused Adam) instead of DistributedDataParallel; the per-step ``dist.barrier()``
 of the reference (:227) is dropped (the all-reduce already synchronises); FID / GIF / tensorboard side paths are out
-of scope -- losses are logged to stdout / log.txt.  Datasets: ``--synthetic`` (default when
-torchvision is absent) feeds uniform-random CIFAR-shaped batches; otherwise torchvision CIFAR-10/100 as the reference.
+of scope -- losses are logged to stdout / log.txt.  Datasets: ``--data FILE.npz`` keeps the uint8
+training set on the device and gathers every batch there (contrad_amd/data.py: the reference's sampler order, ToTensor's
+pixels, no torchvision); ``--synthetic`` (default when neither it nor torchvision is there) feeds uniform-random
+CIFAR-shaped batches; otherwise torchvision CIFAR-10/100 as the reference.
 """
 import functools
 import os
@@ -21,6 +23,7 @@ import torch.distributed as dist
 
 from . import config, engine
 from .augment import get_augment
+from .data import loader_for
 from .engine import GradAllReducer, GraphedDStep, GraphedGStep, OverlappedGradReducer, sample_generator, set_grad
 from .hostio import THROTTLE
 from .models.gan import get_architecture
@@ -61,6 +64,9 @@ def parse_args(argv=None):
     parser.add_argument('--port', default=40404, type=int)
     # additions
     parser.add_argument('--synthetic', action='store_true', help='uniform-random images instead of a dataset')
+    parser.add_argument('--data', default=None, type=str,
+                        help='npz with x_train uint8 [n, H, W, 3] (tools/make_image_npz.py): the set lives on the device, batches '
+                             'are gathered there (contrad_amd/data.py; no torchvision)')
     parser.add_argument('--max_steps', default=None, type=int, help='override options.max_steps')
     parser.add_argument('--logdir', default=None, type=str)
     parser.add_argument('--seed', default=0, type=int)
@@ -235,14 +241,21 @@ def main(argv=None):
         else:
             reducers = (reducers[0], GradAllReducer(D.parameters()))
     use_synth = P.synthetic
-    if not use_synth:
+    if not use_synth and not P.data:
         try:
             import torchvision  # noqa: F401
         except ImportError:
-            log('torchvision not available -> --synthetic')
+            log('torchvision not available -> --synthetic (--data FILE.npz trains on real images without it)')
             use_synth = True
-    loader = _synthetic_loader(options['batch_size'], image_size, dev, P.seed + rank) if use_synth else \
-        _dataset_loader(options['dataset'], options['batch_size'], rank, world, P.workers)
+    if P.data and not use_synth:
+        # a captured step has ONE batch size (GraphedDStep.load_images copies into a fixed buffer)
+        drop_last = bool(P.graph and P.mode == 'contrad')
+        if drop_last:
+            log("--graph: one captured batch size -> the loader drops each epoch's last partial batch")
+        loader = loader_for(P.data, options['dataset'], image_size, options['batch_size'], rank, world, drop_last, dev)
+    else:
+        loader = _synthetic_loader(options['batch_size'], image_size, dev, P.seed + rank) if use_synth else \
+            _dataset_loader(options['dataset'], options['batch_size'], rank, world, P.workers)
     log(f"# Params - G: {sum(p.numel() for p in G.parameters())}, D: {sum(p.numel() for p in D.parameters())}")
     log(str(options))
 

@@ -29,6 +29,7 @@ import torch.distributed as dist
 
 from . import config, engine, ops
 from .augment import get_augment
+from .data import loader_for
 from .engine import (GradAllReducer, GraphedSG2DStep, GraphedSG2GStep, _sg2_fakes, loss_D_fn_separate, r1_loss, set_grad,
                      setup_grad_exchange)
 from .hostio import THROTTLE
@@ -77,6 +78,9 @@ def parse_args(argv=None, contrad_script=False):
     # additions
     parser.add_argument('--port', default=40405, type=int)
     parser.add_argument('--synthetic', action='store_true', help='uniform-random images instead of a dataset')
+    parser.add_argument('--data', default=None, type=str,
+                        help='npz with x_train uint8 [n, H, W, 3] (tools/make_image_npz.py): the set lives on the device, batches '
+                             'are gathered there (contrad_amd/data.py; no torchvision)')
     parser.add_argument('--max_steps', default=None, type=int, help='override options.max_steps')
     parser.add_argument('--batch_size', default=None, type=int, help='override options.batch_size (global)')
     parser.add_argument('--logdir', default=None, type=str)
@@ -366,14 +370,17 @@ def main(argv=None, contrad_script=False):
     if world > 1:
         reducers = (GradAllReducer(G.parameters()), setup_grad_exchange(D))      # D: weights exchanged inside the backward
     use_synth = P.synthetic
-    if not use_synth:
+    if not use_synth and not P.data:
         try:
             import torchvision  # noqa: F401
         except ImportError:
-            log('torchvision not available -> --synthetic')
+            log('torchvision not available -> --synthetic (--data FILE.npz trains on real images without it)')
             use_synth = True
-    loader = _synthetic_loader(options['batch_size'], image_size, dev, P.seed + rank) if use_synth else \
-        _dataset_loader(options['dataset'], options['batch_size'], rank, world, P.workers)
+    if P.data and not use_synth:
+        loader = loader_for(P.data, options['dataset'], image_size, options['batch_size'], rank, world, True, dev)
+    else:
+        loader = _synthetic_loader(options['batch_size'], image_size, dev, P.seed + rank) if use_synth else \
+            _dataset_loader(options['dataset'], options['batch_size'], rank, world, P.workers)
     log(f"# Params - G: {sum(p.numel() for p in G.parameters())}, D: {sum(p.numel() for p in D.parameters())}")
     log(str(options))
     log(f"Use G moving average: {P.accum}")

@@ -690,6 +690,16 @@ long long contrad_gp_penalty_workspace_bytes(int N, long long chw);
 int contrad_gp_penalty(const float* grad, float* norms, float* out1, float* cot, int N, long long chw, float lbd,
                        float* workspace, long long workspace_bytes, contrad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Real-image batches (csrc/data.hip): gather, flip, NHWC -> NCHW and ToTensor in one launch.
+ * ---------------------------------------------------------------------------------------------- */
+/* dst[b, c, i, j] = (float) src[idx_b, i, (flip_b ? W-1-j : j), c] / 255.0f (correctly rounded: bit-equal to
+ * x.float().div(255)).  src uint8 (n, H, W, 3); params (B, 2) fp32 rows {index, flip}: the index is clamped to [0, n)
+ * (NaN -> 0), flip != 0 mirrors the row; dst fp32 (B, 3, H, W), 4-byte aligned.  n <= 2^24 (indices are floats).
+ * 16-byte stores / dword loads where the addresses allow, scalar head and tail of a row otherwise; bitwise repeatable. */
+int contrad_gather_u8_nchw(const unsigned char* src, const float* params, float* dst, int B, int n, int H, int W,
+                           contrad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
