@@ -114,21 +114,71 @@ def to_uint8(x):
     return x.mul(255.0).add_(0.5).clamp_(0, 255).to(torch.uint8)
 
 
+def _png_chunk(tag, data):
+    import struct
+    import zlib
+    return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
+
+
+def _png_rows(img, who):
+    """(height, width, the filter-type-0 scanlines) of a uint8 (H, W, 3) array."""
+    import numpy as np
+    img = np.ascontiguousarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError('%s: uint8 (H, W, 3) expected, got %s %s' % (who, img.dtype, img.shape))
+    h, w, _ = img.shape
+    return h, w, np.concatenate([np.zeros((h, 1), np.uint8), img.reshape(h, w * 3)], axis=1).tobytes()
+
+
 def png_bytes(img):
     """An 8-bit RGB PNG (one IDAT chunk, filter type 0 on every row) of a uint8 (H, W, 3) array."""
     import struct
     import zlib
-    import numpy as np
-    img = np.ascontiguousarray(img)
-    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
-        raise ValueError('png_bytes: uint8 (H, W, 3) expected, got %s %s' % (img.dtype, img.shape))
-    h, w, _ = img.shape
-    raw = np.concatenate([np.zeros((h, 1), np.uint8), img.reshape(h, w * 3)], axis=1).tobytes()
+    h, w, raw = _png_rows(img, 'png_bytes')
+    return (b'\x89PNG\r\n\x1a\n' + _png_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0))
+            + _png_chunk(b'IDAT', zlib.compress(raw, 6)) + _png_chunk(b'IEND', b''))
 
-    def chunk(tag, data):
-        return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
-    return (b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0))
-            + chunk(b'IDAT', zlib.compress(raw, 6)) + chunk(b'IEND', b''))
+
+def apng_bytes(frames, delay_ms=500, deflated=None):
+    """An animated PNG (APNG 1.0: ``acTL``, then ``fcTL`` + ``IDAT`` for the first frame and ``fcTL`` + ``fdAT`` for every
+    later one, one sequence-number series over the fcTL / fdAT chunks) of uint8 (H, W, 3) arrays of one size, each shown for
+    ``delay_ms``, looping forever.  The first frame is the still image a plain PNG reader shows.  ``deflated``: a list the
+    caller keeps between calls with a growing ``frames`` -- it holds the compressed scanlines of the frames seen so far,
+    so that rewriting a training run's animation deflates only the new frames."""
+    import struct
+    import zlib
+    frames = list(frames)
+    if not frames:
+        raise ValueError('apng_bytes: at least one frame')
+    if not 0 < int(delay_ms) < 65536:
+        raise ValueError('apng_bytes: delay_ms in [1, 65535], got %r' % (delay_ms,))
+    cache = deflated if deflated is not None else []
+    size = None
+    for i, f in enumerate(frames):
+        if i < len(cache):
+            h, w = f.shape[0], f.shape[1]
+        else:
+            h, w, raw = _png_rows(f, 'apng_bytes')
+            cache.append(zlib.compress(raw, 6))
+        if size is None:
+            size = (h, w)
+        elif size != (h, w):
+            raise ValueError('apng_bytes: frame %d is %s, frame 0 is %s' % (i, (h, w), size))
+    h, w = size
+    out = [b'\x89PNG\r\n\x1a\n', _png_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0)),
+           _png_chunk(b'acTL', struct.pack('>II', len(frames), 0))]
+    seq = 0
+    for i in range(len(frames)):
+        # full-canvas frame at (0, 0), delay_ms / 1000 s, dispose: none, blend: source
+        out.append(_png_chunk(b'fcTL', struct.pack('>IIIIIHHBB', seq, w, h, 0, 0, int(delay_ms), 1000, 0, 0)))
+        seq += 1
+        if i == 0:
+            out.append(_png_chunk(b'IDAT', cache[0]))
+        else:
+            out.append(_png_chunk(b'fdAT', struct.pack('>I', seq) + cache[i]))
+            seq += 1
+    out.append(_png_chunk(b'IEND', b''))
+    return b''.join(out)
 
 
 def write_png(path, img):

@@ -1429,3 +1429,54 @@ def gather_u8_nchw(src_u8, params, H, W, out=None):
             B, H, W, src_u8.device))
     lib().call('contrad_gather_u8_nchw', _p(src_u8), _p(params), _p(out), B, n, H, W, _stream())
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# images for the host (csrc/imagegrid.hip): float NCHW -> uint8 HWC grid canvas / uint8 NHWC batch in one launch
+# --------------------------------------------------------------------------------------------------
+def _chk_images(images, who):
+    if not torch.is_tensor(images) or not images.is_cuda or images.dtype != torch.float32:
+        raise RuntimeError('contrad_hip: %s: images must be a CUDA float32 tensor (got %s, %s)' % (
+            who, getattr(images, 'device', None), getattr(images, 'dtype', type(images))))
+    if images.dim() != 4 or images.shape[1] != 3 or images.numel() == 0 or not images.is_contiguous():
+        raise RuntimeError('contrad_hip: %s: images must be a contiguous non-empty (n, 3, H, W) tensor, got %s with strides %s'
+                           % (who, tuple(images.shape), tuple(images.stride())))
+
+
+def grid_canvas_shape(n, H, W, nrow=8, padding=2):
+    """(rows, columns, 3) of make_grid's canvas for n images of H x W: xmaps = min(nrow, n) cells per row."""
+    xmaps = min(int(nrow), int(n))
+    ymaps = -(-int(n) // xmaps)
+    return ymaps * (H + padding) + padding, xmaps * (W + padding) + padding, 3
+
+
+def image_grid_u8(images, nrow=8, padding=2, pad_value=0.0, out=None):
+    """torchvision's ``make_grid(images, nrow, padding, pad_value=pad_value)`` followed by ``save_image``'s quantisation
+    (x * 255 + 0.5, clamped to [0, 255], truncated; NaN -> 0) as ONE launch: fp32 (n, 3, H, W) -> uint8 canvas
+    [ymaps * (H + padding) + padding, xmaps * (W + padding) + padding, 3] on the same device.  (A single image is padded
+    like any other batch; torchvision returns it unframed.)  ``out``: a contiguous uint8 CUDA tensor of the canvas shape
+    with a 4-byte aligned base to write into, else a new one."""
+    _chk_images(images, 'image_grid_u8')
+    nrow, padding = int(nrow), int(padding)
+    if nrow <= 0 or padding < 0:
+        raise ValueError('image_grid_u8: nrow > 0 and padding >= 0 expected, got %d, %d' % (nrow, padding))
+    n, _, H, W = images.shape
+    shape = grid_canvas_shape(n, H, W, nrow, padding)
+    if out is None:
+        out = torch.empty(shape, device=images.device, dtype=torch.uint8)
+    elif not torch.is_tensor(out) or out.dtype != torch.uint8 or out.device != images.device or tuple(out.shape) != shape \
+            or not out.is_contiguous() or out.data_ptr() % 4:
+        raise RuntimeError('contrad_hip: image_grid_u8: out must be a contiguous 4-byte aligned uint8 %s tensor on %s' % (
+            shape, images.device))
+    lib().call('contrad_image_grid_u8', _p(images), _p(out), n, H, W, min(nrow, n), padding, float(pad_value), _stream())
+    return out
+
+
+def images_u8(images):
+    """fp32 (n, 3, H, W) -> uint8 (n, H, W, 3), quantised as ``hostio.to_uint8``: the grid kernel with one cell per row and
+    no padding."""
+    _chk_images(images, 'images_u8')
+    n, _, H, W = images.shape
+    out = torch.empty((n, H, W, 3), device=images.device, dtype=torch.uint8)
+    lib().call('contrad_image_grid_u8', _p(images), _p(out), n, H, W, 1, 0, 0.0, _stream())
+    return out

@@ -6,7 +6,8 @@ ordering (train_gan.py:141-179: warm-up, set_grad toggling, D-step, G-step), sam
 Differences by design: data parallelism is ``contrad_amd.engine`` (packed RCCL embedding all-gather inside the loss,
 flat gradient all-reduce folded into the fused Adam) instead of DistributedDataParallel; the per-step ``dist.barrier()``
 of the reference (:227) is dropped (the all-reduce already synchronises); FID / GIF / tensorboard side paths are out
-of scope -- losses are logged to stdout / log.txt.  Datasets: ``--data FILE.npz`` keeps the uint8
+of scope -- losses are logged to stdout / log.txt; ``--monitor`` writes the reference's fixed-latent
+and augmented-real image grids as PNG / animated PNG (contrad_amd/evaluate/gan.py; off by default).  Datasets: ``--data FILE.npz`` keeps the uint8
 training set on the device and gathers every batch there (contrad_amd/data.py: the reference's sampler order, ToTensor's
 pixels, no torchvision); ``--synthetic`` (default when neither it nor torchvision is there) feeds uniform-random
 CIFAR-shaped batches; otherwise torchvision CIFAR-10/100 as the reference.
@@ -24,6 +25,7 @@ import torch.distributed as dist
 from . import config, engine
 from .augment import get_augment
 from .data import loader_for
+from .evaluate.gan import LastBatch, Monitor
 from .engine import GradAllReducer, GraphedDStep, GraphedGStep, OverlappedGradReducer, sample_generator, set_grad
 from .hostio import THROTTLE
 from .models.gan import get_architecture
@@ -48,7 +50,8 @@ def parse_args(argv=None):
     # train_gan.py:55-60: FID / GIF logging is outside the hot path (out of scope) -- the flags are accepted
     # so that the reference's command lines run unchanged
     parser.add_argument('--no_fid', action='store_true', help='accepted for CLI compatibility (FIDs are never tracked here)')
-    parser.add_argument('--no_gif', action='store_true', help='accepted for CLI compatibility (no GIFs are written here)')
+    parser.add_argument('--no_gif', action='store_true', help='with --monitor: keep only the latest fixed-latent grid (fixed_gen_<seed>.png), no '
+                             'per-step files and no animation; without --monitor accepted and ignored')
     parser.add_argument('--n_eval_avg', default=3, type=int, help='accepted for CLI compatibility')
     parser.add_argument('--print_every', default=50, type=int)
     parser.add_argument('--evaluate_every', default=2000, type=int, help='checkpoint period (steps)')
@@ -72,6 +75,9 @@ def parse_args(argv=None):
     parser.add_argument('--seed', default=0, type=int)
     parser.add_argument('--graph', action='store_true',
                         help='replay the D- and G-step from captured hipGraphs (simclr pipeline; with several ranks the RCCL collectives are captured too)')
+    parser.add_argument('--monitor', action='store_true',
+                        help='rank 0 writes image grids at every evaluate_every: progress_<seed>/step_<step>.png and the animated '
+                             'training_progress_<seed>.png (fixed latents), real_augment_<seed>.png; the training trajectory is unchanged')
     return parser.parse_args(argv)
 
 
@@ -259,6 +265,10 @@ def main(argv=None):
     log(f"# Params - G: {sum(p.numel() for p in G.parameters())}, D: {sum(p.numel() for p in D.parameters())}")
     log(str(options))
 
+    monitor = None
+    if P.monitor and rank == 0:
+        monitor = Monitor(logdir, P.architecture, image_size, dev, P.seed, no_gif=P.no_gif, P=P)
+        loader = LastBatch(loader)                                          # the preview shows the batch the step drew
     graphed = None
     if P.graph:
         if P.mode != 'contrad':
@@ -275,6 +285,8 @@ def main(argv=None):
                  P.print_every * options['batch_size'] * world / max(time.time() - t0, 1e-9)))
             t0 = time.time()
         if step % P.evaluate_every == 0 and rank == 0:
+            if monitor is not None:
+                monitor.update(step, G, loader.last, P.augment_fn)
             torch.save(G.state_dict(), logdir + '/gen.pt')
             torch.save(D.state_dict(), logdir + '/dis.pt')
             if step % P.save_every == 0:

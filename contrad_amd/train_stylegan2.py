@@ -15,7 +15,8 @@ The reference parallelises the second one with ``nn.DataParallel(G_D)`` (paramet
 gathered on GPU 0).  Here both are one process per GPU: per-rank batch = batch_size / world, the embeddings travel in
 ONE packed RCCL all-gather inside the loss, parameter gradients in flat all-reduces folded into the fused Adam -- the
 global loss of the DataParallel formulation, without the per-step parameter broadcast.
-FID / GIF / tensorboard side paths are out of scope.
+FID / GIF / tensorboard side paths are out of scope; ``--monitor`` writes the reference's image
+grids from ``g_ema`` as PNG / animated PNG (contrad_amd/evaluate/gan.py; off by default).
 """
 import functools
 import os
@@ -30,6 +31,7 @@ import torch.distributed as dist
 from . import config, engine, ops
 from .augment import get_augment
 from .data import loader_for
+from .evaluate.gan import LastBatch, Monitor
 from .engine import (GradAllReducer, GraphedSG2DStep, GraphedSG2GStep, _sg2_fakes, loss_D_fn_separate, r1_loss, set_grad,
                      setup_grad_exchange)
 from .hostio import THROTTLE
@@ -67,7 +69,8 @@ def parse_args(argv=None, contrad_script=False):
     parser.add_argument('--ema_start_k', default=None, type=int)
     parser.add_argument('--halflife_lr', default=0, type=int)
     parser.add_argument('--no_fid', action='store_true')
-    parser.add_argument('--no_gif', action='store_true')
+    parser.add_argument('--no_gif', action='store_true', help='with --monitor: keep only the latest fixed-latent grid (fixed_gen_<seed>.png), no '
+                             'per-step files and no animation; without --monitor accepted and ignored')
     parser.add_argument('--n_eval_avg', default=3, type=int)
     parser.add_argument('--print_every', default=50, type=int)
     parser.add_argument('--evaluate_every', default=2000, type=int, help='checkpoint period (steps)')
@@ -88,6 +91,10 @@ def parse_args(argv=None, contrad_script=False):
     parser.add_argument('--graph', action='store_true',
                         help='replay the D- and G-step from captured hipGraphs (collectives included; the ContraD script, whose '
                              'D-step draws its own fakes)')
+    parser.add_argument('--monitor', action='store_true',
+                        help='rank 0 writes image grids at every evaluate_every: progress_<seed>/step_<step>.png and the animated '
+                             'training_progress_<seed>.png (g_ema at fixed latents), real_augment_<seed>.png; the training trajectory is '
+                             'unchanged')
     return parser.parse_args(argv)
 
 
@@ -385,6 +392,10 @@ def main(argv=None, contrad_script=False):
     log(str(options))
     log(f"Use G moving average: {P.accum}")
 
+    monitor = None
+    if P.monitor and rank == 0:
+        monitor = Monitor(logdir, P.architecture, image_size, dev, P.seed, no_gif=P.no_gif, P=P)
+        loader = LastBatch(loader)                                  # the preview shows the batch the step drew
     graphed = None
     if P.graph:
         if not contrad_script:
@@ -408,6 +419,8 @@ def main(argv=None, contrad_script=False):
                  P.print_every * options['global_batch_size'] / max(time.time() - t0, 1e-9)))
             t0 = time.time()
         if step % P.evaluate_every == 0 and rank == 0:
+            if monitor is not None:
+                monitor.update(step, g_ema, loader.last, P.augment_fn)
             torch.save(G.state_dict(), logdir + '/gen.pt')
             torch.save(D.state_dict(), logdir + '/dis.pt')
             torch.save(g_ema.state_dict(), logdir + '/gen_ema.pt')

@@ -700,6 +700,18 @@ int contrad_gp_penalty(const float* grad, float* norms, float* out1, float* cot,
 int contrad_gather_u8_nchw(const unsigned char* src, const float* params, float* dst, int B, int n, int H, int W,
                            contrad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Images for the host (csrc/imagegrid.hip): float NCHW -> uint8 HWC canvas in one launch.
+ * ---------------------------------------------------------------------------------------------- */
+/* torchvision's make_grid followed by save_image's quantisation.  src fp32 (n, 3, H, W); dst uint8
+ * [ymaps * (H + pad) + pad, xmaps * (W + pad) + pad, 3] with ymaps = ceil(n / xmaps): image k starts at row
+ * pad + (k / xmaps) * (H + pad), column pad + (k % xmaps) * (W + pad); every other pixel holds pad_value.  Every value is
+ * written as trunc(clamp(v * 255 + 0.5, 0, 255)), multiply and add rounded separately (bit-equal to
+ * v.mul(255).add_(0.5).clamp_(0, 255).to(uint8)); NaN -> 0.  pad = 0, xmaps = 1: the uint8 (n, H, W, 3) batch.
+ * src and dst 4-byte aligned.  Every byte is written once; bitwise repeatable. */
+int contrad_image_grid_u8(const float* src, unsigned char* dst, int n, int H, int W, int xmaps, int pad, float pad_value,
+                          contrad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
