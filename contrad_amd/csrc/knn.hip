@@ -1,0 +1,212 @@
+// Weighted k-nearest-neighbour vote on a similarity matrix (gfx950): per query row the top k columns, their class
+// vote and the predicted class, in ONE launch, one 256-thread workgroup per row.  No float atomics; every output
+// element is written once and every float sum has a fixed order, so two calls are bitwise equal.
+//
+//   1. keys      a float becomes a 32-bit key whose unsigned order is the contract's order: NaN -> 0 (below every
+//                number), -0.0 -> +0.0, then the usual sign flip.  A neighbour is ranked by (key descending, column
+//                ascending), i.e. by the 64-bit word (key << 32 | ~column) descending.
+//   2. select    the k-th largest key by radix select, four 8-bit digits from the top: per digit an LDS histogram (one
+//                per wave, integer adds: the counts do not depend on the order of arrival) of the columns that match
+//                the digits fixed so far, a suffix sum over the 256 bins, the bin that holds the k-th place.
+//   3. compact   one ordered pass over the row (a thread takes 4 consecutive columns, a packed wave scan numbers them):
+//                every column above the threshold key and, in column order, the first k - count columns equal to it.
+//   4. sort      bitonic sort of the (at most 1024, padded to a power of two) 64-bit words in LDS.
+//   5. vote      idx / val out (val re-read from S: the very floats); labels and expf(val * inv_temp) staged in LDS;
+//                thread c adds the weights of class c in rank order; the block's argmax under the same key order.
+//
+// The row is read five times (four digits and the compaction) and never staged: the caller hands over chunks of S small
+// enough to be served from cache (contrad_amd/knn.py), and at n = 50 000 a row is 200 KB, beyond the LDS of a CU.
+#include "../../include/contrad_hip.h"
+#include "common.h"
+
+namespace {
+
+constexpr int KNN_THREADS = 256;
+constexpr int KNN_MAX_K = 1024;
+constexpr int KNN_MAX_C = 1024;
+constexpr unsigned KNN_CHUNK = 4 * KNN_THREADS;     // columns per round of the compaction
+
+__device__ __forceinline__ unsigned knn_key(float f) {
+  unsigned u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;   // NaN: below every number (the key of -inf is 0x007fffff)
+  if (u == 0x80000000u) u = 0u;                     // -0.0 == +0.0
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ unsigned long long knn_word(unsigned key, unsigned col) {
+  return ((unsigned long long)key << 32) | (unsigned long long)(0xffffffffu - col);
+}
+
+__global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(const float* __restrict__ S, long long ldS, int n,
+                                                                 const long long* __restrict__ labels, int C, int k,
+                                                                 int P, float inv_temp, int* __restrict__ idx,
+                                                                 float* __restrict__ val, float* __restrict__ scores,
+                                                                 int* __restrict__ pred) {
+  __shared__ unsigned hist[4][256];
+  __shared__ unsigned long long words[KNN_MAX_K];
+  __shared__ int lab_s[KNN_MAX_K];
+  __shared__ float w_s[KNN_MAX_K];
+  __shared__ unsigned wtot[2][4];
+  __shared__ unsigned sel[2];
+  __shared__ unsigned long long best[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const long long q = blockIdx.x;
+  const float* __restrict__ row = S + q * ldS;
+  const unsigned un = (unsigned)n;
+
+  // ---- 2. the k-th largest key: `prefix` after four digits; `krem` of the columns equal to it are neighbours ----
+  unsigned prefix = 0u, krem = (unsigned)k;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    const unsigned himask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
+    for (int i = tid; i < 4 * 256; i += KNN_THREADS) (&hist[0][0])[i] = 0u;
+    __syncthreads();
+    for (unsigned j = tid; j < un; j += KNN_THREADS) {
+      const unsigned key = knn_key(row[j]);
+      if ((key & himask) == prefix) atomicAdd(&hist[w][(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    const unsigned cnt = hist[0][tid] + hist[1][tid] + hist[2][tid] + hist[3][tid];   // thread t owns bin t
+    unsigned suf = cnt;                                                               // sum over the bins >= t of this wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned t = __shfl_down(suf, o, 64);
+      if (lane + o < 64) suf += t;
+    }
+    if (lane == 0) wtot[0][w] = suf;
+    __syncthreads();
+    unsigned above = suf - cnt;                                                       // columns in higher bins
+    for (int ww = w + 1; ww < 4; ++ww) above += wtot[0][ww];
+    if (above < krem && krem <= above + cnt) {                                        // exactly one bin
+      sel[0] = (unsigned)tid;
+      sel[1] = krem - above;
+    }
+    __syncthreads();
+    prefix |= sel[0] << shift;
+    krem = sel[1];
+  }
+  const unsigned T = prefix, cgt = (unsigned)k - krem;                                // cgt columns have a key above T
+
+  // ---- 3. ordered compaction: words[0, cgt) keys above T, words[cgt, k) the first krem columns equal to T ----
+  for (int r = k + tid; r < P; r += KNN_THREADS) words[r] = 0ull;                     // padding sorts last
+  unsigned base_g = 0u, base_e = 0u;
+  int buf = 0;
+  for (unsigned c0 = 0u; c0 < un; c0 += KNN_CHUNK, buf ^= 1) {
+    const unsigned j0 = c0 + 4u * tid;
+    unsigned key4[4];
+    unsigned g = 0u, e = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool in = j0 + i < un;
+      key4[i] = in ? knn_key(row[j0 + i]) : 0u;
+      g += (in && key4[i] > T) ? 1u : 0u;
+      e += (in && key4[i] == T) ? 1u : 0u;
+    }
+    const unsigned p = g | (e << 16);                  // both counts <= 1024 per round: the two scans share a word
+    unsigned inc = p;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned t = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += t;
+    }
+    if (lane == 63) wtot[buf][w] = inc;
+    __syncthreads();
+    unsigned off = inc - p, tot = 0u;
+    for (int ww = 0; ww < 4; ++ww) {
+      const unsigned t = wtot[buf][ww];
+      if (ww < w) off += t;
+      tot += t;
+    }
+    unsigned pg = base_g + (off & 0xffffu), pe = base_e + (off >> 16);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (j0 + i >= un) break;
+      if (key4[i] > T) {
+        words[pg++] = knn_word(key4[i], j0 + i);       // pg < cgt: exactly cgt columns lie above T
+      } else if (key4[i] == T) {
+        if (pe < krem) words[cgt + pe] = knn_word(key4[i], j0 + i);
+        ++pe;
+      }
+    }
+    base_g += tot & 0xffffu;
+    base_e += tot >> 16;
+    if (base_g >= cgt && base_e >= krem) break;        // (uniform) the k neighbours are complete
+  }
+
+  // ---- 4. bitonic sort, descending ----
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int t = tid; t < (P >> 1); t += KNN_THREADS) {
+        const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+        const bool desc = (i & size) == 0;
+        const unsigned long long a = words[i], b = words[j];
+        if ((a < b) == desc) {
+          words[i] = b;
+          words[j] = a;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- 5. outputs and the vote ----
+  for (int r = tid; r < k; r += KNN_THREADS) {
+    unsigned j = 0xffffffffu - (unsigned)(words[r] & 0xffffffffull);
+    j = j < un ? j : un - 1u;                          // (always j < n; keeps every read inside the row regardless)
+    const float v = row[j];
+    idx[q * k + r] = (int)j;
+    val[q * k + r] = v;
+    const long long l = labels[j];
+    lab_s[r] = (l >= 0 && l < C) ? (int)l : -1;        // a label outside [0, C) votes for nobody
+    w_s[r] = expf(v * inv_temp);
+  }
+  __syncthreads();
+  unsigned long long mine = 0ull;
+  for (int c = tid; c < C; c += KNN_THREADS) {
+    float s = 0.f;
+    for (int r = 0; r < k; ++r)
+      if (lab_s[r] == c) s += w_s[r];
+    scores[q * C + c] = s;
+    const unsigned long long cand = knn_word(knn_key(s), (unsigned)c);
+    mine = cand > mine ? cand : mine;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long t = __shfl_xor(mine, o, 64);
+    mine = t > mine ? t : mine;
+  }
+  if (lane == 0) best[w] = mine;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long m = best[0];
+    for (int ww = 1; ww < 4; ++ww) m = best[ww] > m ? best[ww] : m;
+    pred[q] = (int)(0xffffffffu - (unsigned)(m & 0xffffffffull));
+  }
+}
+
+inline bool knn_shape_ok(int M, int n, int k, int C) {
+  return M >= 1 && n >= 1 && k >= 1 && k <= n && k <= KNN_MAX_K && C >= 1 && C <= KNN_MAX_C;
+}
+
+}  // namespace
+
+extern "C" long long contrad_knn_select_workspace_bytes(int M, int n, int k, int C) {
+  if (!knn_shape_ok(M, n, k, C)) return -22;
+  return 0;                                            // this form keeps everything in LDS
+}
+
+extern "C" int contrad_knn_select(const float* S, long long ldS, int M, int n, const long long* labels, int C, int k,
+                                  float inv_temp, int* idx, float* val, float* scores, int* pred, void* workspace,
+                                  long long workspace_bytes, contrad_stream_t stream) {
+  CONTRAD_ARG(S && labels && idx && val && scores && pred);
+  CONTRAD_ARG(knn_shape_ok(M, n, k, C) && ldS >= n);
+  const long long need = contrad_knn_select_workspace_bytes(M, n, k, C);
+  CONTRAD_ARG(workspace_bytes >= need && (need == 0 || workspace != nullptr));
+  int P = 1;
+  while (P < k) P <<= 1;
+  hipLaunchKernelGGL(knn_select_kernel, dim3(M), dim3(KNN_THREADS), 0, (hipStream_t)stream, S, ldS, n, labels, C, k, P,
+                     inv_temp, idx, val, scores, pred);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}

@@ -1147,6 +1147,45 @@ def linhead_wgrad_sgd(feats, dlogits, weight=None, bias=None, lr=None, grad_weig
     return grad_weight, grad_bias
 
 
+# ---- weighted kNN vote (csrc/knn.hip) ----
+KNN_MAX_K = 1024
+KNN_MAX_CLASSES = 1024
+
+
+def knn_select(S, n, labels, n_classes, k, inv_temp):
+    """Per row of the similarity matrix ``S`` (M, ldS >= n; columns [0, n) are read) the k nearest of the n bank
+    columns and their weighted class vote.  ``labels``: int64 CUDA vector of the n bank labels.  Returns
+    (idx int32 (M, k), val (M, k), scores (M, n_classes), pred int32 (M,)): contrad_knn_select's contract
+    (include/contrad_hip.h)."""
+    _chk(S, 'S')
+    if S.dim() != 2 or S.shape[0] < 1:
+        raise RuntimeError('contrad_hip: S must be a non-empty (M, ldS) matrix')
+    M, ldS = S.shape[0], _ld(S)
+    n, C, k = int(n), int(n_classes), int(k)
+    if not 1 <= n <= S.shape[1]:
+        raise RuntimeError('contrad_hip: n = %d outside [1, %d] (the columns of S)' % (n, S.shape[1]))
+    if not 1 <= k <= min(n, KNN_MAX_K):
+        raise RuntimeError('contrad_hip: k = %d outside [1, min(n, %d)] with n = %d' % (k, KNN_MAX_K, n))
+    if not 1 <= C <= KNN_MAX_CLASSES:
+        raise RuntimeError('contrad_hip: n_classes = %d outside [1, %d]' % (C, KNN_MAX_CLASSES))
+    if not torch.is_tensor(labels) or not labels.is_cuda:
+        raise RuntimeError('contrad_hip: labels must be a CUDA int64 tensor')
+    _chk_labels(labels, n, C)
+    dev = S.device
+    idx = torch.empty((M, k), device=dev, dtype=torch.int32)
+    val = torch.empty((M, k), device=dev, dtype=torch.float32)
+    scores = torch.empty((M, C), device=dev, dtype=torch.float32)
+    pred = torch.empty((M,), device=dev, dtype=torch.int32)
+    nbytes = lib().raw('contrad_knn_select_workspace_bytes')(M, n, k, C)
+    if nbytes < 0:
+        raise RuntimeError('contrad_hip: bad kNN shape (%d)' % nbytes)
+    ws = _workspace(nbytes, dev) if nbytes > 0 else None
+    as_int = lambda t: ctypes.cast(_p(t), ctypes.POINTER(ctypes.c_int))        # (the header's int* maps to a typed pointer)
+    lib().call('contrad_knn_select', _p(S), ctypes.c_longlong(ldS), M, n, _p(labels), C, k, float(inv_temp), as_int(idx),
+               _p(val), _p(scores), as_int(pred), _p(ws), ctypes.c_longlong(nbytes), _stream())
+    return idx, val, scores, pred
+
+
 # ---- cDDLS sampling (csrc/cddls.hip) ----
 def _flat_f32(t, name):
     _chk(t, name)

@@ -7,7 +7,8 @@ Differences by design: data parallelism is ``contrad_amd.engine`` (packed RCCL e
 flat gradient all-reduce folded into the fused Adam) instead of DistributedDataParallel; the per-step ``dist.barrier()``
 of the reference (:227) is dropped (the all-reduce already synchronises); FID / GIF / tensorboard side paths are out
 of scope -- losses are logged to stdout / log.txt; ``--monitor`` writes the reference's fixed-latent
-and augmented-real image grids as PNG / animated PNG (contrad_amd/evaluate/gan.py; off by default).  Datasets: ``--data FILE.npz`` keeps the uint8
+and augmented-real image grids as PNG / animated PNG (contrad_amd/evaluate/gan.py; off by default).  ``--knn_data FILE.npz`` logs the weighted
+kNN accuracy of D's features at every evaluation (contrad_amd/knn.py; an addition, off by default).  Datasets: ``--data FILE.npz`` keeps the uint8
 training set on the device and gathers every batch there (contrad_amd/data.py: the reference's sampler order, ToTensor's
 pixels, no torchvision); ``--synthetic`` (default when neither it nor torchvision is there) feeds uniform-random
 CIFAR-shaped batches; otherwise torchvision CIFAR-10/100 as the reference.
@@ -26,6 +27,7 @@ from . import config, engine
 from .augment import get_augment
 from .data import loader_for
 from .evaluate.gan import LastBatch, Monitor
+from .knn import KNNMonitor, add_hook_arguments
 from .engine import GradAllReducer, GraphedDStep, GraphedGStep, OverlappedGradReducer, sample_generator, set_grad
 from .hostio import THROTTLE
 from .models.gan import get_architecture
@@ -78,6 +80,7 @@ def parse_args(argv=None):
     parser.add_argument('--monitor', action='store_true',
                         help='rank 0 writes image grids at every evaluate_every: progress_<seed>/step_<step>.png and the animated '
                              'training_progress_<seed>.png (fixed latents), real_augment_<seed>.png; the training trajectory is unchanged')
+    add_hook_arguments(parser)
     return parser.parse_args(argv)
 
 
@@ -269,6 +272,9 @@ def main(argv=None):
     if P.monitor and rank == 0:
         monitor = Monitor(logdir, P.architecture, image_size, dev, P.seed, no_gif=P.no_gif, P=P)
         loader = LastBatch(loader)                                          # the preview shows the batch the step drew
+    knn_monitor = None
+    if P.knn_data and rank == 0:
+        knn_monitor = KNNMonitor(logdir, P.architecture, image_size, dev, P.seed, P.knn_data, k=P.knn_k, temp=P.knn_temp, P=P)
     graphed = None
     if P.graph:
         if P.mode != 'contrad':
@@ -287,6 +293,8 @@ def main(argv=None):
         if step % P.evaluate_every == 0 and rank == 0:
             if monitor is not None:
                 monitor.update(step, G, loader.last, P.augment_fn)
+            if knn_monitor is not None:
+                log('[Steps %7d] [kNN Acc@1 %.3f]' % (step, knn_monitor.update(step, D)['acc@1']))
             torch.save(G.state_dict(), logdir + '/gen.pt')
             torch.save(D.state_dict(), logdir + '/dis.pt')
             if step % P.save_every == 0:

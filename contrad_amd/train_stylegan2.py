@@ -16,7 +16,8 @@ gathered on GPU 0).  Here both are one process per GPU: per-rank batch = batch_s
 ONE packed RCCL all-gather inside the loss, parameter gradients in flat all-reduces folded into the fused Adam -- the
 global loss of the DataParallel formulation, without the per-step parameter broadcast.
 FID / GIF / tensorboard side paths are out of scope; ``--monitor`` writes the reference's image
-grids from ``g_ema`` as PNG / animated PNG (contrad_amd/evaluate/gan.py; off by default).
+grids from ``g_ema`` as PNG / animated PNG (contrad_amd/evaluate/gan.py; off by default).  ``--knn_data FILE.npz`` logs the weighted kNN accuracy
+of D's features at every evaluation (contrad_amd/knn.py; an addition, off by default).
 """
 import functools
 import os
@@ -32,6 +33,7 @@ from . import config, engine, ops
 from .augment import get_augment
 from .data import loader_for
 from .evaluate.gan import LastBatch, Monitor
+from .knn import KNNMonitor, add_hook_arguments
 from .engine import (GradAllReducer, GraphedSG2DStep, GraphedSG2GStep, _sg2_fakes, loss_D_fn_separate, r1_loss, set_grad,
                      setup_grad_exchange)
 from .hostio import THROTTLE
@@ -95,6 +97,7 @@ def parse_args(argv=None, contrad_script=False):
                         help='rank 0 writes image grids at every evaluate_every: progress_<seed>/step_<step>.png and the animated '
                              'training_progress_<seed>.png (g_ema at fixed latents), real_augment_<seed>.png; the training trajectory is '
                              'unchanged')
+    add_hook_arguments(parser)
     return parser.parse_args(argv)
 
 
@@ -396,6 +399,9 @@ def main(argv=None, contrad_script=False):
     if P.monitor and rank == 0:
         monitor = Monitor(logdir, P.architecture, image_size, dev, P.seed, no_gif=P.no_gif, P=P)
         loader = LastBatch(loader)                                  # the preview shows the batch the step drew
+    knn_monitor = None
+    if P.knn_data and rank == 0:
+        knn_monitor = KNNMonitor(logdir, P.architecture, image_size, dev, P.seed, P.knn_data, k=P.knn_k, temp=P.knn_temp, P=P)
     graphed = None
     if P.graph:
         if not contrad_script:
@@ -421,6 +427,8 @@ def main(argv=None, contrad_script=False):
         if step % P.evaluate_every == 0 and rank == 0:
             if monitor is not None:
                 monitor.update(step, g_ema, loader.last, P.augment_fn)
+            if knn_monitor is not None:
+                log('[Steps %7d] [kNN Acc@1 %.3f]' % (step, knn_monitor.update(step, D)['acc@1']))
             torch.save(G.state_dict(), logdir + '/gen.pt')
             torch.save(D.state_dict(), logdir + '/dis.pt')
             torch.save(g_ema.state_dict(), logdir + '/gen_ema.pt')

@@ -712,6 +712,27 @@ int contrad_gather_u8_nchw(const unsigned char* src, const float* params, float*
 int contrad_image_grid_u8(const float* src, unsigned char* dst, int n, int H, int W, int xmaps, int pad, float pad_value,
                           contrad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Weighted k-nearest-neighbour vote (csrc/knn.hip): top k per row of a similarity matrix, class scores, prediction.
+ * An addition of this project (the reference has no kNN evaluator): the probe of Wu et al. 2018 on frozen features.
+ * ---------------------------------------------------------------------------------------------- */
+/* Bytes of the workspace of contrad_knn_select (0: this form keeps its state in LDS, workspace may then be NULL);
+ * < 0 on bad arguments. */
+long long contrad_knn_select_workspace_bytes(int M, int n, int k, int C);
+/* For every row i of S[M][ldS] (only columns [0, n) are read; labels[n] int64):
+ *   neighbours   the first k columns under the total order "value descending, then column ascending"; -0.0 and +0.0
+ *                compare equal, NaN compares below every number.  idx[i][0..k) and val[i][0..k) in that order, val the
+ *                very floats of S.
+ *   scores[i][c] = sum_r [labels[idx[i][r]] == c] * expf(val[i][r] * inv_temp), fp32, added in rank order r = 0..k-1.
+ *   pred[i]      the class of the largest score (same order: a NaN score is below every number), the lowest class on
+ *                an exact tie.
+ * A label outside [0, C) contributes to no score.  1 <= k <= min(n, 1024), 1 <= C <= 1024, ldS >= n; -EINVAL (before
+ * any GPU call) on a null pointer, a violated limit or a workspace smaller than contrad_knn_select_workspace_bytes.
+ * One launch; no float atomics; every output element is written once; two calls are bitwise equal. */
+int contrad_knn_select(const float* S, long long ldS, int M, int n, const long long* labels, int C, int k,
+                       float inv_temp, int* idx, float* val, float* scores, int* pred, void* workspace,
+                       long long workspace_bytes, contrad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
