@@ -310,7 +310,7 @@ def load_networks(logdir, linear_path, architecture, n_classes, dev):
     """(G, D, head weight, head bias) from ``gen_best.pt`` / ``dis_best.pt`` in ``logdir`` and the lin-eval checkpoint."""
     from .lineval import _dataset_name
     from .models.gan import get_architecture
-    from .train_gan import IMAGE_SIZES
+    from .data import TRAIN_GAN_IMAGE_SIZES as IMAGE_SIZES
     dataset = _dataset_name(logdir)
     if dataset is None:
         raise RuntimeError('%s holds no *.gin file naming the dataset' % logdir)

@@ -98,6 +98,14 @@ class DeviceLoader(object):
         return ops.gather_u8_nchw(self.x, upload(block, self.x.device), self.h, self.w), None
 
 
+# datasets.py:10,57,99,115,131 of the reference: dataset -> (H, W, C).  The training scripts drive subsets of it.
+IMAGE_SIZES = {'cifar10': (32, 32, 3), 'cifar100': (32, 32, 3), 'cifar10_hflip': (32, 32, 3),
+               'cifar100_hflip': (32, 32, 3), 'celeba128': (128, 128, 3), 'afhq_cat': (512, 512, 3),
+               'afhq_dog': (512, 512, 3), 'afhq_wild': (512, 512, 3)}
+# what train_gan drives (and the cDDLS sampler, on its checkpoints); the others run through the StyleGAN2 scripts
+TRAIN_GAN_IMAGE_SIZES = {k: IMAGE_SIZES[k] for k in ('cifar10', 'cifar100', 'cifar10_hflip')}
+
+
 def dataset_flips(name):
     """The dataset names whose reference transform has RandomHorizontalFlip (datasets.py: ``*_hflip``, ``afhq_*``)."""
     return name.endswith('hflip') or name.startswith('afhq_')

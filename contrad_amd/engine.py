@@ -1,5 +1,11 @@
-"""The discriminator step of the reference training loop (train_gan.py:153-163) as a reusable function, plus the
-data-parallel gradient exchange that replaces DistributedDataParallel's reducer (train_gan.py:311-313).
+"""The eager training steps of the reference loops as reusable functions, their captured twins, and the data-parallel
+gradient exchange that replaces DistributedDataParallel's reducer (train_gan.py:311-313).
+
+Eager steps: ``optimizer_step`` is the one tail every eager step ends in (zero_grad -> backward -> gradient exchange ->
+fused Adam; captured.CapturedTrainStep._finish is its captured counterpart), ``_d_step`` the one discriminator step
+(train_gan.py:153-163, train_stylegan2.py:199-212, train_stylegan2_contraD.py:148-164,218-226 differ in the loss, in
+where the fakes come from and in the lazy R1 term); the script loops' generator steps compute their loss and call the
+tail on G.
 
 Data parallelism: one process per GPU; each rank owns N_local real images, draws its own fakes and
 augmentation parameters; ONE packed RCCL all-gather of embeddings inside the loss (training/gan/contrad.py), then a
@@ -23,9 +29,6 @@ FORCE_DIST = False
 def dist_on():
     """True when this process is one rank of a multi-rank job (or the 1-rank test hook is set)."""
     return dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or FORCE_DIST)
-
-
-_dist_on = dist_on
 
 
 class GradAllReducer(object):
@@ -62,7 +65,7 @@ class GradAllReducer(object):
         return out
 
     def __call__(self):
-        if not _dist_on():
+        if not dist_on():
             return 1
         spans = self.spans()
         small = [t for t in spans if t.numel() < self.SMALL]
@@ -100,8 +103,7 @@ class OverlappedGradReducer(object):
         self.handles = []
 
     def active(self):
-        return _dist_on() or (dist.is_available() and dist.is_initialized() and getattr(self, 'force', False))
-
+        return dist_on() or (dist.is_available() and dist.is_initialized() and getattr(self, 'force', False))
 
     def reduce_async(self, t):
         if self.active():
@@ -129,26 +131,35 @@ def set_grad(model, flag=True):
         p.requires_grad = flag
 
 
-def d_step(P, G, D, opt_D, options, images, reducer=None):
-    """One discriminator step, exactly train_gan.py:153-163 (minus the four logging .item() syncs): fakes under
-    no_grad -> loss_D_fn -> zero_grad -> backward -> [gradient all-reduce] -> Adam.  Returns (d_loss, aux)."""
-    THROTTLE.begin()                          # host stays at most one step ahead of the GPU (hostio.py)
-    gen_images = sample_generator(G, images.size(0), enable_grad=False)
-    d_loss, aux = P.train_fn["D"](P, D, options, images, gen_images)
-    loss = d_loss + aux['penalty']
-    opt_D.zero_grad()
+def optimizer_step(opt, loss, net, reducer=None):
+    """The tail of every eager step: zero_grad -> backward -> [gradient all-reduce] -> fused Adam with the data-parallel
+    mean's 1/W as its grad_scale.  ``net``: the network ``opt`` updates; one that exchanged its gradients inside the
+    backward (``_grad_comm``, overlapped) only reports the world size, else ``reducer`` (or None) exchanges them now.
+    The eager counterpart of captured.CapturedTrainStep._finish."""
+    opt.zero_grad()
     loss.backward()
-    comm = getattr(D, '_grad_comm', None)
-    if comm is not None:                      # gradients were exchanged inside the backward (overlapped)
-        world = comm.world()
-    else:
-        world = reducer() if reducer is not None else 1
-    if world > 1:
-        opt_D.step(grad_scale=1.0 / world)
-    else:
-        opt_D.step()
+    comm = getattr(net, '_grad_comm', None)
+    world = comm.world() if comm is not None else (reducer() if reducer is not None else 1)
+    opt.step(grad_scale=1.0 / world) if world > 1 else opt.step()
+
+
+def _d_step(P, D, opt_D, options, images, loss_fn, draw_fakes, reducer, r1=False):
+    """The eager discriminator step: draw_fakes() -> loss_fn -> [R1 on its own D call] -> zero_grad -> backward ->
+    [gradient exchange] -> Adam.  Returns (d_loss, aux); aux['r1'] with ``r1``."""
+    THROTTLE.begin()                          # host stays at most one step ahead of the GPU (hostio.py)
+    d_loss, aux = loss_fn(P, D, options, images, draw_fakes())
+    loss = d_loss + aux['penalty']
+    if r1:
+        loss = _add_r1(P, D, images, loss, aux)
+    optimizer_step(opt_D, loss, D, reducer)
     THROTTLE.end()
     return d_loss, aux
+
+
+def d_step(P, G, D, opt_D, options, images, reducer=None):
+    """One discriminator step, exactly train_gan.py:153-163 (minus the four logging .item() syncs)."""
+    return _d_step(P, D, opt_D, options, images, loss_fn=P.train_fn["D"], reducer=reducer,
+                   draw_fakes=lambda: sample_generator(G, images.size(0), enable_grad=False))
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -174,24 +185,31 @@ def _sg2_fakes(G, N, style_mix):
     return G(G.sample_latent(N), style_mix=style_mix)
 
 
-def d_step_stylegan2(P, G, D, opt_D, options, images, step, reducer=None, style_mix=0.9):
+def _add_r1(P, D, images, loss, aux):
+    """loss + (0.5 * lbd_r1) * r1 * d_reg_every, the (lazy) R1 term of the StyleGAN2 D-steps, eager and captured, in one
+    launch (and one in the backward); the penalty itself goes into aux['r1']."""
+    aux['r1'] = r1_loss(D, images, P.augment_fn)
+    return torch.add(loss, aux['r1'], alpha=(0.5 * P.lbd_r1) * P.d_reg_every)
+
+
+def _sg2_d_step(loss_fn, P, G, D, opt_D, options, images, step, reducer, style_mix, fakes, r1):
+    """What the two StyleGAN2 D-steps share: the given fakes or fresh ones under no_grad, R1 when asked for and due."""
+    def draw_fakes():
+        if fakes is not None:
+            return fakes
+        with torch.no_grad():
+            return _sg2_fakes(G, images.size(0), style_mix)
+
+    return _d_step(P, D, opt_D, options, images, loss_fn=loss_fn, draw_fakes=draw_fakes, reducer=reducer,
+                   r1=r1 and (step % P.d_reg_every == 0) and P.lbd_r1 > 0)
+
+
+def d_step_stylegan2(P, G, D, opt_D, options, images, step, reducer=None, style_mix=0.9, *, fakes=None, r1=True):
     """D-step of train_stylegan2.py:199-212 (BASELINE config 4): single 3N-image D call via loss_D_fn, plus the
-    R1 penalty every ``P.d_reg_every`` steps weighted (0.5*lbd_r1)*r1*d_reg_every (``--no_lazy`` => every step)."""
-    THROTTLE.begin()
-    with torch.no_grad():
-        gen_images = _sg2_fakes(G, images.size(0), style_mix)
-    d_loss, aux = P.train_fn["D"](P, D, options, images, gen_images)
-    loss = d_loss + aux['penalty']
-    if (step % P.d_reg_every == 0) and P.lbd_r1 > 0:
-        r1 = r1_loss(D, images, P.augment_fn)
-        loss = torch.add(loss, r1, alpha=(0.5 * P.lbd_r1) * P.d_reg_every)      # one launch (and one in the backward)
-        aux['r1'] = r1
-    opt_D.zero_grad()
-    loss.backward()
-    world = reducer() if reducer is not None else 1
-    opt_D.step(grad_scale=1.0 / world) if world > 1 else opt_D.step()
-    THROTTLE.end()
-    return d_loss, aux
+    R1 penalty every ``P.d_reg_every`` steps weighted (0.5*lbd_r1)*r1*d_reg_every (``--no_lazy`` => every step).
+    ``fakes``: the generator step's (detached), as the script feeds them, instead of fresh ones; ``r1=False``: the extra
+    critic iterations, which carry no R1 term."""
+    return _sg2_d_step(P.train_fn["D"], P, G, D, opt_D, options, images, step, reducer, style_mix, fakes, r1)
 
 
 # One discriminator call over [two real views | fakes] with the minibatch-stddev groups kept inside each segment (True, the
@@ -232,25 +250,10 @@ def loss_D_fn_separate(P, D, options, images, gen_images):
     return simclr + P.lbd_a * sup, {'penalty': gan, 'd_real': d_real_m, 'd_gen': d_gen_m}
 
 
-def d_step_stylegan2_contrad(P, G, D, opt_D, options, images, step, reducer=None, style_mix=0.9):
+def d_step_stylegan2_contrad(P, G, D, opt_D, options, images, step, reducer=None, style_mix=0.9, *, fakes=None, r1=True):
     """D-step of train_stylegan2_contraD.py:148-164,218-226 (BASELINE config 5): loss_D_fn_separate + lazy R1 on
-    its own D call."""
-    N = images.size(0)
-    THROTTLE.begin()
-    with torch.no_grad():
-        gen_images = _sg2_fakes(G, N, style_mix)
-    d_loss, aux = loss_D_fn_separate(P, D, options, images, gen_images)
-    loss = d_loss + aux['penalty']
-    if (step % P.d_reg_every == 0) and P.lbd_r1 > 0:
-        r1 = r1_loss(D, images, P.augment_fn)
-        loss = torch.add(loss, r1, alpha=(0.5 * P.lbd_r1) * P.d_reg_every)      # one launch (and one in the backward)
-        aux['r1'] = r1
-    opt_D.zero_grad()
-    loss.backward()
-    world = reducer() if reducer is not None else 1
-    opt_D.step(grad_scale=1.0 / world) if world > 1 else opt_D.step()
-    THROTTLE.end()
-    return d_loss, aux
+    its own D call.  Options as d_step_stylegan2."""
+    return _sg2_d_step(loss_D_fn_separate, P, G, D, opt_D, options, images, step, reducer, style_mix, fakes, r1)
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -450,9 +453,7 @@ class GraphedSG2DStep(CapturedTrainStep):
             d_loss, aux = P.train_fn["D"](P, D, self.options, self.images, gen)
         loss = d_loss + aux['penalty']
         if self.r1_in_graph:
-            r1 = r1_loss(D, self.images, self.saug)
-            loss = torch.add(loss, r1, alpha=(0.5 * P.lbd_r1) * P.d_reg_every)     # (as the eager step)
-            aux['r1'] = r1
+            loss = _add_r1(P, D, self.images, loss, aux)        # (P is self.Pg: the static stand-in augments)
         return self._finish(loss, (d_loss, aux))
 
     def __call__(self, step):

@@ -42,7 +42,7 @@ def parse_args(argv=None):
 def image_size_of(logdir):
     """Image size of the dataset named by the first ``*.gin`` in ``logdir`` (as cddls.load_networks reads it)."""
     from .lineval import _dataset_name
-    from .train_stylegan2 import IMAGE_SIZES                       # (a superset of train_gan's)
+    from .data import IMAGE_SIZES
     dataset = _dataset_name(logdir)
     if dataset is None:
         raise RuntimeError('%s holds no *.gin file naming the dataset' % logdir)

@@ -12,75 +12,42 @@ kNN accuracy of D's features at every evaluation (contrad_amd/knn.py; an additio
 training set on the device and gathers every batch there (contrad_amd/data.py: the reference's sampler order, ToTensor's
 pixels, no torchvision); ``--synthetic`` (default when neither it nor torchvision is there) feeds uniform-random
 CIFAR-shaped batches; otherwise torchvision CIFAR-10/100 as the reference.
+
+This module holds what the script does differently from the StyleGAN2 ones (its flags, option defaults, warm-up, loaders,
+log directory and ``train_step``, which calls the eager steps of engine.py); everything else of ``main()`` is
+contrad_amd/train_driver.py.
 """
 import functools
 import os
-import time
-from argparse import ArgumentParser
-from pathlib import Path
 
-import numpy as np
 import torch
-import torch.distributed as dist
 
-from . import config, engine
-from .augment import get_augment
-from .data import loader_for
-from .evaluate.gan import LastBatch, Monitor
-from .knn import KNNMonitor, add_hook_arguments
-from .engine import GradAllReducer, GraphedDStep, GraphedGStep, OverlappedGradReducer, sample_generator, set_grad
+from . import config, engine, train_driver
+from .data import TRAIN_GAN_IMAGE_SIZES as IMAGE_SIZES
+from .engine import GraphedDStep, GraphedGStep, sample_generator, set_grad
 from .hostio import THROTTLE
-from .models.gan import get_architecture
-from .optim import FusedAdam
-from .training.gan import BASELINE_MODES, setup
-
-IMAGE_SIZES = {'cifar10': (32, 32, 3), 'cifar100': (32, 32, 3), 'cifar10_hflip': (32, 32, 3)}
 
 
 def parse_args(argv=None):
-    parser = ArgumentParser(description='Training script: ContraD on MI355X (one process per GPU).')
-    parser.add_argument('gin_config', type=str, help='Path to the gin configuration file')
-    parser.add_argument('architecture', type=str, help='Architecture')
-    parser.add_argument('--mode', default='std', type=str, help='Training mode (contrad | simclr_only | std | aug | aug_both)')
-    parser.add_argument('--penalty', default='none', type=str, help='none | cr | bcr | gp (std / aug / aug_both)')
-    parser.add_argument('--aug', default='none', type=str, help='Augmentation (simclr | simclr_hq | simclr_hq_cutout | none | hflip | hfrt | diffaug; diffaug needs a gin '
-                             'file that binds augment.diffaug_policy = "color,cutout", as configs/gan/diffaug/c10_diffaug.gin '
-                             'does: with any other file it raises NotImplementedError until the line is added)')
-    parser.add_argument('--use_warmup', action='store_true', help='Use warmup strategy on LR')
-    parser.add_argument('--temp', default=0.1, type=float)
-    parser.add_argument('--lbd_a', default=1.0, type=float)
-    # train_gan.py:55-60: FID / GIF logging is outside the hot path (SURVEY.md 8: out of scope) -- the flags are accepted
-    # so that the reference's command lines run unchanged
-    parser.add_argument('--no_fid', action='store_true', help='accepted for CLI compatibility (FIDs are never tracked here)')
-    parser.add_argument('--no_gif', action='store_true', help='with --monitor: keep only the latest fixed-latent grid (fixed_gen_<seed>.png), no '
-                             'per-step files and no animation; without --monitor accepted and ignored')
-    parser.add_argument('--n_eval_avg', default=3, type=int, help='accepted for CLI compatibility')
-    parser.add_argument('--print_every', default=50, type=int)
-    parser.add_argument('--evaluate_every', default=2000, type=int, help='checkpoint period (steps)')
-    parser.add_argument('--save_every', default=100000, type=int)
-    parser.add_argument('--comment', default='', type=str)
-    parser.add_argument('--resume', default=None, type=str)
-    parser.add_argument('--finetune', default=None, type=str)
-    parser.add_argument('--workers', default=0, type=int)
-    # train_gan.py:79-82 (NODE count / node rank of the reference's mp.spawn launch): accepted; this build is one process
-    # per GPU of ONE node and takes rank / world size from the launcher's environment (RANK / WORLD_SIZE)
-    parser.add_argument('--world-size', default=1, type=int, help='accepted for CLI compatibility (nodes; single-node build)')
-    parser.add_argument('--rank', default=0, type=int, help='accepted for CLI compatibility (node rank)')
-    parser.add_argument('--port', default=40404, type=int)
-    # additions
-    parser.add_argument('--synthetic', action='store_true', help='uniform-random images instead of a dataset')
-    parser.add_argument('--data', default=None, type=str,
-                        help='npz with x_train uint8 [n, H, W, 3] (tools/make_image_npz.py): the set lives on the device, batches '
-                             'are gathered there (contrad_amd/data.py; no torchvision)')
-    parser.add_argument('--max_steps', default=None, type=int, help='override options.max_steps')
-    parser.add_argument('--logdir', default=None, type=str)
-    parser.add_argument('--seed', default=0, type=int)
-    parser.add_argument('--graph', action='store_true',
-                        help='replay the D- and G-step from captured hipGraphs (simclr pipeline; with several ranks the RCCL collectives are captured too)')
-    parser.add_argument('--monitor', action='store_true',
-                        help='rank 0 writes image grids at every evaluate_every: progress_<seed>/step_<step>.png and the animated '
-                             'training_progress_<seed>.png (fixed latents), real_augment_<seed>.png; the training trajectory is unchanged')
-    add_hook_arguments(parser)
+    accepted = 'accepted for CLI compatibility'
+    parser = train_driver.make_parser('Training script: ContraD on MI355X (one process per GPU).', [
+        'gin_config', 'architecture', '--mode',
+        ('--penalty', dict(help='none | cr | bcr | gp (std / aug / aug_both)')),
+        '--aug', '--use_warmup', '--temp', '--lbd_a',
+        ('--no_fid', dict(help=accepted + ' (FIDs are never tracked here)')),
+        '--no_gif',
+        ('--n_eval_avg', dict(help=accepted)),
+        '--print_every', '--evaluate_every', '--save_every', '--comment', '--resume', '--finetune',
+        ('--workers', dict(default=0)),
+        # train_gan.py:79-82 (NODE count / node rank of the reference's mp.spawn launch): accepted; this build is one
+        # process per GPU of ONE node and takes rank / world size from the launcher's environment (RANK / WORLD_SIZE)
+        ('--world-size', dict(default=1, type=int, help=accepted + ' (nodes; single-node build)')),
+        ('--rank', dict(default=0, type=int, help=accepted + ' (node rank)')),
+        ('--port', dict(default=40404)),
+        '--synthetic', '--data', '--max_steps', '--logdir', '--seed',
+        ('--graph', dict(help='replay the D- and G-step from captured hipGraphs (simclr pipeline; with several ranks the '
+                              'RCCL collectives are captured too)')),
+        ('--monitor', dict(help=train_driver.monitor_help('fixed latents')))])
     return parser.parse_args(argv)
 
 
@@ -128,13 +95,15 @@ def _dataset_loader(name, batch, rank, world, workers):
         sampler.set_epoch(epoch)
 
 
+NOT_CONTRAD = "--graph captures the ContraD critic iteration (--mode contrad), not '%s'"
+
+
 class GraphedCritic(engine.GraphedCritic):
     """``--graph``: the critic iteration of ``train_step`` replayed from ONE captured hipGraph (engine.GraphedDStep) and
     the generator step from a second one (engine.GraphedGStep)."""
 
     def __init__(self):
-        super().__init__(functools.partial(GraphedDStep, warmup=0), GraphedGStep,
-                         "--graph captures the ContraD critic iteration (--mode contrad), not '%s'")
+        super().__init__(functools.partial(GraphedDStep, warmup=0), GraphedGStep, NOT_CONTRAD)
 
 
 def train_step(P, opt, G, D, opt_G, opt_D, loader, step, reducers, graphed=None):
@@ -151,26 +120,12 @@ def train_step(P, opt, G, D, opt_G, opt_D, loader, step, reducers, graphed=None)
     for _ in range(opt['n_critic']):
         images, _labels = next(loader)
         done = graphed(P, opt, G, D, opt_D, images) if graphed is not None else None
-        if done is not None:
-            d_loss, aux = done
-            continue
-        gen_images = sample_generator(G, images.size(0), enable_grad=False)
-        d_loss, aux = P.train_fn["D"](P, D, opt, images, gen_images)
-        loss = d_loss + aux['penalty']
-        opt_D.zero_grad()
-        loss.backward()
-        comm = getattr(D, '_grad_comm', None)
-        world = comm.world() if comm is not None else (red_D() if red_D is not None else 1)
-        opt_D.step(grad_scale=1.0 / world) if world > 1 else opt_D.step()
+        d_loss, aux = done if done is not None else engine.d_step(P, G, D, opt_D, opt, images, red_D)
     set_grad(G, True); set_grad(D, False)
     g_loss = graphed.generator(P, opt, G, D, opt_G, images) if graphed is not None else None
     if g_loss is None:
-        gen_images = sample_generator(G, images.size(0))
-        g_loss = P.train_fn["G"](P, D, opt, images, gen_images)
-        opt_G.zero_grad()
-        g_loss.backward()
-        world = red_G() if red_G is not None else 1
-        opt_G.step(grad_scale=1.0 / world) if world > 1 else opt_G.step()
+        g_loss = P.train_fn["G"](P, D, opt, images, sample_generator(G, images.size(0)))
+        engine.optimizer_step(opt_G, g_loss, G, red_G)
     THROTTLE.end()
     # detached: a loss that keeps last iteration's autograd graph (and its AccumulateGrad nodes) alive would tie the next
     # D-step to the stream that graph ran on -- which breaks a hipGraph capture
@@ -178,133 +133,21 @@ def train_step(P, opt, G, D, opt_G, opt_D, loader, step, reducers, graphed=None)
             'D_real': aux['d_real'].detach(), 'D_gen': aux['d_gen'].detach()}
 
 
+def _logdir(P):
+    return f'logs/gan/{P.gin_stem}/{P.architecture}/{P.filename}{P.comment}'
+
+
+SCRIPT = train_driver.Script(
+    get_options=get_options_dict, image_sizes=IMAGE_SIZES, logdir=_logdir, synthetic_loader=_synthetic_loader,
+    dataset_loader=_dataset_loader, make_critic=GraphedCritic, not_contrad=NOT_CONTRAD, data_keeps_partial_batch=True,
+    dataset_hint=" (train_gan.py drives %s; the StyleGAN2 high-resolution configs run through "
+                 "train_stylegan2_contraD.py)" % sorted(IMAGE_SIZES))
+
+
 def main(argv=None):
-    P = parse_args(argv)
-    if P.comment:
-        P.comment = '_' + P.comment
-    P.gin_stem = Path(P.gin_config).stem
-    P = setup(P)
-    world = int(os.environ.get('WORLD_SIZE', '1'))
-    rank = int(os.environ.get('RANK', '0'))
-    local_rank = int(os.environ.get('LOCAL_RANK', '0'))
-    if world > 1 and P.mode in BASELINE_MODES:
-        raise NotImplementedError("--mode=%s runs on one GPU (WORLD_SIZE=%d): the gradient exchange inside D's backward assumes "
-                                  "one discriminator call per step, and the baseline modes (%s) with cr / bcr make two"
-                                  % (P.mode, world, ', '.join(BASELINE_MODES)))
-    torch.cuda.set_device(local_rank)
-    dev = torch.device('cuda', local_rank)
-    if world > 1:
-        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
-        os.environ.setdefault('MASTER_PORT', str(P.port))
-        dist.init_process_group('nccl', device_id=dev)
-    P.rank, P.distributed = rank, world > 1
-
-    config.clear_config()
-    config.parse_config_files_and_bindings([os.path.join(config.CONFIG_ROOT, 'defaults', 'gan.gin'),
-                                            os.path.join(config.CONFIG_ROOT, 'defaults', 'augment.gin'), P.gin_config])
-    options = get_options_dict()
-    if P.max_steps is not None:
-        options['max_steps'] = P.max_steps
-    options['batch_size'] = options['batch_size'] // world                  # train_gan.py:247
-    if options['dataset'] not in IMAGE_SIZES:
-        raise NotImplementedError("dataset '%s' (train_gan.py drives %s; the StyleGAN2 high-resolution configs run "
-                                  "through train_stylegan2_contraD.py)" % (options['dataset'], sorted(IMAGE_SIZES)))
-    image_size = IMAGE_SIZES[options['dataset']]
-
-    torch.manual_seed(P.seed); np.random.seed(P.seed)                       # identical initial weights on all ranks
-    G, D = get_architecture(P.architecture, image_size, P=P)
-    if P.resume:
-        G.load_state_dict(torch.load(f"{P.resume}/gen.pt", map_location='cpu'))
-        D.load_state_dict(torch.load(f"{P.resume}/dis.pt", map_location='cpu'))
-    if P.finetune:
-        D.load_state_dict(torch.load(f"{P.finetune}/dis.pt", map_location='cpu'), strict=False)
-        D.reset_parameters(D.linear)
-        P.comment += 'ft'
-    G, D = G.to(dev), D.to(dev)
-    torch.manual_seed(P.seed + 1000 * (rank + 1)); np.random.seed(P.seed + 1000 * (rank + 1))
-
-    opt_G = FusedAdam(G.parameters(), lr=options["lr"], betas=tuple(options["beta"]))
-    opt_D = FusedAdam(D.parameters(), lr=options["lr_d"], betas=tuple(options["beta"]))
-    starting_step = 1
-    if P.resume:
-        ck = torch.load(f"{P.resume}/optim.pt", map_location=dev)
-        opt_G.load_state_dict(ck['optim_G']); opt_D.load_state_dict(ck['optim_D'])
-        starting_step = ck['epoch'] + 1
-    logdir = P.logdir or P.resume or f'logs/gan/{P.gin_stem}/{P.architecture}/{P.filename}{P.comment}'
-    log_file = None
-    if rank == 0:
-        os.makedirs(logdir, exist_ok=True)
-        log_file = open(os.path.join(logdir, 'log.txt'), 'a')
-
-    def log(msg):
-        if rank == 0:
-            print(msg, flush=True)
-            log_file.write(msg + '\n'); log_file.flush()
-
-    P.augment_fn = get_augment(mode=P.aug).to(dev)
-    reducers = (None, None)
-    if world > 1:
-        reducers = (GradAllReducer(G.parameters()), None)
-        if hasattr(D, 'enable_grad_overlap'):
-            D.enable_grad_overlap(OverlappedGradReducer())
-        else:
-            reducers = (reducers[0], GradAllReducer(D.parameters()))
-    use_synth = P.synthetic
-    if not use_synth and not P.data:
-        try:
-            import torchvision  # noqa: F401
-        except ImportError:
-            log('torchvision not available -> --synthetic (--data FILE.npz trains on real images without it)')
-            use_synth = True
-    if P.data and not use_synth:
-        # a captured step has ONE batch size (GraphedDStep.load_images copies into a fixed buffer)
-        drop_last = bool(P.graph and P.mode == 'contrad')
-        if drop_last:
-            log("--graph: one captured batch size -> the loader drops each epoch's last partial batch")
-        loader = loader_for(P.data, options['dataset'], image_size, options['batch_size'], rank, world, drop_last, dev)
-    else:
-        loader = _synthetic_loader(options['batch_size'], image_size, dev, P.seed + rank) if use_synth else \
-            _dataset_loader(options['dataset'], options['batch_size'], rank, world, P.workers)
-    log(f"# Params - G: {sum(p.numel() for p in G.parameters())}, D: {sum(p.numel() for p in D.parameters())}")
-    log(str(options))
-
-    monitor = None
-    if P.monitor and rank == 0:
-        monitor = Monitor(logdir, P.architecture, image_size, dev, P.seed, no_gif=P.no_gif, P=P)
-        loader = LastBatch(loader)                                          # the preview shows the batch the step drew
-    knn_monitor = None
-    if P.knn_data and rank == 0:
-        knn_monitor = KNNMonitor(logdir, P.architecture, image_size, dev, P.seed, P.knn_data, k=P.knn_k, temp=P.knn_temp, P=P)
-    graphed = None
-    if P.graph:
-        if P.mode != 'contrad':
-            log("--graph captures the ContraD critic iteration (--mode contrad), not '%s' -> eager" % P.mode)
-        else:
-            graphed = GraphedCritic()
-    t0 = time.time()
-    for step in range(starting_step, options['max_steps'] + 1):
-        losses = train_step(P, options, G, D, opt_G, opt_D, loader, step, reducers, graphed)
-        if step % P.print_every == 0:
-            vals = {k: float(v.detach()) for k, v in losses.items()}              # the only host sync of the loop
-            log('[Steps %7d] [G %.3f] [D %.3f] [pen %.3f] [%.1f img/s]' %
-                (step, vals['G_loss'], vals['D_loss'], vals['D_penalty'],
-                 P.print_every * options['batch_size'] * world / max(time.time() - t0, 1e-9)))
-            t0 = time.time()
-        if step % P.evaluate_every == 0 and rank == 0:
-            if monitor is not None:
-                monitor.update(step, G, loader.last, P.augment_fn)
-            if knn_monitor is not None:
-                log('[Steps %7d] [kNN Acc@1 %.3f]' % (step, knn_monitor.update(step, D)['acc@1']))
-            torch.save(G.state_dict(), logdir + '/gen.pt')
-            torch.save(D.state_dict(), logdir + '/dis.pt')
-            if step % P.save_every == 0:
-                torch.save(G.state_dict(), logdir + f'/gen_{step}.pt')
-                torch.save(D.state_dict(), logdir + f'/dis_{step}.pt')
-            torch.save({'epoch': step, 'optim_G': opt_G.state_dict(), 'optim_D': opt_D.state_dict()},
-                       logdir + '/optim.pt')
-    if world > 1:
-        dist.destroy_process_group()
-    return logdir
+    run = train_driver.build_run(parse_args(argv), SCRIPT)
+    return train_driver.run_loop(run, lambda step: train_step(run.P, run.options, run.G, run.D, run.opt_G, run.opt_D,
+                                                              run.loader, step, run.reducers, run.graphed))
 
 
 if __name__ == '__main__':

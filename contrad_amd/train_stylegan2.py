@@ -18,86 +18,48 @@ global loss of the DataParallel formulation, without the per-step parameter broa
 FID / GIF / tensorboard side paths are out of scope; ``--monitor`` writes the reference's image
 grids from ``g_ema`` as PNG / animated PNG (contrad_amd/evaluate/gan.py; off by default).  ``--knn_data FILE.npz`` logs the weighted kNN accuracy
 of D's features at every evaluation (contrad_amd/knn.py; an addition, off by default).
+
+This module holds what the two scripts do differently from train_gan (their flags, option defaults, schedules, EMA,
+loaders, log directory and ``train_iteration``, whose D-steps are engine.d_step_stylegan2 / d_step_stylegan2_contrad);
+everything else of ``main()`` is contrad_amd/train_driver.py.
 """
 import functools
 import os
-import time
-from argparse import ArgumentParser
-from pathlib import Path
 
-import numpy as np
 import torch
-import torch.distributed as dist
 
-from . import config, engine, ops
-from .augment import get_augment
-from .data import loader_for
-from .evaluate.gan import LastBatch, Monitor
-from .knn import KNNMonitor, add_hook_arguments
-from .engine import (GradAllReducer, GraphedSG2DStep, GraphedSG2GStep, _sg2_fakes, loss_D_fn_separate, r1_loss, set_grad,
-                     setup_grad_exchange)
+from . import config, engine, ops, train_driver
+from .data import IMAGE_SIZES                   # every dataset of the table
+from .engine import GraphedSG2DStep, GraphedSG2GStep, _sg2_fakes, set_grad
 from .hostio import THROTTLE
-from .models.gan import get_architecture
-from .optim import FusedAdam
-from .training.gan import BASELINE_MODES, setup
 from .training.gan.contrad import _GanGLoss
-
-# datasets.py:10,57,99,115,131 of the reference
-IMAGE_SIZES = {'cifar10': (32, 32, 3), 'cifar100': (32, 32, 3), 'cifar10_hflip': (32, 32, 3),
-               'cifar100_hflip': (32, 32, 3), 'celeba128': (128, 128, 3), 'afhq_cat': (512, 512, 3),
-               'afhq_dog': (512, 512, 3), 'afhq_wild': (512, 512, 3)}
 
 
 def parse_args(argv=None, contrad_script=False):
-    parser = ArgumentParser(description='Training script: StyleGAN2%s on MI355X (one process per GPU).'
-                                        % (' + ContraD' if contrad_script else ''))
-    parser.add_argument('gin_config', type=str, help='Path to the gin configuration file')
-    parser.add_argument('architecture', type=str, help='Architecture')
-    parser.add_argument('--mode', default='std', type=str, help='Training mode (contrad | simclr_only | std | aug | aug_both)')
-    parser.add_argument('--penalty', default='none', type=str, help='none | cr | bcr (std / aug / aug_both)')
-    parser.add_argument('--aug', default='none', type=str, help='Augmentation (simclr | simclr_hq | simclr_hq_cutout | none | hflip | hfrt | diffaug; diffaug needs a gin '
-                             'file that binds augment.diffaug_policy = "color,cutout", as configs/gan/diffaug/c10_diffaug.gin '
-                             'does: with any other file it raises NotImplementedError until the line is added)')
-    parser.add_argument('--use_warmup', action='store_true', help='Use warmup strategy on LR')
-    parser.add_argument('--workers', default=8, type=int)
-    parser.add_argument('--temp', default=0.1, type=float)
-    parser.add_argument('--lbd_a', default=1.0, type=float)
-    # StyleGAN2 options (train_stylegan2.py:61-75)
-    parser.add_argument('--no_lazy', action='store_true', help='Do not use lazy regularization')
-    parser.add_argument('--d_reg_every', type=int, default=16)
-    parser.add_argument('--lbd_r1', type=float, default=10)
-    parser.add_argument('--style_mix', default=0.9, type=float)
-    parser.add_argument('--halflife_k', default=20, type=int)
-    parser.add_argument('--ema_start_k', default=None, type=int)
-    parser.add_argument('--halflife_lr', default=0, type=int)
-    parser.add_argument('--no_fid', action='store_true')
-    parser.add_argument('--no_gif', action='store_true', help='with --monitor: keep only the latest fixed-latent grid (fixed_gen_<seed>.png), no '
-                             'per-step files and no animation; without --monitor accepted and ignored')
-    parser.add_argument('--n_eval_avg', default=3, type=int)
-    parser.add_argument('--print_every', default=50, type=int)
-    parser.add_argument('--evaluate_every', default=2000, type=int, help='checkpoint period (steps)')
-    parser.add_argument('--save_every', default=100000, type=int)
-    parser.add_argument('--comment', default='', type=str)
-    parser.add_argument('--resume', default=None, type=str)
-    parser.add_argument('--finetune', default=None, type=str)
-    # additions
-    parser.add_argument('--port', default=40405, type=int)
-    parser.add_argument('--synthetic', action='store_true', help='uniform-random images instead of a dataset')
-    parser.add_argument('--data', default=None, type=str,
-                        help='npz with x_train uint8 [n, H, W, 3] (tools/make_image_npz.py): the set lives on the device, batches '
-                             'are gathered there (contrad_amd/data.py; no torchvision)')
-    parser.add_argument('--max_steps', default=None, type=int, help='override options.max_steps')
-    parser.add_argument('--batch_size', default=None, type=int, help='override options.batch_size (global)')
-    parser.add_argument('--logdir', default=None, type=str)
-    parser.add_argument('--seed', default=0, type=int)
-    parser.add_argument('--graph', action='store_true',
-                        help='replay the D- and G-step from captured hipGraphs (collectives included; the ContraD script, whose '
-                             'D-step draws its own fakes)')
-    parser.add_argument('--monitor', action='store_true',
-                        help='rank 0 writes image grids at every evaluate_every: progress_<seed>/step_<step>.png and the animated '
-                             'training_progress_<seed>.png (g_ema at fixed latents), real_augment_<seed>.png; the training trajectory is '
-                             'unchanged')
-    add_hook_arguments(parser)
+    parser = train_driver.make_parser(
+        'Training script: StyleGAN2%s on MI355X (one process per GPU).' % (' + ContraD' if contrad_script else ''), [
+            'gin_config', 'architecture', '--mode',
+            ('--penalty', dict(help='none | cr | bcr (std / aug / aug_both)')),
+            '--aug', '--use_warmup',
+            ('--workers', dict(default=8)),
+            '--temp', '--lbd_a',
+            # StyleGAN2 options (train_stylegan2.py:61-75)
+            ('--no_lazy', dict(action='store_true', help='Do not use lazy regularization')),
+            ('--d_reg_every', dict(type=int, default=16)),
+            ('--lbd_r1', dict(type=float, default=10)),
+            ('--style_mix', dict(default=0.9, type=float)),
+            ('--halflife_k', dict(default=20, type=int)),
+            ('--ema_start_k', dict(default=None, type=int)),
+            ('--halflife_lr', dict(default=0, type=int)),
+            '--no_fid', '--no_gif', '--n_eval_avg', '--print_every', '--evaluate_every', '--save_every', '--comment',
+            '--resume', '--finetune',
+            ('--port', dict(default=40405)),
+            '--synthetic', '--data', '--max_steps',
+            ('--batch_size', dict(default=None, type=int, help='override options.batch_size (global)')),
+            '--logdir', '--seed',
+            ('--graph', dict(help='replay the D- and G-step from captured hipGraphs (collectives included; the ContraD '
+                                  'script, whose D-step draws its own fakes)')),
+            ('--monitor', dict(help=train_driver.monitor_help('g_ema at fixed latents')))])
     return parser.parse_args(argv)
 
 
@@ -155,14 +117,11 @@ def loss_G_nonsat(d_gen):
     return _GanGLoss.apply(d_gen, 'nonsat')
 
 
-def _opt_step(opt, reducer):
-    world = reducer() if reducer is not None else 1
-    opt.step(grad_scale=1.0 / world) if world > 1 else opt.step()
-
-
 # train_stylegan2_contraD.py calls G_D.forward WITHOUT its style_mix argument (:207,218 -> the default 0.9 of :128): the
 # ``--style_mix`` flag only names the log directory there (:349).  Reproduced as is.
 CONTRAD_SCRIPT_STYLE_MIX = 0.9
+
+NOT_CONTRAD = "--graph captures the ContraD D-step (--mode contrad), not '%s'"
 
 
 class GraphedCritic(engine.GraphedCritic):
@@ -172,8 +131,7 @@ class GraphedCritic(engine.GraphedCritic):
 
     def __init__(self):
         super().__init__(functools.partial(GraphedSG2DStep, contrad_script=True, style_mix=CONTRAD_SCRIPT_STYLE_MIX, warmup=0),
-                         functools.partial(GraphedSG2GStep, style_mix=CONTRAD_SCRIPT_STYLE_MIX),
-                         "--graph captures the ContraD D-step (--mode contrad), not '%s'")
+                         functools.partial(GraphedSG2GStep, style_mix=CONTRAD_SCRIPT_STYLE_MIX), NOT_CONTRAD)
 
 
 def train_iteration(P, opt, G, D, g_ema, opt_G, opt_D, loader, step, reducers, contrad_script, graphed=None):
@@ -182,7 +140,7 @@ def train_iteration(P, opt, G, D, g_ema, opt_G, opt_D, loader, step, reducers, c
     THROTTLE.begin()
     red_G, red_D = reducers
     style_mix = CONTRAD_SCRIPT_STYLE_MIX if contrad_script else P.style_mix
-    d_regularize = (step % P.d_reg_every == 0) and (P.lbd_r1 > 0)
+    d_step = engine.d_step_stylegan2_contrad if contrad_script else engine.d_step_stylegan2
     if P.use_warmup:
         _update_warmup(opt_G, step, opt["warmup"], opt["lr"])
         _update_warmup(opt_D, step, opt["warmup"], opt["lr_d"])
@@ -210,43 +168,19 @@ def train_iteration(P, opt, G, D, g_ema, opt_G, opt_D, loader, step, reducers, c
             g_loss = loss_G_nonsat(d_gen)
         else:
             g_loss = P.train_fn["G"](P, D, opt, images, gen_images)
-        opt_G.zero_grad()
-        g_loss.backward()
-        _opt_step(opt_G, red_G)
+        engine.optimizer_step(opt_G, g_loss, G, red_G)
     out['G_loss'] = g_loss.detach()
 
-    # ---- discriminator step ----
+    # ---- discriminator step: train_stylegan2 feeds it the generator step's fakes, the ContraD script draws fresh ones ----
     set_grad(G, False); set_grad(D, True)
-
-    def d_loss_of(images, gen_images):
-        if contrad_script:
-            return loss_D_fn_separate(P, D, opt, images, gen_images)
-        return P.train_fn["D"](P, D, opt, images, gen_images)
-
     done = graphed(P, opt, G, D, opt_D, images, step) if graphed is not None else None
-    if done is not None:
-        d_loss, aux = done
-        if 'r1' in aux:
-            out['D_r1'] = aux['r1'].detach()
-    else:
-        if contrad_script:
-            gen_images = sample_generator(G, N, style_mix=style_mix, enable_grad=False)
-        d_loss, aux = d_loss_of(images, gen_images.detach())
-        loss = d_loss + aux['penalty']
-        if d_regularize:
-            r1 = r1_loss(D, images, P.augment_fn)
-            loss = loss + (0.5 * P.lbd_r1) * r1 * P.d_reg_every
-            out['D_r1'] = r1.detach()
-        opt_D.zero_grad()
-        loss.backward()
-        _opt_step(opt_D, red_D)
-    for _ in range(opt['n_critic'] - 1):
+    d_loss, aux = done if done is not None else d_step(P, G, D, opt_D, opt, images, step, red_D, style_mix,
+                                                       fakes=None if contrad_script else gen_images.detach())
+    if 'r1' in aux:
+        out['D_r1'] = aux['r1'].detach()
+    for _ in range(opt['n_critic'] - 1):        # the extra critic iterations: fresh batch, fresh fakes, no R1
         images, _labels = next(loader)
-        gen_images = sample_generator(G, images.size(0), style_mix=style_mix, enable_grad=False)
-        d_loss, aux = d_loss_of(images, gen_images)
-        opt_D.zero_grad()
-        (d_loss + aux['penalty']).backward()
-        _opt_step(opt_D, red_D)
+        d_loss, aux = d_step(P, G, D, opt_D, opt, images, step, red_D, style_mix, r1=False)
     G.eval(); D.eval()
     THROTTLE.end()
     out.update({'D_loss': d_loss.detach(), 'D_penalty': aux['penalty'].detach(), 'D_real': aux['d_real'].detach(),
@@ -292,155 +226,43 @@ def _dataset_loader(name, batch, rank, world, workers):
         sampler.set_epoch(epoch)
 
 
-def main(argv=None, contrad_script=False):
-    P = parse_args(argv, contrad_script)
-    if P.comment:
-        P.comment = '_' + P.comment
-    P.gin_stem = Path(P.gin_config).stem
-    P = setup(P)
-    world = int(os.environ.get('WORLD_SIZE', '1'))
-    rank = int(os.environ.get('RANK', '0'))
-    local_rank = int(os.environ.get('LOCAL_RANK', '0'))
-    if world > 1 and P.mode in BASELINE_MODES:
-        raise NotImplementedError("--mode=%s runs on one GPU (WORLD_SIZE=%d): the gradient exchange inside D's backward assumes "
-                                  "one discriminator call per step, and the baseline modes (%s) with cr / bcr make two"
-                                  % (P.mode, world, ', '.join(BASELINE_MODES)))
-    torch.cuda.set_device(local_rank)
-    dev = torch.device('cuda', local_rank)
-    if world > 1:
-        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
-        os.environ.setdefault('MASTER_PORT', str(P.port))
-        dist.init_process_group('nccl', device_id=dev)
-    P.rank, P.distributed = rank, world > 1
-
-    config.clear_config()
-    config.parse_config_files_and_bindings([os.path.join(config.CONFIG_ROOT, 'defaults', 'gan.gin'),
-                                            os.path.join(config.CONFIG_ROOT, 'defaults', 'augment.gin'), P.gin_config])
-    options = get_options_dict()
-    if P.max_steps is not None:
-        options['max_steps'] = P.max_steps
+def _prepare(P, options, contrad_script):
     if P.batch_size is not None:
         options['batch_size'] = P.batch_size
     if options['loss'] != 'nonsat' and contrad_script:
         raise NotImplementedError('train_stylegan2_contraD.py hard-codes the non-saturating loss (:105,:113)')
-    if options['dataset'] not in IMAGE_SIZES:
-        raise NotImplementedError("dataset '%s'" % options['dataset'])
-    image_size = IMAGE_SIZES[options['dataset']]
-    if options['batch_size'] % world:
-        raise ValueError('batch_size %d is not divisible by the %d ranks' % (options['batch_size'], world))
-    options['global_batch_size'] = options['batch_size']            # the schedules count GLOBAL images
-    options['batch_size'] = options['batch_size'] // world
     if P.no_lazy:
         P.d_reg_every = 1
     if P.ema_start_k is None:
         P.ema_start_k = P.halflife_k
-    P.accum = 0.5 ** (options['global_batch_size'] / (P.halflife_k * 1000))
+    P.accum = 0.5 ** (options['batch_size'] / (P.halflife_k * 1000))       # (the global batch: the ranks divide it later)
 
-    torch.manual_seed(P.seed); np.random.seed(P.seed)               # identical initial weights on all ranks
-    G, D = get_architecture(P.architecture, image_size, P=P)
-    g_ema, _ = get_architecture(P.architecture, image_size, P=P)
-    if P.resume:
-        G.load_state_dict(torch.load(f"{P.resume}/gen.pt", map_location='cpu'))
-        D.load_state_dict(torch.load(f"{P.resume}/dis.pt", map_location='cpu'))
-        g_ema.load_state_dict(torch.load(f"{P.resume}/gen_ema.pt", map_location='cpu'))
-    if P.finetune:
-        D.load_state_dict(torch.load(f"{P.finetune}/dis.pt", map_location='cpu'), strict=False)
-        D.reset_parameters(D.linear)
-        P.comment += 'ft'
-    G, D, g_ema = G.to(dev), D.to(dev), g_ema.to(dev)
-    g_ema.eval()
-    torch.manual_seed(P.seed + 1000 * (rank + 1)); np.random.seed(P.seed + 1000 * (rank + 1))
-    torch.cuda.manual_seed(P.seed + 1000 * (rank + 1))
-    P.augment_fn = get_augment(mode=P.aug).to(dev)
 
-    opt_G = FusedAdam(G.parameters(), lr=options["lr"], betas=tuple(options["beta"]))
-    opt_D = FusedAdam(D.parameters(), lr=options["lr_d"], betas=tuple(options["beta"]))
-    starting_step = 1
-    if P.resume:
-        ck = torch.load(f"{P.resume}/optim.pt", map_location=dev)
-        opt_G.load_state_dict(ck['optim_G']); opt_D.load_state_dict(ck['optim_D'])
-        starting_step = ck['epoch'] + 1
+def _logdir(P, contrad_script):
     desc = f"R{P.lbd_r1}_mix{P.style_mix}_H{P.halflife_k}"
     if P.halflife_lr > 0:
         desc += f"_lr{P.halflife_lr / 1000000:.1f}M"
     desc += "_NoLazy" if P.no_lazy else "_Lazy"
     sub = 'gan_dp' if contrad_script else 'gan'
-    logdir = P.logdir or P.resume or f'logs/{sub}/st_{P.gin_stem}/{P.architecture}/{P.filename}_{desc}{P.comment}'
-    log_file = None
-    if rank == 0:
-        os.makedirs(logdir, exist_ok=True)
-        log_file = open(os.path.join(logdir, 'log.txt'), 'a')
+    return f'logs/{sub}/st_{P.gin_stem}/{P.architecture}/{P.filename}_{desc}{P.comment}'
 
-    def log(msg):
-        if rank == 0:
-            print(msg, flush=True)
-            log_file.write(msg + '\n'); log_file.flush()
 
-    reducers = (None, None)
-    if world > 1:
-        reducers = (GradAllReducer(G.parameters()), setup_grad_exchange(D))      # D: weights exchanged inside the backward
-    use_synth = P.synthetic
-    if not use_synth and not P.data:
-        try:
-            import torchvision  # noqa: F401
-        except ImportError:
-            log('torchvision not available -> --synthetic (--data FILE.npz trains on real images without it)')
-            use_synth = True
-    if P.data and not use_synth:
-        loader = loader_for(P.data, options['dataset'], image_size, options['batch_size'], rank, world, True, dev)
-    else:
-        loader = _synthetic_loader(options['batch_size'], image_size, dev, P.seed + rank) if use_synth else \
-            _dataset_loader(options['dataset'], options['batch_size'], rank, world, P.workers)
-    log(f"# Params - G: {sum(p.numel() for p in G.parameters())}, D: {sum(p.numel() for p in D.parameters())}")
-    log(str(options))
-    log(f"Use G moving average: {P.accum}")
+def script(contrad_script):
+    return train_driver.Script(
+        get_options=get_options_dict, image_sizes=IMAGE_SIZES, logdir=lambda P: _logdir(P, contrad_script),
+        synthetic_loader=_synthetic_loader, dataset_loader=_dataset_loader, make_critic=GraphedCritic,
+        not_contrad=NOT_CONTRAD,
+        graph_refusal=None if contrad_script else
+        "--graph: train_stylegan2_contraD.py only (train_stylegan2.py feeds the D-step the G-step's fakes)",
+        prepare=lambda P, options: _prepare(P, options, contrad_script), divisible_batch=True, seed_cuda=True, ema=True,
+        start_up_lines=lambda P: [f"Use G moving average: {P.accum}"])
 
-    monitor = None
-    if P.monitor and rank == 0:
-        monitor = Monitor(logdir, P.architecture, image_size, dev, P.seed, no_gif=P.no_gif, P=P)
-        loader = LastBatch(loader)                                  # the preview shows the batch the step drew
-    knn_monitor = None
-    if P.knn_data and rank == 0:
-        knn_monitor = KNNMonitor(logdir, P.architecture, image_size, dev, P.seed, P.knn_data, k=P.knn_k, temp=P.knn_temp, P=P)
-    graphed = None
-    if P.graph:
-        if not contrad_script:
-            log('--graph: train_stylegan2_contraD.py only (train_stylegan2.py feeds the D-step the G-step\'s fakes) '
-                '-> eager')
-        elif P.mode != 'contrad':
-            log("--graph captures the ContraD D-step (--mode contrad), not '%s' -> eager" % P.mode)
-        else:
-            graphed = GraphedCritic()
-    t0 = time.time()
-    for step in range(starting_step, options['max_steps'] + 1):
-        losses = train_iteration(P, options, G, D, g_ema, opt_G, opt_D, loader, step, reducers, contrad_script,
-                                 graphed)
-        if losses['lr_note']:
-            log('LR Updated: [G %.5f] [D %.5f]' % losses['lr_note'])
-        if step % P.print_every == 0:
-            vals = {k: float(v) for k, v in losses.items() if torch.is_tensor(v)}      # the only host sync of the loop
-            log('[Steps %7d] [G %.3f] [D %.3f] [pen %.3f]%s [%.1f img/s]' %
-                (step, vals['G_loss'], vals['D_loss'], vals['D_penalty'],
-                 (' [r1 %.4g]' % vals['D_r1']) if 'D_r1' in vals else '',
-                 P.print_every * options['global_batch_size'] / max(time.time() - t0, 1e-9)))
-            t0 = time.time()
-        if step % P.evaluate_every == 0 and rank == 0:
-            if monitor is not None:
-                monitor.update(step, g_ema, loader.last, P.augment_fn)
-            if knn_monitor is not None:
-                log('[Steps %7d] [kNN Acc@1 %.3f]' % (step, knn_monitor.update(step, D)['acc@1']))
-            torch.save(G.state_dict(), logdir + '/gen.pt')
-            torch.save(D.state_dict(), logdir + '/dis.pt')
-            torch.save(g_ema.state_dict(), logdir + '/gen_ema.pt')
-            if step % P.save_every == 0:
-                torch.save(G.state_dict(), logdir + f'/gen_{step}.pt')
-                torch.save(D.state_dict(), logdir + f'/dis_{step}.pt')
-                torch.save(g_ema.state_dict(), logdir + f'/gen_ema_{step}.pt')
-            torch.save({'epoch': step, 'optim_G': opt_G.state_dict(), 'optim_D': opt_D.state_dict()},
-                       logdir + '/optim.pt')
-    if world > 1:
-        dist.destroy_process_group()
-    return logdir
+
+def main(argv=None, contrad_script=False):
+    run = train_driver.build_run(parse_args(argv, contrad_script), script(contrad_script))
+    return train_driver.run_loop(run, lambda step: train_iteration(
+        run.P, run.options, run.G, run.D, run.g_ema, run.opt_G, run.opt_D, run.loader, step, run.reducers, contrad_script,
+        run.graphed))
 
 
 if __name__ == '__main__':

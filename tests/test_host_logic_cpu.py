@@ -300,3 +300,107 @@ def test_captured_train_step_protocol_on_the_host(monkeypatch):
         assert not d_loss.requires_grad and not aux['twice'].requires_grad and (d_loss.item(), aux['twice'].item()) == (4.0, 8.0)
         assert step.opt.steps == k and step.hyper.tolist() == [0.5 * k, 0.25, 1.0]
     assert log == ['begin', 'inputs', 'replay', 'end'] * 2
+
+
+_GAN_DEFAULTS = {
+    'gin_config': 'c.gin', 'architecture': 'arch', 'mode': 'std', 'penalty': 'none', 'aug': 'none', 'use_warmup': False,
+    'temp': 0.1, 'lbd_a': 1.0, 'no_fid': False, 'no_gif': False, 'n_eval_avg': 3, 'print_every': 50,
+    'evaluate_every': 2000, 'save_every': 100000, 'comment': '', 'resume': None, 'finetune': None, 'workers': 0,
+    'world_size': 1, 'rank': 0, 'port': 40404, 'synthetic': False, 'data': None, 'max_steps': None, 'logdir': None,
+    'seed': 0, 'graph': False, 'monitor': False, 'knn_data': None, 'knn_k': 200, 'knn_temp': 0.1}
+_SG2_DEFAULTS = {
+    'gin_config': 'c.gin', 'architecture': 'arch', 'mode': 'std', 'penalty': 'none', 'aug': 'none', 'use_warmup': False,
+    'workers': 8, 'temp': 0.1, 'lbd_a': 1.0, 'no_lazy': False, 'd_reg_every': 16, 'lbd_r1': 10, 'style_mix': 0.9,
+    'halflife_k': 20, 'ema_start_k': None, 'halflife_lr': 0, 'no_fid': False, 'no_gif': False, 'n_eval_avg': 3,
+    'print_every': 50, 'evaluate_every': 2000, 'save_every': 100000, 'comment': '', 'resume': None, 'finetune': None,
+    'port': 40405, 'synthetic': False, 'data': None, 'max_steps': None, 'batch_size': None, 'logdir': None, 'seed': 0,
+    'graph': False, 'monitor': False, 'knn_data': None, 'knn_k': 200, 'knn_temp': 0.1}
+_SHARED_FLAGS = ['--mode', 'contrad', '--penalty', 'bcr', '--aug', 'simclr', '--use_warmup', '--temp', '0.2', '--lbd_a', '2.0',
+                 '--no_fid', '--no_gif', '--n_eval_avg', '4', '--print_every', '5', '--evaluate_every', '6', '--save_every',
+                 '7', '--comment', 'x', '--resume', 'r', '--finetune', 'f', '--workers', '3', '--port', '1234', '--synthetic',
+                 '--data', 'd.npz', '--max_steps', '9', '--logdir', 'l', '--seed', '11', '--graph', '--monitor',
+                 '--knn_data', 'k.npz', '--knn_k', '20', '--knn_temp', '0.5']
+_SHARED_SET = {'mode': 'contrad', 'penalty': 'bcr', 'aug': 'simclr', 'use_warmup': True, 'temp': 0.2, 'lbd_a': 2.0,
+               'no_fid': True, 'no_gif': True, 'n_eval_avg': 4, 'print_every': 5, 'evaluate_every': 6, 'save_every': 7,
+               'comment': 'x', 'resume': 'r', 'finetune': 'f', 'workers': 3, 'port': 1234, 'synthetic': True,
+               'data': 'd.npz', 'max_steps': 9, 'logdir': 'l', 'seed': 11, 'graph': True, 'monitor': True,
+               'knn_data': 'k.npz', 'knn_k': 20, 'knn_temp': 0.5}
+
+
+def test_the_three_command_lines_keep_every_flag_and_default():
+    """Every destination and default of the three parsers, one command line per script that sets every flag, and the
+    flags a script does not have."""
+    from contrad_amd import train_gan, train_stylegan2
+    assert vars(train_gan.parse_args(['c.gin', 'arch'])) == _GAN_DEFAULTS
+    assert vars(train_stylegan2.parse_args(['c.gin', 'arch'])) == _SG2_DEFAULTS
+    assert vars(train_stylegan2.parse_args(['c.gin', 'arch'], contrad_script=True)) == _SG2_DEFAULTS
+    a = vars(train_gan.parse_args(['c.gin', 'arch'] + _SHARED_FLAGS + ['--world-size', '2', '--rank', '1']))
+    assert a == dict(_GAN_DEFAULTS, world_size=2, rank=1, **_SHARED_SET)
+    own = ['--no_lazy', '--d_reg_every', '4', '--lbd_r1', '0.5', '--style_mix', '0.5', '--halflife_k', '10',
+           '--ema_start_k', '2', '--halflife_lr', '1000', '--batch_size', '8']
+    own_set = {'no_lazy': True, 'd_reg_every': 4, 'lbd_r1': 0.5, 'style_mix': 0.5, 'halflife_k': 10, 'ema_start_k': 2,
+               'halflife_lr': 1000, 'batch_size': 8}
+    for contrad_script in (False, True):
+        a = vars(train_stylegan2.parse_args(['c.gin', 'arch'] + _SHARED_FLAGS + own, contrad_script))
+        assert a == dict(_SG2_DEFAULTS, **_SHARED_SET, **own_set)
+        with pytest.raises(SystemExit):
+            train_stylegan2.parse_args(['c.gin', 'arch', '--world-size', '1'], contrad_script)
+    with pytest.raises(SystemExit):
+        train_gan.parse_args(['c.gin', 'arch', '--batch_size', '8'])
+
+
+def test_train_driver_pure_pieces():
+    """What the driver decides on the host: the two log-directory names, the per-rank batch rule of each script, the two
+    warm-up ratios, the --graph gate's log lines and the image-size table with train_gan's subset."""
+    import argparse
+    from contrad_amd import data, train_driver, train_gan, train_stylegan2
+    # log directories
+    P = argparse.Namespace(gin_stem='c10_b512', architecture='sndcgan', filename='contrad_simclr_L1.0_T0.1', comment='_x')
+    assert train_gan.SCRIPT.logdir(P) == 'logs/gan/c10_b512/sndcgan/contrad_simclr_L1.0_T0.1_x'
+    P = argparse.Namespace(gin_stem='c10_style64', architecture='stylegan2', filename='contrad_simclr_L1.0_T0.1',
+                           comment='', lbd_r1=10, style_mix=0.9, halflife_k=20, halflife_lr=0, no_lazy=False)
+    assert train_stylegan2.script(False).logdir(P) == \
+        'logs/gan/st_c10_style64/stylegan2/contrad_simclr_L1.0_T0.1_R10_mix0.9_H20_Lazy'
+    P.lbd_r1, P.halflife_lr, P.no_lazy, P.comment = 0.5, 2500000, True, '_runft'
+    assert train_stylegan2.script(True).logdir(P) == \
+        'logs/gan_dp/st_c10_style64/stylegan2/contrad_simclr_L1.0_T0.1_R0.5_mix0.9_H20_lr2.5M_NoLazy_runft'
+    # per-rank batch
+    o = {'batch_size': 512}
+    train_driver.per_rank_batch(o, 8, train_gan.SCRIPT.divisible_batch)
+    assert o == {'batch_size': 64}
+    o = {'batch_size': 10}
+    train_driver.per_rank_batch(o, 4, train_gan.SCRIPT.divisible_batch)
+    assert o == {'batch_size': 2}                                   # train_gan floors
+    with pytest.raises(ValueError):
+        train_driver.per_rank_batch({'batch_size': 10}, 4, train_stylegan2.script(True).divisible_batch)
+    o = {'batch_size': 64}
+    train_driver.per_rank_batch(o, 8, train_stylegan2.script(False).divisible_batch)
+    assert o == {'batch_size': 8, 'global_batch_size': 64}
+    # warm-up ratios: (step + 1) / warmup against (step + 1) / (warmup + 1e-8)
+    opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=1.0)
+    train_gan._update_warmup(opt, 0, 3, 2e-3)
+    assert opt.param_groups[0]['lr'] == (1 / 3) * 2e-3
+    train_stylegan2._update_warmup(opt, 0, 3, 2e-3)
+    assert opt.param_groups[0]['lr'] == (1 / (3 + 1e-8)) * 2e-3 != (1 / 3) * 2e-3
+    # --graph
+    gate = lambda script, **kw: train_driver.graph_gate(argparse.Namespace(**kw), script)
+    assert gate(train_gan.SCRIPT, graph=False, mode='std') == (None, None)
+    assert gate(train_gan.SCRIPT, graph=True, mode='std') == \
+        (None, "--graph captures the ContraD critic iteration (--mode contrad), not 'std' -> eager")
+    critic, why_not = gate(train_gan.SCRIPT, graph=True, mode='contrad')
+    assert isinstance(critic, train_gan.GraphedCritic) and why_not is None
+    for mode in ('contrad', 'std'):
+        assert gate(train_stylegan2.script(False), graph=True, mode=mode) == \
+            (None, "--graph: train_stylegan2_contraD.py only (train_stylegan2.py feeds the D-step the G-step's fakes) "
+                   "-> eager")
+    assert gate(train_stylegan2.script(True), graph=True, mode='aug') == \
+        (None, "--graph captures the ContraD D-step (--mode contrad), not 'aug' -> eager")
+    critic, why_not = gate(train_stylegan2.script(True), graph=True, mode='contrad')
+    assert isinstance(critic, train_stylegan2.GraphedCritic) and why_not is None
+    # image sizes
+    assert data.IMAGE_SIZES == {'cifar10': (32, 32, 3), 'cifar100': (32, 32, 3), 'cifar10_hflip': (32, 32, 3),
+                                'cifar100_hflip': (32, 32, 3), 'celeba128': (128, 128, 3), 'afhq_cat': (512, 512, 3),
+                                'afhq_dog': (512, 512, 3), 'afhq_wild': (512, 512, 3)}
+    assert train_stylegan2.IMAGE_SIZES == data.IMAGE_SIZES
+    assert train_gan.IMAGE_SIZES == {'cifar10': (32, 32, 3), 'cifar100': (32, 32, 3), 'cifar10_hflip': (32, 32, 3)}
+    assert train_gan.SCRIPT.image_sizes is train_gan.IMAGE_SIZES and 'afhq_dog' not in train_gan.IMAGE_SIZES
