@@ -433,9 +433,10 @@ __global__ __launch_bounds__(256) void wino22_filter_kernel(const float* __restr
 // phases x 64 channels) x 64 output channels x all 9 xi x one split of the tile axis, chunks of 8 tiles; eight waves, each a
 // 32 x 32 sub-block with nine accumulator tiles.  LDS rows are contraction-major ([xi][tile][row], fragments ds_read_b32
 // pairs 2 tiles apart) as in wino_wgrad_kernel; waves 0-3 transform x (raw boxes -> B^T d B, a 3x3 tile x 4 channels per
-// thread), waves 4-7 move x and gy (gy through G gy G^T on the way; the (1,1) plane is the tile's pixel sum = the bias
-// gradient, summed in the blocks of the first row block).  The block's 2x2 taps per phase go into its slab of the workspace
-// in the packed-weight layout [(kh * 4 + kw) * C + c][K]; wgrad_reduce_kernel sums the slabs.
+// thread) and carry gy (global -> G gy G^T -> LDS, one row of a 2x2 tile per thread; the (1,1) plane is the tile's pixel
+// sum = the bias gradient, written out by the blocks of the first row block), waves 4-7 move x.  No staging store sits
+// behind a branch: a join makes the compiler wait for every load in flight.  The block's 2x2 taps per phase go into its
+// slab of the workspace in the packed-weight layout [(kh * 4 + kw) * C + c][K]; wgrad_reduce_kernel sums the slabs.
 constexpr int WV_PL = 8 * 128, WG_PL = 8 * 64;        // dwords per plane: V 8 tiles x 128 rows, Gy 8 tiles x 64 cols
 constexpr int WV_SZ = 9 * WV_PL, WG_SZ = 9 * WG_PL;
 constexpr int W_STAGE = WV_SZ + WG_SZ;                // 13 824 dwords
@@ -444,6 +445,7 @@ constexpr int W_RAWSZ = W_RAWPX * 128;                // ... x 128 rows' channel
 constexpr int W_RAW0 = 2 * W_STAGE;
 constexpr int W_LDS_DWORDS = 2 * W_STAGE + 2 * W_RAWSZ;   // 161 792 B
 constexpr int W_NRAW = 7;                             // 50 px x 32 quads / 256
+constexpr int W_NRAW_FULL = 5;                        // pieces that lie inside every box (45 px x 32 quads = 1440 >= 5 x 256)
 
 struct WArgs {
   const float* x;      // [N][H][W][ldx]     H = 2 GH
@@ -484,12 +486,18 @@ __device__ __forceinline__ void wbody(const WArgs& p, float* smem) {
 
   // ---- movers, raw x: items (box, image, pixel, channel quad) ----
   int xfix[W_NRAW], xpk[W_NRAW];       // xpk: image << 24 | x row offset + 64 << 12 | x col offset + 64 (relative to the chunk's first x pixel)
+  int wrRaw[W_NRAW - W_NRAW_FULL];     // LDS dword offsets of the pieces that can wrap
   const int qpb = p.CPB >> 2;          // channel quads per box
-  const int nitems = NBOX * p.CNIMG * BHW * qpb;
+  const int nitems = NBOX * p.CNIMG * BHW * qpb;      // 1440 (5 x 9 box) or 1600 (2 images x 5 x 5); Wino22Wgrad::ok (wino_host.h)
+                                                      // admits only 256 * W_NRAW_FULL <= nitems <= 256 * W_NRAW: one wrap at most
   if constexpr (ROLE == 1) {
 #pragma unroll
     for (int i = 0; i < W_NRAW; ++i) {
-      const int item = tid + 256 * i;
+      // (pieces past the box repeat pieces of its start -- the same load, the same store: no branch around the stores, whose
+      // joins merge the wait counts of the loads in flight, as in wino_wgrad_kernel)
+      const int lin_item = tid + 256 * i;
+      const int item = (i >= W_NRAW_FULL && lin_item >= nitems) ? lin_item - nitems : lin_item;
+      if (i >= W_NRAW_FULL) wrRaw[i - W_NRAW_FULL] = item * 4;
       const int cq = item % qpb, t1 = item / qpb;
       const int px = t1 % BHW, t2 = t1 / BHW;
       const int im = t2 % p.CNIMG, box = t2 / p.CNIMG;
@@ -499,22 +507,23 @@ __device__ __forceinline__ void wbody(const WArgs& p, float* smem) {
       const int pp = ph >> 1, pq = ph & 1;
       // box row r of phase p <-> x row 2 (row0_grid + r + s_p) + p, s_1 = -1, s_0 = 0: relative to the chunk's first grid row: 2 r - 1 | 2 r
       const int dr = 2 * r - pp, dc = 2 * c - pq;
-      xpk[i] = (item < nitems) ? (im << 24 | (dr + 64) << 12 | (dc + 64)) : (127 << 24);
+      xpk[i] = im << 24 | (dr + 64) << 12 | (dc + 64);
       xfix[i] = ((im * p.H + dr) * p.W + dc) * p.ldx * 4 + (c0 + cq * 4) * 4;
     }
   }
-  // gy: (channel quad, tile) on the first 128 threads of the TRANSFORM waves (the movers' registers hold the x pieces in flight:
-  // with gy's four on top they spilled inside the loop)
-  const int gq = tid & 15, gt = (tid >> 4) & 7;
-  const bool g_on = tid < 128;
+  // gy: (channel quad, tile row, tile) on the TRANSFORM waves (the movers' registers hold the x pieces in flight: with gy's on
+  // top they spilled inside the loop).  A thread loads ONE ROW of the 2x2 gy tile and stores that row's three planes; the lane
+  // 8 further on (row_ror:8) holds the other row, and the middle row of G gy G^T is made from both.  Lane bits: 0-2 and 4 the
+  // channel quad, 3 the row: the 8 lanes of a ds_write_b128 group store 128 contiguous bytes of one plane.
+  const int gq = (tid & 7) | ((tid >> 1) & 8), gh = (tid >> 3) & 1, gt = tid >> 5;
   int gfix = 0, gimg = 0;
   if constexpr (ROLE == 0) {
     gimg = gt >> p.sh_cthw;
     const int ty = (gt >> p.sh_ctw) & (p.CTH - 1), tx = gt & (p.CTW - 1);
-    gfix = ((gimg * p.GH + 2 * ty) * p.GW + 2 * tx) * p.ldy * 4 + (kb * 64 + gq * 4) * 4;
+    gfix = ((gimg * p.GH + 2 * ty + gh) * p.GW + 2 * tx) * p.ldy * 4 + (kb * 64 + gq * 4) * 4;
   }
   Stream sx = stream_at(q_begin), sg = stream_at(q_begin);
-  float4 rraw[W_NRAW], rg[4];
+  float4 rraw[W_NRAW], rg[2];
   float4 colacc = make_float4(0.f, 0.f, 0.f, 0.f);
   const bool do_bias = p.bias_ws != nullptr && rb == 0;
 
@@ -535,39 +544,41 @@ __device__ __forceinline__ void wbody(const WArgs& p, float* smem) {
   };
   auto store_raw = [&](int stage) {
 #pragma unroll
-    for (int i = 0; i < W_NRAW; ++i)
-      if (tid + 256 * i < nitems) *reinterpret_cast<float4*>(smem + W_RAW0 + stage * W_RAWSZ + (tid + 256 * i) * 4) = rraw[i];
+    for (int i = 0; i < W_NRAW_FULL; ++i)
+      *reinterpret_cast<float4*>(smem + W_RAW0 + stage * W_RAWSZ + (tid + 256 * i) * 4) = rraw[i];
+#pragma unroll
+    for (int j = 0; j < W_NRAW - W_NRAW_FULL; ++j)      // the pieces that can wrap
+      *reinterpret_cast<float4*>(smem + W_RAW0 + stage * W_RAWSZ + wrRaw[j]) = rraw[W_NRAW_FULL + j];
   };
   auto load_gy = [&]() {
-    const bool on = g_on && sg.q < q_end && sg.ng * p.CNIMG + gimg < p.N;
+    const bool on = sg.q < q_end && sg.ng * p.CNIMG + gimg < p.N;
     const float* base = p.gy + (size_t)sg.ng * p.CNIMG * p.GH * p.GW * p.ldy;
     const __amdgpu_buffer_rsrc_t rs = rsrc(base, sg.q < q_end);
     const unsigned v = on ? (unsigned)(gfix + ((sg.cy * 2 * p.CTH * p.GW + sg.cx * 2 * p.CTW) * p.ldy) * 4) : OOB;
-    const unsigned dc = (unsigned)p.ldy * 4u, dr = (unsigned)(p.GW * p.ldy) * 4u;
-    rg[0] = bload4(rs, v, 0); rg[1] = bload4(rs, v + dc, 0);
-    rg[2] = bload4(rs, v + dr, 0); rg[3] = bload4(rs, v + dr + dc, 0);
+    rg[0] = bload4(rs, v, 0); rg[1] = bload4(rs, v + (unsigned)p.ldy * 4u, 0);
     step(sg);
   };
   auto add4 = [](const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); };
+  auto other_row = [](const float4& a) {       // the value of the lane 8 further on in its row of 16: the tile's other gy row
+    auto ror8 = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true)); };
+    return make_float4(ror8(a.x), ror8(a.y), ror8(a.z), ror8(a.w));
+  };
   const int wrG = WV_SZ + gt * 64 + gq * 4;
-  auto gy_stage_store = [&](int bufoff) {      // G gy G^T, G = [[1,0],[1,1],[0,1]]: 9 planes x float4
-    if (!g_on) return;
-    const float4 m0 = add4(rg[0], rg[2]), m1 = add4(rg[1], rg[3]);      // middle row: g0. + g1.
-    float* dst = smem + bufoff + wrG;
-    *reinterpret_cast<float4*>(dst + 0 * WG_PL) = rg[0];
-    *reinterpret_cast<float4*>(dst + 1 * WG_PL) = add4(rg[0], rg[1]);
-    *reinterpret_cast<float4*>(dst + 2 * WG_PL) = rg[1];
-    *reinterpret_cast<float4*>(dst + 3 * WG_PL) = m0;
+  const int wrGrow = wrG + gh * 6 * WG_PL, wrGmid = wrG + (3 + 2 * gh) * WG_PL;
+  // G gy G^T, G = [[1,0],[1,1],[0,1]]: 9 planes x float4.  Row gh: planes 6 gh + (0, 1, 2) = (g.0, g.0 + g.1, g.1).  Middle row:
+  // m0 = g00 + g10 (plane 3, stored by row 0), m1 = g01 + g11 (plane 5, by row 1), m0 + m1 (plane 4: both rows hold the same
+  // value and store it to the same place; it is the tile's pixel sum = the bias gradient, kept by every block and written
+  // out by those of the first row block).  The sums are the ones one thread made before: a + b is commutative bit for bit.
+  auto gy_stage_store = [&](int bufoff) {
+    const float4 m0 = add4(rg[0], other_row(rg[0])), m1 = add4(rg[1], other_row(rg[1]));
     const float4 mm = add4(m0, m1);
-    *reinterpret_cast<float4*>(dst + 4 * WG_PL) = mm;
-    *reinterpret_cast<float4*>(dst + 5 * WG_PL) = m1;
-    *reinterpret_cast<float4*>(dst + 6 * WG_PL) = rg[2];
-    *reinterpret_cast<float4*>(dst + 7 * WG_PL) = add4(rg[2], rg[3]);
-    *reinterpret_cast<float4*>(dst + 8 * WG_PL) = rg[3];
-    if (do_bias) {
-      asm volatile("" ::: "memory");
-      colacc = add4(colacc, mm);
-    }
+    float* row = smem + bufoff + wrGrow;
+    *reinterpret_cast<float4*>(row + 0 * WG_PL) = rg[0];
+    *reinterpret_cast<float4*>(row + 1 * WG_PL) = add4(rg[0], rg[1]);
+    *reinterpret_cast<float4*>(row + 2 * WG_PL) = rg[1];
+    *reinterpret_cast<float4*>(smem + bufoff + wrGmid) = make_float4(gh ? m1.x : m0.x, gh ? m1.y : m0.y, gh ? m1.z : m0.z, gh ? m1.w : m0.w);
+    *reinterpret_cast<float4*>(smem + bufoff + wrG + 4 * WG_PL) = mm;
+    colacc = add4(colacc, mm);
   };
 
   // ---- transform waves: (row quad, tile) ----
@@ -699,7 +710,7 @@ __device__ __forceinline__ void wbody(const WArgs& p, float* smem) {
   if (do_bias) {      // uniform: sum the eight tiles' partial column sums
     __syncthreads();
     float* red = smem;
-    if (ROLE == 0 && g_on) *reinterpret_cast<float4*>(red + gt * 64 + gq * 4) = colacc;
+    if (ROLE == 0 && gh == 0) *reinterpret_cast<float4*>(red + gt * 64 + gq * 4) = colacc;
     __syncthreads();
     if (ROLE == 1 && tid < 64) {
       float sum = 0.f;

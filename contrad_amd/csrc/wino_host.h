@@ -421,6 +421,11 @@ struct Wino22Wgrad {
     if (!grid_ok(d->Ho) || !grid_ok(d->Wo)) return false;
     if ((d->C != 64 && (d->C & 127)) || (d->K & 63) || (d->ldx & 3) || (d->ldy & 3)) return false;
     if (2ll * d->H * d->W * std::max(d->ldx, d->ldy) * 4 >= (1ll << 31)) return false;
+    // the movers' raw pieces (box, image, pixel, channel quad) wrap once at most and stay inside a raw stage: a grid or channel
+    // rule widened above must not reach the kernel with a box it has no room for
+    const Args a = args(d);
+    const int raw_items = (128 / a.CPB) * a.CNIMG * (2 * a.CTH + 1) * (2 * a.CTW + 1) * (a.CPB / 4);
+    if (raw_items < 256 * wino22::W_NRAW_FULL || raw_items > 256 * wino22::W_NRAW || raw_items * 4 > wino22::W_RAWSZ) return false;
     return true;
   }
   static Args args(const contrad_conv_desc* d) {
