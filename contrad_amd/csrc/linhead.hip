@@ -108,6 +108,14 @@ __global__ __launch_bounds__(256) void linhead_logits_kernel(const float* __rest
     stage_tile(fs, F, ldf, N, K, r0, LH_TM, k0, fvec != 0);
     stage_tile(wsm, W, K, C, K, 0, 16 * CT, k0, wvec != 0);
     __syncthreads();
+    // A chunk's 64 products are summed on their own and enter the split's sum as one term: with few K-splits (from about 2^16
+    // rows on the plan has one) a single fp32 chain would run over all of K and lose about a decimal digit.  One chunk per split:
+    // bitwise as before.  Costs 4 * CT registers; the kernel's time with them has not been measured.
+    float cacc[4][CT];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < CT; ++j) cacc[i][j] = 0.f;
 #pragma unroll 4
     for (int q = 0; q < LH_KC / 4; ++q) {
       float4 a[4], b[CT];
@@ -118,8 +126,12 @@ __global__ __launch_bounds__(256) void linhead_logits_kernel(const float* __rest
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < CT; ++j) fma4(acc[i][j], a[i], b[j]);
+        for (int j = 0; j < CT; ++j) fma4(cacc[i][j], a[i], b[j]);
     }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < CT; ++j) acc[i][j] += cacc[i][j];
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {

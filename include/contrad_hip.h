@@ -44,7 +44,14 @@ typedef struct {
   int ldw;          /* floats between rows of the packed weight [KH*KW*C][ldw] (>= K)  */
 } contrad_conv_desc;
 
-/* Alignment: when the channel counts / leading dimensions are multiples of 4 the kernels use 16-byte accesses, and
+/* Sizes: N * H * W * ldx, N * Ho * Wo * ldy and KH * KW * C * ldw are each below 2^31 ELEMENTS (leading dimensions counted):
+ * every entry point returns -EINVAL and every plan / workspace / *_ok query -22 from 2^31 on.  Bytes are not limited: an
+ * operand may span up to 8 GiB, base pointers are 64-bit.  What is relative to a block's or an image's base is a 32-bit byte
+ * offset below 2^31: a shape whose block would reach further (nimg * H * W * max(ldi, ldo) * 4 >= 2^31 for a Winograd family,
+ * one image of 2^31 bytes for the branch-free FIR forms of contrad_upfirdn2d) is refused by that family's guard and runs on a
+ * family that can address it -- slower, never wrong (tests/test_far_offsets_gpu.py, tests/test_far_offsets_cpu.py).
+ *
+ * Alignment: when the channel counts / leading dimensions are multiples of 4 the kernels use 16-byte accesses, and
  * x, wp, y, gy, dx, act_ref and the workspaces must then be 16-byte aligned (-EINVAL otherwise).
  *
  * y[n,ho,wo,k] = gain * lrelu_slope( sum_{kh,kw,c} x[n,ho*s-p+kh,wo*s-p+kw,c] * wp[(kh,kw,c),k] + bias[k] )
@@ -325,7 +332,9 @@ long long contrad_rgb_conv_wgrad_workspace_bytes(int N, int Cin, int H, int W, i
 int contrad_rgb_conv_wgrad(const float* img, const float* gy, float* dwp, float* dbias, int N, int Cin,
                            int H, int W, int K, int k, int ldy, int ldw, float in_scale, float in_shift,
                            float* workspace, long long workspace_bytes, contrad_stream_t stream);
-/* Stride-1 transposed conv onto C <= 4 channels, NHWC in -> NCHW out,
+/* The three RGB-end entry points index with 64-bit element offsets and have no element limit: gy of contrad_rgb_conv_dgrad may
+ * hold more than 2^31 floats (tests/test_far_offsets_gpu.py runs 1030 x 512 x 512 x 16 into 4 GiB of images).
+ * Stride-1 transposed conv onto C <= 4 channels, NHWC in -> NCHW out,
  * out = f(acc + bias + residual) * out_scale + out_shift, f = identity (act 0) or tanh (act 1); `mod` (may be
  * NULL) is a per-sample [N][K] modulation of the input channels, `residual` (may be NULL) an NCHW tensor:
  * G_SNDCGAN's last ConvTranspose2d+Tanh+0.5x+0.5 (models/gan/sndcgan.py:37-38,47), d loss / d image of D's first
