@@ -1186,6 +1186,71 @@ def knn_select(S, n, labels, n_classes, k, inv_temp):
     return idx, val, scores, pred
 
 
+# ---- precision / recall / density / coverage (csrc/prdc.hip) ----
+def _chk_S(S, n):
+    _chk(S, 'S')
+    if S.dim() != 2 or S.shape[0] < 1:
+        raise RuntimeError('contrad_hip: S must be a non-empty (M, ldS) matrix')
+    if not 1 <= int(n) <= S.shape[1]:
+        raise RuntimeError('contrad_hip: n = %d outside [1, %d] (the columns of S)' % (n, S.shape[1]))
+    return S.shape[0], _ld(S), int(n)
+
+
+def _chk_vec(t, name, numel, dtype):
+    if t is None:
+        return
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or t.dim() != 1 or t.numel() != numel \
+            or not t.is_contiguous():
+        raise RuntimeError('contrad_hip: %s must be a contiguous CUDA %s vector of %d elements'
+                           % (name, str(dtype).replace('torch.', ''), numel))
+
+
+def _as_int(t):
+    return ctypes.cast(_p(t), ctypes.POINTER(ctypes.c_int))                    # (the header's int* maps to a typed pointer)
+
+
+def prdc_kth(S, n, k, self0=-1, out=None):
+    """thr (M,): per row of ``S`` (M, ldS >= n; columns [0, n) are read) the k-th largest value, column ``self0 + i`` left
+    out of row i when it lies in [0, n) (``self0 < 0``: nothing is left out).  ``out``: a float32 CUDA vector of M elements
+    to write into.  contrad_prdc_kth's contract (include/contrad_hip.h)."""
+    M, ldS, n = _chk_S(S, n)
+    k, self0 = int(k), int(self0)
+    remain = n - 1 if 0 <= self0 < n else n
+    if not 1 <= k <= remain:
+        raise RuntimeError('contrad_hip: k = %d outside [1, %d] (n = %d, self0 = %d)' % (k, remain, n, self0))
+    if out is None:
+        out = torch.empty((M,), device=S.device, dtype=torch.float32)
+    _chk_vec(out, 'out', M, torch.float32)
+    lib().call('contrad_prdc_kth', _p(S), ctypes.c_longlong(ldS), M, n, k, ctypes.c_longlong(self0), _p(out), _stream())
+    return out
+
+
+def prdc_count(S, n, thr_row=None, thr_col=None, row_hits=None, col_hits_c=None, col_hits_r=None):
+    """One pass over ``S`` (M, ldS >= n): with ``thr_col`` (n,) ``row_hits`` (M,) int32 is WRITTEN (a new vector unless given)
+    and ``col_hits_c`` (n,) int32 ADDED to; with ``thr_row`` (M,) ``col_hits_r`` (n,) int32 is ADDED to.  The column arrays
+    are the caller's (zeroed once, one call per row chunk).  Returns ``row_hits`` (None without ``thr_col``).
+    contrad_prdc_count's contract (include/contrad_hip.h)."""
+    M, ldS, n = _chk_S(S, n)
+    if thr_row is None and thr_col is None:
+        raise RuntimeError('contrad_hip: prdc_count needs thr_row or thr_col')
+    _chk_vec(thr_row, 'thr_row', M, torch.float32); _chk_vec(thr_col, 'thr_col', n, torch.float32)
+    if thr_col is not None:
+        if col_hits_c is None:
+            raise RuntimeError('contrad_hip: thr_col adds into col_hits_c')
+        if row_hits is None:
+            row_hits = torch.empty((M,), device=S.device, dtype=torch.int32)
+    else:
+        row_hits = None
+    if thr_row is not None and col_hits_r is None:
+        raise RuntimeError('contrad_hip: thr_row adds into col_hits_r')
+    _chk_vec(row_hits, 'row_hits', M, torch.int32); _chk_vec(col_hits_c, 'col_hits_c', n, torch.int32)
+    _chk_vec(col_hits_r, 'col_hits_r', n, torch.int32)
+    lib().call('contrad_prdc_count', _p(S), ctypes.c_longlong(ldS), M, n, _p(thr_row), _p(thr_col), _as_int(row_hits),
+               _as_int(col_hits_c if thr_col is not None else None), _as_int(col_hits_r if thr_row is not None else None),
+               _stream())
+    return row_hits
+
+
 # ---- cDDLS sampling (csrc/cddls.hip) ----
 def _flat_f32(t, name):
     _chk(t, name)

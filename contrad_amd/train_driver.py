@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import config
+from . import config, prdc
 from .augment import get_augment
 from .data import loader_for
 from .engine import GradAllReducer, setup_grad_exchange
@@ -74,12 +74,13 @@ def monitor_help(shows):
 def make_parser(description, layout):
     """``layout``: the script's flags in ``--help`` order -- the name of a common flag, or ``(name, kwargs)`` for a flag of
     the script's own or for what it sets differently on a common one.  The monitoring hooks' flags
-    (knn.add_hook_arguments) come last."""
+    (knn.add_hook_arguments, then prdc.add_hook_arguments) come last."""
     parser = ArgumentParser(description=description)
     for item in layout:
         name, own = (item, {}) if isinstance(item, str) else item
         parser.add_argument(name, **dict(COMMON_FLAGS.get(name, {}), **own))
     add_hook_arguments(parser)
+    prdc.add_hook_arguments(parser)
     return parser
 
 
@@ -183,6 +184,7 @@ def _loader(P, script, options, image_size, rank, world, dev, log):
 def build_run(P, script):
     """Everything between the parsed command line and the first iteration -> the run: P, options, G, D, g_ema (or None),
     opt_G, opt_D, reducers, loader, graphed, and what ``run_loop`` needs around them."""
+    H = prdc.check_hook_arguments(P)                                # (refusals that need no device come first)
     if P.comment:
         P.comment = '_' + P.comment
     P.gin_stem = Path(P.gin_config).stem
@@ -239,18 +241,23 @@ def build_run(P, script):
     for line in (script.start_up_lines(P) if script.start_up_lines is not None else ()):
         log(line)
 
-    monitor = knn_monitor = None
+    monitor = knn_monitor = prdc_monitor = None
     if P.monitor and rank == 0:
         monitor = Monitor(logdir, P.architecture, image_size, dev, P.seed, no_gif=P.no_gif, P=P)
         loader = LastBatch(loader)                                  # the preview shows the batch the step drew
     if P.knn_data and rank == 0:
         knn_monitor = KNNMonitor(logdir, P.architecture, image_size, dev, P.seed, P.knn_data, k=P.knn_k, temp=P.knn_temp, P=P)
+    if H.prdc_data and rank == 0:
+        prdc_monitor = prdc.PRDCMonitor(logdir, P.architecture, image_size, dev, P.seed, H.prdc_data, H.prdc_encoder,
+                                        encoder_arch=H.prdc_encoder_arch, k=H.prdc_k, n_fake=H.prdc_n, best=H.prdc_best,
+                                        resumed_step=starting_step - 1, P=P)
     graphed, why_not = graph_gate(P, script)
     if why_not:
         log(why_not)
     return SimpleNamespace(P=P, options=options, G=G, D=D, g_ema=g_ema, opt_G=opt_G, opt_D=opt_D, reducers=reducers,
                            loader=loader, graphed=graphed, nets=nets, rank=rank, world=world, logdir=logdir, log=log,
-                           starting_step=starting_step, monitor=monitor, knn_monitor=knn_monitor)
+                           starting_step=starting_step, monitor=monitor, knn_monitor=knn_monitor,
+                           prdc_monitor=prdc_monitor)
 
 
 def run_loop(run, iteration):
@@ -276,7 +283,15 @@ def run_loop(run, iteration):
                 run.monitor.update(step, run.g_ema if run.g_ema is not None else run.G, run.loader.last, P.augment_fn)
             if run.knn_monitor is not None:
                 log('[Steps %7d] [kNN Acc@1 %.3f]' % (step, run.knn_monitor.update(step, run.D)['acc@1']))
-            for tag in (('', f'_{step}') if step % P.save_every == 0 else ('',)):
+            tags = ('', f'_{step}') if step % P.save_every == 0 else ('',)
+            if run.prdc_monitor is not None:
+                m = run.prdc_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)
+                log('[Steps %7d] [precision %.4f] [recall %.4f] [density %.4f] [coverage %.4f]%s' % (
+                    step, m['precision'], m['recall'], m['density'], m['coverage'],
+                    ' [best %s]' % run.prdc_monitor.metric if m['improved'] else ''))
+                if m['improved']:                                   # the reference's best-checkpoint names: this step's networks
+                    tags += ('_best',)
+            for tag in tags:
                 for name, net in run.nets.items():
                     torch.save(net.state_dict(), f'{logdir}/{name}{tag}.pt')
             torch.save({'epoch': step, 'optim_G': run.opt_G.state_dict(), 'optim_D': run.opt_D.state_dict()},

@@ -742,6 +742,32 @@ int contrad_knn_select(const float* S, long long ldS, int M, int n, const long l
                        float inv_temp, int* idx, float* val, float* scores, int* pred, void* workspace,
                        long long workspace_bytes, contrad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Precision / recall / density / coverage on a similarity matrix (csrc/prdc.hip): k-th largest per row, hit counts.
+ * An addition of this project (the reference selects by FID): the k-NN manifold metrics of Kynkaanniemi et al. 2019
+ * and Naeem et al. 2020 on frozen, L2-normalised features, where "inside the k-NN ball" is "similarity >= threshold".
+ * ---------------------------------------------------------------------------------------------- */
+/* thr[i], i in [0, M): the k-th largest value of row i of S[M][ldS] over the columns [0, n), column self0 + i left out
+ * when it lies in [0, n) (row i of a chunk is global row self0 + i: exclusion is by index, whatever the value there);
+ * self0 < 0 leaves nothing out.  The order is contrad_knn_select's: value descending, then column ascending; -0.0 and
+ * +0.0 compare equal, NaN compares below every number, so a row with fewer than k numbers yields a NaN.  thr[i] is the
+ * very float of the column that holds the k-th place.  1 <= k <= the columns that remain in the shortest row (n - 1 if
+ * 0 <= self0 < n, else n), ldS >= n; -EINVAL (before any GPU call) on a null pointer or a violated limit.  One launch,
+ * one workgroup per row, no workspace, k not bound by LDS; every output element is written once; bitwise repeatable. */
+int contrad_prdc_kth(const float* S, long long ldS, int M, int n, int k, long long self0, float* thr,
+                     contrad_stream_t stream);
+/* One pass over S[M][ldS] (only columns [0, n) are read), hit(a, t) = a >= t (inclusive; false when either is NaN):
+ *   row_hits[i]    = #{j : hit(S[i][j], thr_col[j])}, written (zeroed by a memset node on `stream`, then added to);
+ *   col_hits_c[j] += #{i : hit(S[i][j], thr_col[j])};
+ *   col_hits_r[j] += #{i : hit(S[i][j], thr_row[i])}.
+ * The caller zeroes the two column arrays once and calls once per row chunk.  thr_col == NULL skips row_hits and
+ * col_hits_c (both may then be NULL), thr_row == NULL skips col_hits_r; at least one of the two is given.  ldS >= n;
+ * -EINVAL (before any GPU call) on a missing pointer or a violated limit.  16-byte loads when S is 16-byte aligned and
+ * ldS a multiple of 4, scalar loads otherwise and in a row's tail.  Integer adds only (no float atomics): the sums do not
+ * depend on the order of arrival and two calls are bitwise equal. */
+int contrad_prdc_count(const float* S, long long ldS, int M, int n, const float* thr_row, const float* thr_col,
+                       int* row_hits, int* col_hits_c, int* col_hits_r, contrad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
