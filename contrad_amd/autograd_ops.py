@@ -104,7 +104,8 @@ class ConvDgradFn(Function):
     def backward(ctx, h):
         gy, wp = ctx.saved_tensors
         g_gy = Conv2dFn.apply(h, wp, ctx.geom) if ctx.needs_input_grad[0] else None
-        g_wp = ConvWgradFn.apply(h, gy, ctx.geom, tuple(wp.shape)) if ctx.needs_input_grad[1] else None
+        g_wp = ConvWgradFn.apply(h, gy, ctx.geom, tuple(wp.shape)) if (ctx.needs_input_grad[1]
+                                                                      and not _INPUT_GRAD_ONLY) else None
         return g_gy, g_wp, None, None
 
 
@@ -293,7 +294,8 @@ class RgbDgradFn(Function):
         C, (k, scale) = ctx.cfg
         K = g.shape[3]
         g_g = RgbConvFn.apply(h, wp, K, (k, scale, 0.0)) if ctx.needs_input_grad[0] else None
-        g_wp = RgbWgradFn.apply(h, g, (k, scale, 0.0), tuple(wp.shape)) if ctx.needs_input_grad[1] else None
+        g_wp = RgbWgradFn.apply(h, g, (k, scale, 0.0), tuple(wp.shape)) if (ctx.needs_input_grad[1]
+                                                                             and not _INPUT_GRAD_ONLY) else None
         return g_g, g_wp, None, None
 
 

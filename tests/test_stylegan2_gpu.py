@@ -39,7 +39,8 @@ def test_upfirdn2d_against_reference(golden, tag):
 
 
 def test_upfirdn2d_adjoint_and_double_backward():
-    """<blur(x), g> == <x, blur_backward(g)> and the backward of the backward is the forward (op/upfirdn2d.py:19-85)."""
+    """<blur(x), g> == <x, blur_backward(g)> and the backward of the backward is the forward (op/upfirdn2d.py:19-85).
+    (Float64 parity of both nodes to second order: tests/test_autograd_nodes_gpu.py, twins in tests/nodes_ref64.py.)"""
     from contrad_amd import autograd_ops as A
     g = torch.Generator(device='cuda').manual_seed(0)
     x = torch.randn(3, 9, 9, 8, device=DEV, generator=g, requires_grad=True)
@@ -70,7 +71,8 @@ def test_fused_bias_act(golden):
 def test_minibatch_stddev_node_family_against_torch_ops(B, splits):
     """The HIP minibatch-stddev channel (forward, backward, and the backward's backward that R1 needs) against the same layer
     written in differentiable torch ops (the round-3 implementation, discriminator.py:22-33): values, first-order input
-    gradient, and both second-order gradients (w.r.t. x and w.r.t. the incoming gradient), 1e-4."""
+    gradient, and both second-order gradients (w.r.t. x and w.r.t. the incoming gradient), 1e-4.
+    (All four quantities against float64: tests/test_autograd_nodes_gpu.py, twins in tests/nodes_ref64.py.)"""
     from contrad_amd.models.gan.stylegan2.discriminator import minibatch_stddev_batches, minibatch_stddev_nhwc
     g = torch.Generator(device='cuda').manual_seed(B)
     x0 = torch.randn(B, 4, 4, 32, device=DEV, generator=g)
