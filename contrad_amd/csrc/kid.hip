@@ -1,0 +1,128 @@
+// Kernel distance (KID) on a similarity matrix (gfx950): the one reduction of contrad_amd/kid.py.
+//
+//   kid_sums    sum over a block of S of (gamma * s + coef0)^3 with the column self0 + row left out of every row by
+//               index.  Every term is formed and added in float64.  A workgroup takes 4 * rpw rows x 256 columns
+//               (rpw = 32, or 4 where that would leave fewer than 1024 workgroups: a 1000 x 1000 block is 252 of them
+//               instead of 32); a wave takes every fourth row of the tile, a lane four consecutive columns (one 16-byte
+//               load where the address allows), four rows in flight: prdc_count_kernel's shape.  A lane sums its terms
+//               in row order, the wave by a butterfly, the four waves in wave order: one float64 partial per workgroup
+//               into the workspace.
+//   kid_final   one workgroup adds the partials in a fixed order (thread t the partials t, t + 256, ...; then a tree
+//               in LDS) and one thread adds the old value last when `accumulate` is set.
+// No atomics: out[0] depends on no order of arrival, two calls are bitwise equal.
+#include "../../include/contrad_hip.h"
+#include "common.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int KID_THREADS = 256;
+constexpr int KID_COLS = 256;                       // columns of a tile: 4 per lane
+constexpr int KID_RPW_MAX = 32;                     // rows per wave of a tile
+constexpr int KID_RPW_MIN = 4;
+constexpr long long KID_ENOUGH_BLOCKS = 1024;
+
+struct KidPlan {
+  long long ctiles, blocks;
+  int rpw;
+};
+
+// A function of (M, n) alone: the workspace query and the launcher agree, and so do two calls.
+KidPlan kid_plan(int M, int n) {
+  KidPlan p;
+  p.ctiles = cdivll(n, KID_COLS);
+  p.rpw = p.ctiles * cdivll(M, 4 * KID_RPW_MAX) >= KID_ENOUGH_BLOCKS ? KID_RPW_MAX : KID_RPW_MIN;
+  p.blocks = p.ctiles * cdivll(M, 4 * p.rpw);
+  return p;
+}
+
+__global__ __launch_bounds__(KID_THREADS) void kid_sums_kernel(const float* __restrict__ S, long long ldS, int M, int n,
+                                                               long long self0, double gamma, double coef0,
+                                                               double* __restrict__ partial, int ctiles, int rpw, int vec_ok) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int ct = blockIdx.x % ctiles, rt = blockIdx.x / ctiles;
+  const long long c0 = (long long)ct * KID_COLS + 4 * lane;
+  const long long r0 = (long long)rt * 4 * rpw + w;   // this wave's rows: r0, r0 + 4, ...
+  const int rows = r0 < M ? (int)min((long long)rpw, (M - r0 + 3) >> 2) : 0;
+  const bool whole = vec_ok && c0 + 3 < n;
+
+  double acc = 0.0;
+  for (int t0 = 0; t0 < rows; t0 += 4) {               // four rows in flight; a round's missing rows re-read the last one
+    float v[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long i = r0 + 4 * min(t0 + u, rows - 1);
+      const float* __restrict__ row = S + i * ldS;
+      if (whole) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(row + c0);
+        v[u][0] = x.x; v[u][1] = x.y; v[u][2] = x.z; v[u][3] = x.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[u][j] = c0 + j < n ? row[c0 + j] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const bool live = t0 + u < rows;                 // (uniform)
+      const long long excl = self0 >= 0 ? self0 + r0 + 4 * (t0 + u) : -1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const double x = gamma * (double)v[u][j] + coef0;
+        const bool in = live && c0 + j < n && c0 + j != excl;     // left out by index: a select, so a NaN there is not seen
+        acc += in ? x * x * x : 0.0;
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if (lane == 0) red[w] = acc;
+  __syncthreads();
+  if (tid == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(KID_THREADS) void kid_final_kernel(const double* __restrict__ partial, int nb, int accumulate,
+                                                                double* __restrict__ out) {
+  __shared__ double red[KID_THREADS];
+  const int tid = threadIdx.x;
+  double a = 0.0;
+  for (int i = tid; i < nb; i += KID_THREADS) a += partial[i];
+  red[tid] = a;
+  __syncthreads();
+  for (int s = KID_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) out[0] = accumulate ? out[0] + red[0] : red[0];   // the old value is added last
+}
+
+}  // namespace
+
+extern "C" long long contrad_kid_sums_workspace_bytes(int M, int n) {
+  if (M < 1 || n < 1) return -22;
+  const KidPlan p = kid_plan(M, n);
+  if (p.blocks > 0x7fffffffll) return -22;
+  return p.blocks * (long long)sizeof(double);
+}
+
+extern "C" int contrad_kid_sums(const float* S, long long ldS, int M, int n, long long self0, double gamma, double coef0,
+                                int accumulate, double* out, void* workspace, long long workspace_bytes,
+                                contrad_stream_t stream) {
+  CONTRAD_ARG(S && out);
+  CONTRAD_ARG(M >= 1 && n >= 1 && ldS >= n);
+  CONTRAD_ARG(isfinite(gamma) && isfinite(coef0));
+  const KidPlan p = kid_plan(M, n);
+  CONTRAD_ARG(p.blocks <= 0x7fffffffll);
+  CONTRAD_ARG(workspace && workspace_bytes >= p.blocks * (long long)sizeof(double));
+  CONTRAD_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)out & 7) == 0);
+  const int vec_ok = (ldS % 4 == 0 && ((uintptr_t)S & 15) == 0) ? 1 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  double* partial = (double*)workspace;
+  hipLaunchKernelGGL(kid_sums_kernel, dim3((unsigned)p.blocks), dim3(KID_THREADS), 0, st, S, ldS, M, n, self0, gamma, coef0,
+                     partial, (int)p.ctiles, p.rpw, vec_ok);
+  CONTRAD_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kid_final_kernel, dim3(1), dim3(KID_THREADS), 0, st, partial, (int)p.blocks, accumulate ? 1 : 0, out);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}

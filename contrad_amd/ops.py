@@ -7,6 +7,7 @@ Activations are NHWC: a tensor of shape (N, H, W, C) whose last dim is contiguou
 ``stride(2)`` is the leading dimension (allows channel-sliced views of wider buffers).
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -1249,6 +1250,32 @@ def prdc_count(S, n, thr_row=None, thr_col=None, row_hits=None, col_hits_c=None,
                _as_int(col_hits_c if thr_col is not None else None), _as_int(col_hits_r if thr_row is not None else None),
                _stream())
     return row_hits
+
+
+# ---- kernel distance (csrc/kid.hip) ----
+def kid_sums(S, n, self0=-1, gamma=1.0, coef0=1.0, out=None, accumulate=False):
+    """out (1,) float64: the sum over rows i and columns j < n of ``S`` (M, ldS >= n), column ``self0 + i`` left out of row
+    i by index (``self0 < 0``: nothing is left out), of (gamma * S[i][j] + coef0)^3, every term in float64.  ``out``: a
+    float64 CUDA vector of one element to write into -- or, with ``accumulate``, to add to (a row chunk passes its first
+    row as ``self0``).  No atomics: two calls are bitwise equal.  contrad_kid_sums's contract (include/contrad_hip.h)."""
+    M, ldS, n = _chk_S(S, n)
+    gamma, coef0 = float(gamma), float(coef0)
+    if not (math.isfinite(gamma) and math.isfinite(coef0)):
+        raise RuntimeError('contrad_hip: kid_sums needs a finite gamma and coef0, got %r, %r' % (gamma, coef0))
+    if out is None:
+        if accumulate:
+            raise RuntimeError('contrad_hip: kid_sums with accumulate adds to `out`')
+        out = torch.empty((1,), device=S.device, dtype=torch.float64)
+    _chk_vec(out, 'out', 1, torch.float64)
+    if out.device != S.device:
+        raise RuntimeError('contrad_hip: out is on %s, S on %s' % (out.device, S.device))
+    nbytes = lib().raw('contrad_kid_sums_workspace_bytes')(M, n)
+    if nbytes < 0:
+        raise RuntimeError('contrad_hip: bad kid_sums shape (%d)' % nbytes)
+    ws = _workspace(nbytes, S.device)
+    lib().call('contrad_kid_sums', _p(S), ctypes.c_longlong(ldS), M, n, ctypes.c_longlong(int(self0)), gamma, coef0,
+               1 if accumulate else 0, _p(out), _p(ws), ctypes.c_longlong(nbytes), _stream())
+    return out
 
 
 # ---- cDDLS sampling (csrc/cddls.hip) ----

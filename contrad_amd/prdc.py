@@ -26,7 +26,8 @@ fake rows, S_XY = X Y^T:
 ``--prdc_data`` / ``--prdc_encoder`` of the training scripts run this at every ``--evaluate_every`` through ``PRDCMonitor``,
 which follows ``KNNMonitor``: modules of its own, so that the training trajectory does not move by a bit.  ``--prdc_best
 METRIC`` keeps ``gen_best.pt`` / ``dis_best.pt`` (/ ``gen_ema_best.pt``), the names the reference gives its best-FID
-checkpoints, for the best value of that metric.
+checkpoints, for the best value of that metric.  ``--prdc_kid`` adds the kernel distance of contrad_amd/kid.py to every
+evaluation (``kid_<seed>.csv``; ``--prdc_best kid`` selects its minimum).
 """
 import json
 import os
@@ -44,6 +45,7 @@ from .models.gan import get_architecture
 
 METRICS = ('precision', 'recall', 'density', 'coverage')
 CSV_HEAD = 'step,' + ','.join(METRICS)
+BEST_CHOICES = METRICS + ('kid',)                                           # --prdc_best: kid (contrad_amd/kid.py) is minimised
 
 
 def _rows(feats, what, normalize):
@@ -233,19 +235,27 @@ class PRDCMonitor(object):
     generator's state dict at each evaluation; the fakes come from fixed latents of the eval seed.  The real features and
     t_R are computed once, here.  ``best``: one of METRICS; ``update`` then says whether the evaluation improved it (the
     caller writes the ``*_best.pt`` files); a run resumed from the checkpoint of step ``resumed_step`` reads the best value
-    up to that step back from its csv (``best_in_csv``)."""
+    up to that step back from its csv (``best_in_csv``).  ``kid`` (``--prdc_kid``): each evaluation also appends
+    ``step,kid,kid_std`` to ``kid_<eval_seed>.csv`` (contrad_amd/kid.py); ``best`` may then be ``'kid'``, which is minimised."""
 
     def __init__(self, logdir, architecture, image_size, device, seed, data_path, encoder_path, encoder_arch=None, k=5,
-                 n_fake=10000, batch=500, best=None, resumed_step=0, P=None):
+                 n_fake=10000, batch=500, best=None, resumed_step=0, P=None, kid=False):
+        from . import kid as kid_mod                                       # (kid.py is built on this module)
         real = load_images(data_path, 'x_train')
         if tuple(real.shape[1:]) != tuple(image_size):
             raise ValueError('%s: x_train holds %s images, the generator makes %s' % (data_path, tuple(real.shape[1:]), tuple(image_size)))
         check_k(k, len(real), n_fake)
-        if best is not None and best not in METRICS:
-            raise ValueError('--prdc_best %r (one of %s)' % (best, ', '.join(METRICS)))
+        if best is not None and best not in BEST_CHOICES:
+            raise ValueError('--prdc_best %r (one of %s)' % (best, ', '.join(BEST_CHOICES)))
+        if best == 'kid' and not kid:
+            raise ValueError('--prdc_best kid needs --prdc_kid')
+        if kid:
+            kid_mod.check_sizes(len(real), n_fake)
         self.k, self.n_fake, self.batch, self.device, self.metric = int(k), int(n_fake), int(batch), device, best
         self.eval_seed = eval_seed_of(seed)
         self.path = os.path.join(logdir, 'prdc_%d.csv' % self.eval_seed)
+        self.kid_path = os.path.join(logdir, 'kid_%d.csv' % self.eval_seed) if kid else None
+        self.n_real = len(real)
         with preserved_rng(device):                                        # the constructors draw the initial weights
             G, _ = get_architecture(architecture, image_size, P=P)
             _, E = get_architecture(encoder_arch or architecture, image_size)
@@ -259,29 +269,51 @@ class PRDCMonitor(object):
         if not os.path.exists(self.path):                                  # (a resumed run appends to its file)
             with open(self.path, 'w') as f:
                 f.write(CSV_HEAD + '\n')
-        elif best is not None:
+        elif best is not None and best != 'kid':
             self.best = best_in_csv(self.path, best, resumed_step)
+        if kid and not os.path.exists(self.kid_path):
+            with open(self.kid_path, 'w') as f:
+                f.write(kid_mod.CSV_HEAD + '\n')
+        elif best == 'kid':
+            self.best = kid_mod.best_in_csv(self.kid_path, resumed_step)
 
     def update(self, step, generator):
         """One evaluation of ``generator``'s weights (G, or g_ema in the StyleGAN2 loops) -> the metrics, with
-        ``improved``: the tracked metric rose above the best so far (False without ``best``; a tie keeps the earlier)."""
+        ``improved``: the tracked metric rose above (kid: fell below) the best so far (False without ``best``; a tie keeps
+        the earlier).  With ``kid`` the kernel distance of the same fake features (contrad_amd/kid.py: the subsets of the
+        eval seed, the same at every evaluation) comes as ``kid`` / ``kid_std`` and goes to ``kid_<eval_seed>.csv``."""
+        from . import kid as kid_mod
         with torch.no_grad(), preserved_rng(self.device):
             self.G.load_state_dict(generator.state_dict())
             self.G.eval()
             fake = sample_u8(self.G, self.n_fake, self.batch, self.eval_seed)
-            out = prdc_of(self.E, None, fake, self.k, self.batch, real_state=self.real_state)
+            _check_u8(fake, 'fake')
+            feats = extract_features(self.E, fake, self.batch)
+            out = prdc(None, feats, self.k, real_state=self.real_state, normalize=False)
+            if self.kid_path is not None:                                  # the same fake features, the same real rows (bankT)
+                d = kid_mod.kid(None, feats, seed=self.eval_seed, normalize=False, real_bank=(self.real_state[0], self.n_real))
+                out['kid'], out['kid_std'] = d['kid'], d['kid_std']
         line = csv_line(step, out)
         with open(self.path, 'a') as f:
             f.write(line + '\n')
+        if self.kid_path is not None:
+            kid_line = kid_mod.csv_line(step, out)
+            with open(self.kid_path, 'a') as f:
+                f.write(kid_line + '\n')
         out['improved'] = False
-        if self.metric is not None:
+        if self.metric == 'kid':
+            value = float(kid_line.split(',')[1])                          # as the csv keeps it; the smaller the better
+            if self.best is None or value < self.best:
+                self.best, out['improved'] = value, True
+        elif self.metric is not None:
             value = float(line.split(',')[1 + METRICS.index(self.metric)])      # as the csv keeps it: a resumed run compares alike
             if self.best is None or value > self.best:
                 self.best, out['improved'] = value, True
         return out
 
 
-HOOK_DEFAULTS = {'prdc_data': None, 'prdc_encoder': None, 'prdc_encoder_arch': None, 'prdc_k': 5, 'prdc_n': 10000, 'prdc_best': None}
+HOOK_DEFAULTS = {'prdc_data': None, 'prdc_encoder': None, 'prdc_encoder_arch': None, 'prdc_k': 5, 'prdc_n': 10000, 'prdc_best': None,
+                 'prdc_kid': False}
 
 
 def add_hook_arguments(parser):
@@ -300,13 +332,18 @@ def add_hook_arguments(parser):
     parser.add_argument('--prdc_k', type=int, **off, help='with --prdc_data: neighbours (default: 5)')
     parser.add_argument('--prdc_n', type=int, **off,
                         help='with --prdc_data: generated images per evaluation (default: 10000; x_train is used whole)')
-    parser.add_argument('--prdc_best', type=str, choices=METRICS, **off,
+    parser.add_argument('--prdc_best', type=str, choices=BEST_CHOICES, **off,
                         help='with --prdc_data: keep gen_best.pt / dis_best.pt (and gen_ema_best.pt) of the evaluation with the '
-                             'best value of this metric (the reference keeps these names for its best FID)')
+                             'best value of this metric (the reference keeps these names for its best FID); kid (needs '
+                             '--prdc_kid) is minimised')
+    parser.add_argument('--prdc_kid', action='store_true', **off,
+                        help='with --prdc_data: every evaluation also appends step,kid,kid_std to kid_<seed>.csv: the kernel '
+                             'distance (cubic kernel, gamma = coef0 = 1, 100 subsets of up to 1000) of the same fake features '
+                             'from the real set, comparable only under one --prdc_encoder file, never with Inception-based KID')
 
 
 def hook_options(P):
-    """The six hook flags of a parsed command line, defaults filled in."""
+    """The hook flags of a parsed command line, defaults filled in."""
     return SimpleNamespace(**{name: getattr(P, name, default) for name, default in HOOK_DEFAULTS.items()})
 
 
@@ -319,6 +356,8 @@ def check_hook_arguments(P):
     given = [name for name in HOOK_DEFAULTS if name != 'prdc_data' and hasattr(P, name)]
     if not H.prdc_data and given:
         raise ValueError('%s do%s nothing without --prdc_data FILE.npz' % (', '.join('--' + g for g in given), 'es' if len(given) == 1 else ''))
+    if H.prdc_best == 'kid' and not H.prdc_kid:
+        raise ValueError('--prdc_best kid needs --prdc_kid: without it no kernel distance is computed')
     return H
 
 

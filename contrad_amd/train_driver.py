@@ -250,7 +250,7 @@ def build_run(P, script):
     if H.prdc_data and rank == 0:
         prdc_monitor = prdc.PRDCMonitor(logdir, P.architecture, image_size, dev, P.seed, H.prdc_data, H.prdc_encoder,
                                         encoder_arch=H.prdc_encoder_arch, k=H.prdc_k, n_fake=H.prdc_n, best=H.prdc_best,
-                                        resumed_step=starting_step - 1, P=P)
+                                        resumed_step=starting_step - 1, P=P, kid=H.prdc_kid)
     graphed, why_not = graph_gate(P, script)
     if why_not:
         log(why_not)
@@ -288,7 +288,10 @@ def run_loop(run, iteration):
                 m = run.prdc_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)
                 log('[Steps %7d] [precision %.4f] [recall %.4f] [density %.4f] [coverage %.4f]%s' % (
                     step, m['precision'], m['recall'], m['density'], m['coverage'],
-                    ' [best %s]' % run.prdc_monitor.metric if m['improved'] else ''))
+                    ' [best %s]' % run.prdc_monitor.metric if m['improved'] and run.prdc_monitor.metric != 'kid' else ''))
+                if 'kid' in m:
+                    log('[Steps %7d] [kid %.6f +- %.6f]%s' % (
+                        step, m['kid'], m['kid_std'], ' [best kid]' if m['improved'] and run.prdc_monitor.metric == 'kid' else ''))
                 if m['improved']:                                   # the reference's best-checkpoint names: this step's networks
                     tags += ('_best',)
             for tag in tags:

@@ -9,7 +9,8 @@ of the reference (:227) is dropped (the all-reduce already synchronises); FID / 
 of scope -- losses are logged to stdout / log.txt; ``--monitor`` writes the reference's fixed-latent
 and augmented-real image grids as PNG / animated PNG (contrad_amd/evaluate/gan.py; off by default).  ``--knn_data FILE.npz`` logs the weighted
 kNN accuracy of D's features at every evaluation (contrad_amd/knn.py; an addition, off by default); ``--prdc_data FILE.npz --prdc_encoder FILE.pt`` logs
-precision / recall / density / coverage of the generator in a frozen encoder's features (contrad_amd/prdc.py; an addition, off by default).  Datasets: ``--data FILE.npz`` keeps the uint8
+precision / recall / density / coverage of the generator in a frozen encoder's features (contrad_amd/prdc.py; an addition, off by default).  With it ``--prdc_kid`` adds the kernel distance (KID)
+of the same features to ``kid_<seed>.csv`` (contrad_amd/kid.py; ``--prdc_best kid`` keeps the checkpoints of its minimum).  Datasets: ``--data FILE.npz`` keeps the uint8
 training set on the device and gathers every batch there (contrad_amd/data.py: the reference's sampler order, ToTensor's
 pixels, no torchvision); ``--synthetic`` (default when neither it nor torchvision is there) feeds uniform-random
 CIFAR-shaped batches; otherwise torchvision CIFAR-10/100 as the reference.

@@ -18,7 +18,8 @@ global loss of the DataParallel formulation, without the per-step parameter broa
 FID / GIF / tensorboard side paths are out of scope; ``--monitor`` writes the reference's image
 grids from ``g_ema`` as PNG / animated PNG (contrad_amd/evaluate/gan.py; off by default).  ``--knn_data FILE.npz`` logs the weighted kNN accuracy
 of D's features at every evaluation (contrad_amd/knn.py; an addition, off by default); ``--prdc_data FILE.npz --prdc_encoder FILE.pt`` logs
-precision / recall / density / coverage of the generator in a frozen encoder's features (contrad_amd/prdc.py; an addition, off by default).
+precision / recall / density / coverage of the generator in a frozen encoder's features (contrad_amd/prdc.py; an addition, off by default).  With it ``--prdc_kid`` adds the kernel distance (KID)
+of the same features to ``kid_<seed>.csv`` (contrad_amd/kid.py; ``--prdc_best kid`` keeps the checkpoints of its minimum).
 
 This module holds what the two scripts do differently from train_gan (their flags, option defaults, schedules, EMA,
 loaders, log directory and ``train_iteration``, whose D-steps are engine.d_step_stylegan2 / d_step_stylegan2_contrad);

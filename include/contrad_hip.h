@@ -768,6 +768,26 @@ int contrad_prdc_kth(const float* S, long long ldS, int M, int n, int k, long lo
 int contrad_prdc_count(const float* S, long long ldS, int M, int n, const float* thr_row, const float* thr_col,
                        int* row_hits, int* col_hits_c, int* col_hits_r, contrad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Kernel distance (KID, Binkowski et al. 2018) on a similarity matrix (csrc/kid.hip): the cubic-kernel block sum.
+ * An addition of this project (the reference selects by FID): the unbiased MMD^2 under k(a, b) = (gamma a.b + coef0)^3
+ * on frozen, L2-normalised features, gamma = coef0 = 1 (contrad_amd/kid.py).  Its values are comparable between
+ * evaluations under one encoder file, never with Inception-based KID.
+ * ---------------------------------------------------------------------------------------------- */
+/* Bytes of workspace contrad_kid_sums needs for an (M, n) block (one float64 partial per workgroup); -EINVAL on M < 1
+ * or n < 1. */
+long long contrad_kid_sums_workspace_bytes(int M, int n);
+/* out[0] = (accumulate ? out[0] : 0) + sum over i < M, j < n, j != self0 + i of (gamma * (double)S[i][j] + coef0)^3 on
+ * S[M][ldS] (only columns [0, n) are read: a padding column may hold anything).  self0 < 0 leaves nothing out
+ * (contrad_prdc_kth's convention: a row chunk passes its first row); the column is left out by index, whatever it holds.
+ * A NaN or inf inside the block propagates.  Every term is formed and added in float64; per-workgroup partials go to
+ * `workspace` and are added in one fixed order by a second launch, the old value last and by one thread: no atomics,
+ * two calls are bitwise equal.  16-byte loads when S is 16-byte aligned and ldS a multiple of 4, guarded scalar loads
+ * otherwise and wherever four columns cross n.  -EINVAL (before any GPU call) on a null S or out, M < 1, n < 1,
+ * ldS < n, a non-finite gamma or coef0, a workspace that is null, smaller than the query says or not 8-byte aligned. */
+int contrad_kid_sums(const float* S, long long ldS, int M, int n, long long self0, double gamma, double coef0,
+                     int accumulate, double* out, void* workspace, long long workspace_bytes, contrad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
