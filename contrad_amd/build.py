@@ -8,7 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB = os.path.join(CSRC, 'libcontrad_hip.so')
 # the same library with the development switches of the conv engine compiled in (common.h: CONTRAD_DEV_SWITCHES); only the
-# A/B tools and the two parity tests that force a tile plan load it (CONTRAD_HIP_LIB=<this path>)
+# A/B tools and the parity tests that force a tile plan load it (CONTRAD_HIP_LIB=<this path>)
 DEV_LIB = os.path.join(CSRC, 'libcontrad_hip_dev.so')
 DEV_SOURCES = ('igemm',)                 # every getenv-style switch lives in igemm.hip and the headers it includes (the Winograd ones: wino_host.h)
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

@@ -3,6 +3,10 @@
 * Every (path, mode, split-K) triple the planner returns over the BASELINE layers and a grid of small and odd shapes is
   reached by a case of the GPU parity matrix (tests/test_conv_paths_gpu.py: PATH_CASES), and each case's declared path is
   what the planner says -- a planner change that opens a path, or moves a case off its path, fails here.
+* Below the triple, on the direct families (paths 0 - 3): every sub-form (path, mode, bm, bn, split, tile-order table,
+  data-gradient stride) the planner returns over the same descriptors is declared by a case of PATH_CASES or of the form
+  table (tests/igemm_forms.py, run on the GPU by tests/test_igemm_forms_gpu.py), and each form case's declared form is what
+  the library reports in that case's environment -- a planner change that opens a sub-form fails here.
 * The Winograd workspace queries return -22 exactly where the matching *_ok query rejects the shape.
 * The supported-map statement of include/contrad_hip.h (F(2x2,3x3) / F(4x4,3x3)) is what wino_ok / wino44_ok do.
 """
@@ -125,6 +129,70 @@ def test_the_gpu_matrix_reaches_every_planned_path(L):
     missing = reachable(L) - declared
     assert not missing, 'planner triples no GPU parity case reaches: %s' % sorted(missing)
     assert {P for (P, _, _) in declared} == set(range(12))       # (and every family of contrad_conv2d_path's list)
+
+
+def _forms():
+    """tests/igemm_forms.py (it lives beside this module)."""
+    import sys
+    sys.path.insert(0, _HERE)
+    try:
+        import igemm_forms
+    finally:
+        sys.path.remove(_HERE)
+    return igemm_forms
+
+
+def test_the_form_table_reaches_every_planned_sub_form(L):
+    """Shipped library: nothing the planner returns on paths 0 - 3 is left without a float64 case."""
+    M, IF = _gpu_matrix(), _forms()
+    declared = {c.signature for c in IF.FORM_CASES}
+    for case in M.PATH_CASES:
+        sig = IF.signature(L, M.case_desc(case), case[1])
+        if sig is not None:
+            declared.add(sig)
+    reached = set()
+    for d in list(baseline_descs()) + list(grid_descs()):
+        for mode in (0, 1, 2):
+            reached.add(IF.signature(L, d, mode))
+    reached.discard(None)
+    missing = reached - declared
+    assert missing == set(), 'planner sub-forms no float64 case runs: %s' % sorted(missing)
+    assert {c.path for c in IF.FORM_CASES} == {0, 1, 2, 3}
+    assert len({c.id for c in IF.FORM_CASES}) == len(IF.FORM_CASES)
+
+
+@pytest.mark.parametrize('group', ['bal', 'border', 'img', 'pix', 'pixblk'])
+def test_every_form_case_declares_what_the_library_reports(L, group):
+    """In a child process with the group's environment, on the development library (host queries only: no GPU)."""
+    import json
+    import subprocess
+    import sys
+    from contrad_amd import build
+    IF = _forms()
+    assert sorted(IF.GROUPS) == ['bal', 'border', 'img', 'pix', 'pixblk']
+    assert os.path.exists(build.DEV_LIB)
+    env = dict(os.environ)
+    for name in IF.SWITCHES:
+        env.pop(name, None)
+    env.update(IF.GROUPS[group])
+    env['CONTRAD_HIP_LIB'] = build.DEV_LIB
+    r = subprocess.run([sys.executable, os.path.join(_HERE, 'igemm_forms.py'), group], env=env, capture_output=True, text=True,
+                       timeout=120, cwd=os.path.dirname(_HERE))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    cases = [c for c in IF.FORM_CASES if c.group == group]
+    reports = json.loads(r.stdout)
+    assert len(reports) == len(cases) > 0
+    for case, rep in zip(cases, reports):
+        assert not IF.mismatch(case, rep), (case.id, IF.mismatch(case, rep))
+        assert rep['path'] < 4
+        # a forced plan stays inside what the planner emits at some shape (igemm.hip: pick_tile, split_plan)
+        N, H, W, C, K, k, s, p = case.shape
+        if case.mode != 2:
+            ncol, depth = (K, C) if case.mode == 0 else (C, K)
+            assert case.bn <= 64 or ncol > 64, case.id
+            if case.split:
+                t_total = k * k * depth // 16
+                assert t_total >= 32 and -(-t_total // case.ov[2]) >= 8, case.id
 
 
 def test_the_plan_queries_agree_with_one_another(L):

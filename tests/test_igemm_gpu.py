@@ -36,7 +36,7 @@ CASES = [
     (3, 16, 16, 48, 80, 3, 1, 1),      # Kg = 432: ragged WGRAD row tile
     (2, 20, 12, 32, 48, 3, 1, 1),      # Wo = 12: lean FWD / DGRAD with a ragged M tile, general WGRAD
     (70, 8, 8, 64, 64, 3, 1, 1),       # M-tiles that start in the middle of an image (descriptor rebasing)
-    (6, 16, 16, 72, 136, 3, 1, 1),     # Cin % 16 != 0: the general float4 kernel at the big tile
+    (6, 16, 16, 72, 136, 3, 1, 1),     # Cin % 16 != 0 (and Cout % 16 != 0): the general float4 kernel, FWD and DGRAD on 64x64 tiles (contrad_conv2d_path 1); lean WGRAD on 128x128
     (2, 32, 32, 32, 32, 3, 1, 1),      # 32 -> 32 channels (StyleGAN2 at 512x512): the 128x32 tile in all three modes
     (3, 16, 16, 64, 16, 3, 1, 1),      # Cout = 16: half-empty 32-column tile; DGRAD contraction of one K-tile per tap
     (2, 16, 16, 16, 32, 3, 2, 1),      # Cin = 16 -> DGRAD writes a 16-column tile
@@ -58,13 +58,13 @@ CASES = [
     # 1 / 2 / 2 / 4 M-tiles): several groups of 8 M-tile indices, ragged last group, classes of different sizes
     (7, 17, 17, 64, 128, 3, 2, 0),     # 567 / 504 / 504 / 448 rows per class: 9 (8, 8, 7) tiles of 64 -> two groups, the second almost empty
     (40, 9, 9, 32, 48, 3, 2, 0),       # 1000 / 800 / 800 / 640 rows, Cout = 48: ragged K walk (3 K-tiles per tap)
-    (3, 33, 33, 128, 144, 3, 2, 0),    # two N-tiles (128 + ragged 16), 128-row tiles
+    (3, 33, 33, 128, 144, 3, 2, 0),    # DGRAD on 64x64 tiles (contrad_conv2d_tile): two N-tiles of its 128 columns, 14 M-tiles per class (two groups of 8 in the balanced order)
     (20, 11, 15, 16, 32, 3, 2, 1),     # pad 1: the class order is 1 / 2 / 2 / 4 taps, non-square odd map
     (2, 129, 129, 16, 16, 3, 2, 0),    # a long launch: 66 M-tiles per class at BM = 128 -> nine groups
     (16, 65, 65, 64, 64, 3, 2, 0),     # > 1024 blocks in the plain order: the plan itself takes the balanced order here
     # pixel-major tiles in the slot-balanced order of the whole launch (pixel_order_full): FWD / stride-1 DGRAD on a 4x4 map,
     # and the strided DGRAD of the 4x4 stride-2 layer (class-major launch, one table mirrored into the four parity classes)
-    (384, 4, 4, 64, 256, 3, 1, 1),     # 3 image blocks x 16 pixels, 2 / 4 N-tiles
+    (384, 4, 4, 64, 256, 3, 1, 1),     # (36 / 144 K-tiles: the plan splits K on image-major 64x64 tiles today, path 2; the tables of this block size run in tests/test_igemm_forms_gpu.py)
     (260, 8, 8, 32, 64, 4, 2, 1),      # strided: ragged last image block, one N-tile
     (256, 8, 8, 256, 64, 4, 2, 1),     # strided: several N-tiles per M-tile
 ]
