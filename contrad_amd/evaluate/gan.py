@@ -137,19 +137,32 @@ def eval_seed_of(seed):
     return int(np.random.RandomState(int(seed)).randint(10000))
 
 
+def freeze(module):
+    """``module`` in eval mode with gradients off on every parameter."""
+    module.eval()
+    for p in module.parameters():
+        p.requires_grad_(False)
+    return module
+
+
+def own_network(which, architecture, image_size, device, P=None):
+    """A network of a monitor's own: the ``'G'`` or ``'D'`` of ``get_architecture``, built inside ``preserved_rng`` (the
+    constructors draw the initial weights), on ``device``, frozen.  The monitor loads the shown weights into it at each
+    evaluation, so the training modules' modes, packed-weight caches and captured graphs are not touched."""
+    from ..models.gan import get_architecture
+    with preserved_rng(device):
+        net = get_architecture(architecture, image_size, P=P)['GD'.index(which)]
+    return freeze(net.to(device))
+
+
 class Monitor(object):
     """``--monitor`` on rank 0.  ``architecture`` / ``image_size`` / ``P``: what ``get_architecture`` built the training
     generator from; ``device``: where it lives."""
 
     def __init__(self, logdir, architecture, image_size, device, seed, no_gif=False, P=None, delay_ms=500):
-        from ..models.gan import get_architecture
         self.logdir, self.device, self.no_gif, self.delay_ms = logdir, device, bool(no_gif), delay_ms
         self.eval_seed = eval_seed_of(seed)
-        with preserved_rng(device):                                # the constructors draw the initial weights
-            G, _ = get_architecture(architecture, image_size, P=P)
-        self.G = G.to(device).eval()
-        for p in self.G.parameters():
-            p.requires_grad_(False)
+        self.G = own_network('G', architecture, image_size, device, P)
         self.fixed_gen = FixedSampleGeneration(self.G, volatile=self.no_gif, seed=self.eval_seed)
         self.image_grid = ImageGrid(volatile=self.no_gif)
         self._deflated = []                                        # apng_bytes: compressed frames so far

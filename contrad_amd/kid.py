@@ -7,7 +7,7 @@ same encoder file, NEVER with the Inception-based KID of papers.
     python test_kid.py enc/dis.pt sndcgan --real cifar10.npz --fake <run>/samples_7_n10000/samples.npz
     python test_kid.py enc/dis.pt sndcgan --real cifar10.npz --gen <run>/gen.pt --n_fake 10000 --seed 7
 
-Features are ``D.penultimate`` in eval mode with L2-normalised rows (``knn.extract_features``), and
+Features are ``D.penultimate`` in eval mode with L2-normalised rows (``features.extract_features``), and
 
     k(a, b) = (gamma a.b + coef0)^3,  gamma = 1, coef0 = 1
 
@@ -18,7 +18,7 @@ would flatten the cubic to 1 + 3 a.b / d).  With m = min(subset_size, n_r, n_f) 
     A_t = sum_{i != j} k(S_RR)    B_t = sum_{i != j} k(S_FF)    C_t = sum_{i, j} k(S_FR)       (self pairs left out by index)
     MMD2_t = (A_t + B_t) / (m (m - 1)) - 2 C_t / m^2        kid = mean_t MMD2_t        kid_std = std_t MMD2_t (ddof 0)
 
-  * S comes from ``ops.conv2d_fwd`` (``prdc.similarities``) in row chunks of at most 64 MB, the chunk rule of ``KNNClassifier``;
+  * banks and the row chunks of S: contrad_amd/features.py;
   * csrc/kid.hip: ``kid_sums`` per chunk, every term and every sum in float64, ``self0`` = the chunk's first row, the
     second and later chunks accumulate;
   * the host reads the [n_subsets][3] table of sums once and divides, averages and takes the deviation in float64.  KID
@@ -28,18 +28,12 @@ would flatten the cubic to 1 + 3 a.b / d).  With m = min(subset_size, n_r, n_f) 
 same frozen encoder, the same fakes, the same real set), appended to ``kid_<eval_seed>.csv``; ``--prdc_best kid`` keeps the
 ``*_best.pt`` files of the evaluation with the SMALLEST value.
 """
-import json
 import math
-import os
-from argparse import ArgumentParser
-from pathlib import Path
 
 import numpy as np
 import torch
 
-from . import ops, prdc
-from .knn import extract_features, new_bank, normalize_rows
-from .models.gan import get_architecture
+from . import features, ops
 
 DEGREE = 3
 CSV_HEAD = 'step,kid,kid_std'
@@ -104,31 +98,18 @@ def gather_subset(real, real_bankT, fake, idx_r, idx_f):
     F_t = fake.index_select(0, idx_f)
     if real is not None:
         R_t = real.index_select(0, idx_r)
-        bank_R = prdc.bank_of(R_t)
+        bank_R = features.bank_of(R_t)
     else:
-        bank_R = new_bank(m, d, fake.device)
+        bank_R = features.new_bank(m, d, fake.device)
         bank_R[:, :m].copy_(real_bankT.index_select(1, idx_r))
         R_t = bank_R[:, :m].t().contiguous()
-    return R_t, F_t, bank_R, prdc.bank_of(F_t)
-
-
-def similarity_chunks(q, bankT, S=None):
-    """Yields ``(row0, S_chunk)``: the similarities of the rows [row0, row0 + len(S_chunk)) of ``q`` [m, d] to the bank, in
-    row chunks under ``prdc.chunk_rows_of``.  ``S_chunk`` is a view of one buffer (``S``, or one made here) that the next
-    chunk overwrites."""
-    m, n_pad = q.shape[0], bankT.shape[1]
-    if S is None:
-        S = torch.empty(min(prdc.chunk_rows_of(n_pad), m), n_pad, device=q.device)
-    chunk = S.shape[0]
-    for i in range(0, m, chunk):
-        r = min(chunk, m - i)
-        yield i, prdc.similarities(q[i:i + r], bankT, S[:r])
+    return R_t, F_t, bank_R, features.bank_of(F_t)
 
 
 def block_sum(q, bankT, n, leave_self_out, gamma, coef0, out, S=None):
     """out[0] = sum of k over the similarities of ``q`` to the first ``n`` columns of the bank, pair (i, i) left out with
     ``leave_self_out``."""
-    for i, chunk in similarity_chunks(q, bankT, S):
+    for i, chunk in features.similarity_chunks(q, bankT, S):
         ops.kid_sums(chunk, n, self0=i if leave_self_out else -1, gamma=gamma, coef0=coef0, out=out, accumulate=i > 0)
     return out
 
@@ -138,7 +119,7 @@ def kid(real_feats, fake_feats, n_subsets=100, subset_size=1000, seed=0, normali
     """The kernel distance of fake feature rows [n_f, d] from real ones [n_r, d] (CUDA fp32) in the features they come
     from -- comparable only between evaluations under one encoder, never with Inception-based KID.  ``normalize``:
     L2-normalise the rows here (False: the caller did, as ``extract_features`` does).  ``real_bank``: ``(bankT, n_real)``, the
-    transposed bank ``prdc.bank_of`` of the normalised real rows (``real_feats`` is then not read and may be None).
+    transposed bank ``features.bank_of`` of the normalised real rows (``real_feats`` is then not read and may be None).
     Returns kid, kid_std, n_subsets, subset_size (the m actually used), n_real, n_fake, gamma, coef0, degree, seed, the
     table ``sums`` of (A_t, B_t, C_t) behind them and ``kernel``, the note on the kernel."""
     n_f = _feats(fake_feats, 'fake')
@@ -155,18 +136,18 @@ def kid(real_feats, fake_feats, n_subsets=100, subset_size=1000, seed=0, normali
     check_kernel(gamma, coef0)
     n_subsets, gamma, coef0 = int(n_subsets), float(gamma), float(coef0)
     _on_device(fake_feats, 'fake')
-    fake = normalize_rows(fake_feats) if normalize else fake_feats.contiguous()
+    fake = features.normalize_rows(fake_feats) if normalize else fake_feats.contiguous()
     real = real_bankT = None
     if real_bank is None:
         _on_device(real_feats, 'real')
-        real = normalize_rows(real_feats) if normalize else real_feats.contiguous()
+        real = features.normalize_rows(real_feats) if normalize else real_feats.contiguous()
     else:
         real_bankT = real_bank[0]
     dev = fake.device
     idx = torch.from_numpy(np.stack(subset_indices(n_r, n_f, m, n_subsets, seed))).to(dev)      # [2][n_subsets][m]
     table = torch.empty(n_subsets, 3, device=dev, dtype=torch.float64)
     m_pad = ops.round_up(m, 4)
-    S = torch.empty(min(prdc.chunk_rows_of(m_pad), m), m_pad, device=dev)
+    S = torch.empty(min(features.chunk_rows_of(m_pad), m), m_pad, device=dev)
     for t in range(n_subsets):
         R_t, F_t, bank_R, bank_F = gather_subset(real, real_bankT, fake, idx[0, t], idx[1, t])
         block_sum(R_t, bank_R, m, True, gamma, coef0, table[t, 0:1], S)
@@ -182,13 +163,13 @@ def kid(real_feats, fake_feats, n_subsets=100, subset_size=1000, seed=0, normali
 def kid_of(encoder, real_u8, fake_u8, n_subsets=100, subset_size=1000, seed=0, batch=500, gamma=1.0, coef0=1.0):
     """``kid`` of device-resident uint8 [n, H, W, 3] sets through ``encoder`` (on the GPU, in eval mode), ``batch`` images per
     trunk forward.  Comparable only between evaluations under one encoder file, never with Inception-based KID."""
-    prdc._check_u8(fake_u8, 'fake')
-    prdc._check_u8(real_u8, 'real')
+    features.check_u8(fake_u8, 'fake', 'kid')
+    features.check_u8(real_u8, 'real', 'kid')
     if tuple(real_u8.shape[1:]) != tuple(fake_u8.shape[1:]):
         raise ValueError('kid: the real images are %s, the fake ones %s' % (tuple(real_u8.shape[1:]), tuple(fake_u8.shape[1:])))
     check_sizes(real_u8.shape[0], fake_u8.shape[0], n_subsets, subset_size)
     check_kernel(gamma, coef0)
-    return kid(extract_features(encoder, real_u8, batch), extract_features(encoder, fake_u8, batch), n_subsets, subset_size,
+    return kid(features.extract_features(encoder, real_u8, batch), features.extract_features(encoder, fake_u8, batch), n_subsets, subset_size,
                seed, normalize=False, gamma=gamma, coef0=coef0)
 
 
@@ -197,73 +178,31 @@ def csv_line(step, out):
 
 
 def best_in_csv(path, upto_step):
-    """The smallest kid among the rows of a ``kid_<seed>.csv`` with step <= ``upto_step`` (None: no such row); the rule of
-    ``prdc.best_in_csv`` for a resumed run."""
-    with open(path) as f:
-        rows = [ln.split(',') for ln in f.read().split()[1:]]
-    kept = [float(r[1]) for r in rows if int(r[0]) <= upto_step]
-    return min(kept) if kept else None
+    """The smallest kid among the rows of a ``kid_<seed>.csv`` with step <= ``upto_step`` (None: no such row)."""
+    return features.best_in_csv(path, 1, upto_step, min)
 
 
 def parse_args(argv=None):
-    parser = ArgumentParser(description='Testing script: kernel distance (KID, cubic kernel, gamma = coef0 = 1) in the '
-                                        'L2-normalised features of a frozen discriminator (one process, one GPU).  Comparable '
-                                        'only between evaluations under one encoder file, never with Inception-based KID')
-    parser.add_argument('model_path', type=str, help='Path to the (discriminator) checkpoint used as the encoder')
-    parser.add_argument('architecture', type=str, help="The encoder's architecture")
-    parser.add_argument('--real', required=True, type=str, help='npz with x_train uint8 [n, H, W, 3]')
-    src = parser.add_mutually_exclusive_group(required=True)
-    src.add_argument('--fake', default=None, type=str, help='npz with images uint8 [n, H, W, 3] (samples.npz of test_gan_sample.py)')
-    src.add_argument('--gen', default=None, type=str, help='generator checkpoint to sample from at fixed latents of --seed')
-    parser.add_argument('--gen_arch', default=None, type=str, help="with --gen: the generator's architecture (default: the encoder's)")
-    parser.add_argument('--n_real', default=None, type=int, help='use the first N images of x_train (default: all)')
-    parser.add_argument('--n_fake', default=None, type=int,
-                        help='use the first N of --fake (default: all) / sample N from --gen (default: min(n_real, 10000))')
-    parser.add_argument('--n_subsets', default=100, type=int, help='subsets the estimate is averaged over (default: 100)')
-    parser.add_argument('--subset_size', default=1000, type=int,
-                        help='rows of each set per subset (default: 1000; at most the smaller set)')
-    parser.add_argument('--batch_size', default=500, type=int, help='images per forward (default: 500)')
-    parser.add_argument('--seed', default=None, type=int,
-                        help='file-name tag, seed of the subsets and of the latents of --gen (default: drawn)')
-    return parser.parse_args(argv)
+    return features.real_fake_parser(
+        'Testing script: kernel distance (KID, cubic kernel, gamma = coef0 = 1) in the L2-normalised features of a frozen '
+        'discriminator (one process, one GPU).  Comparable only between evaluations under one encoder file, never with '
+        'Inception-based KID',
+        'file-name tag, seed of the subsets and of the latents of --gen (default: drawn)',
+        after_sizes=(('--n_subsets', dict(default=100, type=int, help='subsets the estimate is averaged over (default: 100)')),
+                     ('--subset_size', dict(default=1000, type=int,
+                                            help='rows of each set per subset (default: 1000; at most the smaller set)')))
+    ).parse_args(argv)
 
 
 def main(argv=None):
     P = parse_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError('the kernel distance runs on the MI355X HIP path only (no CPU fallback)')
-    dev = torch.device('cuda', 0)
-    torch.cuda.set_device(dev)
-    seed = int(np.random.randint(10000)) if P.seed is None else P.seed
-    if P.batch_size < 1:
-        raise ValueError('--batch_size must be at least 1, got %r' % (P.batch_size,))
-    real = prdc.load_images(P.real, 'x_train', P.n_real)
-    image_size = tuple(real.shape[1:])                                     # the image size comes from the data
-    if P.fake:
-        fake = prdc.load_images(P.fake, 'images', P.n_fake)
-        if tuple(fake.shape[1:]) != image_size:
-            raise ValueError('%s holds %s images, %s holds %s' % (P.real, image_size, P.fake, tuple(fake.shape[1:])))
-        n_fake = len(fake)
-    else:
-        n_fake = min(len(real), 10000) if P.n_fake is None else P.n_fake
-        if n_fake < 1:
-            raise ValueError('--n_fake must be at least 1, got %r' % (n_fake,))
-    check_sizes(len(real), n_fake, P.n_subsets, P.subset_size)
-    E = prdc.load_frozen(get_architecture(P.architecture, image_size)[1], P.model_path, dev)
-    if P.fake:
-        fake = torch.from_numpy(fake).to(dev)
-    else:
-        G = prdc.load_frozen(get_architecture(P.gen_arch or P.architecture, image_size)[0], P.gen, dev)
-        fake = prdc.sample_u8(G, n_fake, P.batch_size, seed)
-    with torch.no_grad():
-        out = kid_of(E, torch.from_numpy(real).to(dev), fake, P.n_subsets, P.subset_size, seed, P.batch_size)
-    print('KID (cubic kernel, gamma 1, coef0 1, features of this encoder: not an Inception KID): [kid %.6f +- %.6f] over %d '
-          'subsets of %d on %d fake / %d real images' % (out['kid'], out['kid_std'], out['n_subsets'], out['subset_size'],
-                                                        out['n_fake'], out['n_real']), flush=True)
-    path = os.path.join(Path(P.fake or P.gen).parent, 'kid_%d.json' % seed)
-    with open(path, 'w') as f:
-        json.dump(out, f)
-    return path
+    return features.real_fake_main(
+        P, 'the kernel distance runs', lambda n_real, n_fake: check_sizes(n_real, n_fake, P.n_subsets, P.subset_size),
+        lambda E, real, fake, seed: kid_of(E, real, fake, P.n_subsets, P.subset_size, seed, P.batch_size),
+        lambda out: 'KID (cubic kernel, gamma 1, coef0 1, features of this encoder: not an Inception KID): [kid %.6f +- %.6f] '
+                    'over %d subsets of %d on %d fake / %d real images' % (
+                        out['kid'], out['kid_std'], out['n_subsets'], out['subset_size'], out['n_fake'], out['n_real']),
+        'kid_%d.json')
 
 
 if __name__ == '__main__':

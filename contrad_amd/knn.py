@@ -6,12 +6,8 @@ eval-mode trunk forward per image, one similarity GEMM, one select-and-vote laun
     python test_knn.py <run>/dis.pt sndcgan --n_classes 10 --data cifar10.npz
     python test_knn.py <run>/dis.pt sndcgan --synthetic --k 200 --temp 0.1
 
-  * features: ``D.penultimate`` under ``no_grad`` in eval mode (no power iteration, no augmentation), rows L2-normalised
-    by ``contrad_l2norm_fwd`` (x / max(||x||, 1e-12), F.normalize's rule);
-  * the bank is kept transposed, [d][n_pad] with n_pad = round_up(n, 4) and zero padding columns: the packed weight
-    layout of the conv engine, so ``S = Q bank^T`` is ``ops.conv2d_fwd`` on a (m, 1, 1, d) input;
-  * queries go through in row chunks of about 64 MB of ``S``: the GEMM writes a chunk, csrc/knn.hip reads it back five
-    times (four radix digits and the compaction) while it is still cached;
+  * features, the transposed bank and the row chunks of ``S``: contrad_amd/features.py;
+  * per chunk csrc/knn.hip reads ``S`` back five times (four radix digits and the compaction) while it is still cached;
   * ``knn_accuracy`` reads the device once, at the end.
 
 ``--knn_data`` of the training scripts runs ``knn_accuracy`` at every ``--evaluate_every`` through ``KNNMonitor``, which
@@ -25,13 +21,10 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import ops
-from .evaluate.gan import eval_seed_of, preserved_rng
-from .lineval import _to_float_nchw, load_npz, synthetic_set
+from . import features, ops
+from .evaluate.gan import eval_seed_of, own_network, preserved_rng
+from .lineval import load_npz, synthetic_set
 from .models.gan import get_architecture
-
-S_CHUNK_FLOATS = 1 << 24          # one chunk of S: 64 MB
-MAX_CHUNK_ROWS = 512
 
 
 def check_labels(y, n_classes, what='labels'):
@@ -41,52 +34,11 @@ def check_labels(y, n_classes, what='labels'):
         raise ValueError('%s in [%d, %d] with n_classes %d' % (what, int(y.min()), int(y.max()), n_classes))
 
 
-def normalize_rows(feats):
-    """x / max(||x||_2, 1e-12) per row of a CUDA fp32 (n, d) matrix (contrad_l2norm_fwd)."""
-    if feats.dim() != 2:
-        raise RuntimeError('knn: features must be an (n, d) matrix, got %s' % (tuple(feats.shape),))
-    if feats.stride(-1) != 1:
-        feats = feats.contiguous()
-    return ops.l2norm_fwd(feats)[0]
-
-
-def new_bank(n, d, device):
-    """The transposed bank [d][round_up(n, 4)], zero-filled (the padding columns stay zero)."""
-    return torch.zeros(d, ops.round_up(n, 4), device=device, dtype=torch.float32)
-
-
-def extract_features(D, x_u8, batch, bankT=None):
-    """Normalised penultimate features of the device-resident uint8 set ``x_u8`` [n, H, W, 3], ``batch`` images per
-    forward.  Returns them as [n, d]; with ``bankT`` (``new_bank(n, d, device)``) writes column i of the bank per image
-    instead and returns ``bankT``.  ``D`` must be in eval mode (the caller's business: this function touches no mode)."""
-    if D.training:
-        raise RuntimeError('knn.extract_features: D must be in eval mode (train mode runs a power iteration per call)')
-    if not x_u8.is_cuda or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3] != 3:
-        raise RuntimeError('knn.extract_features: images must be a CUDA uint8 [n, H, W, 3] tensor')
-    n, h, w, c = x_u8.shape
-    dev = x_u8.device
-    if batch < 1:
-        raise ValueError('knn.extract_features: batch must be at least 1, got %r' % (batch,))
-    rows = None
-    buf = torch.empty(min(batch, n), c, h, w, device=dev)
-    with torch.no_grad():
-        for i in range(0, n, batch):
-            m = min(batch, n - i)
-            x = _to_float_nchw(x_u8, torch.arange(i, i + m, device=dev), buf[:m])
-            z = normalize_rows(D.penultimate(x).reshape(m, -1))
-            if bankT is not None:
-                bankT[:, i:i + m].copy_(z.t())
-                continue
-            if rows is None:
-                rows = torch.empty(n, z.shape[1], device=dev)
-            rows[i:i + m].copy_(z)
-    return bankT if bankT is not None else rows
-
-
 class KNNClassifier(object):
     """Weighted kNN vote against a bank of ``n`` labelled feature rows.  ``bank_feats``: CUDA fp32 [n, d], or with
-    ``transposed=True`` the [d][round_up(n, 4)] bank itself (``new_bank`` + ``extract_features``; kept, not copied).
-    ``normalize``: L2-normalise bank and query rows here (False: the caller did, as ``extract_features`` does).
+    ``transposed=True`` the [d][round_up(n, 4)] bank itself (``features.new_bank`` filled by ``features.extract_features``;
+    kept, not copied).  ``normalize``: L2-normalise bank and query rows here (False: the caller did, as
+    ``extract_features`` does).
     ``k`` is clamped to the bank size."""
 
     def __init__(self, bank_feats, bank_labels, n_classes, k=200, temp=0.1, normalize=True, transposed=False):
@@ -117,21 +69,14 @@ class KNNClassifier(object):
         else:
             if bank_feats.shape[0] != self.n:
                 raise RuntimeError('knn: %d labels for %d bank rows' % (self.n, bank_feats.shape[0]))
-            self.bankT = new_bank(self.n, bank_feats.shape[1], dev)
-            self.bankT[:, :self.n].copy_((normalize_rows(bank_feats) if normalize else bank_feats).t())
+            self.bankT = features.bank_of(features.normalize_rows(bank_feats) if normalize else bank_feats)
         self.d, self.n_pad = self.bankT.shape
         self.n_classes, self.normalize = int(n_classes), bool(normalize)
         self.k = min(int(k), self.n)
         if self.k > ops.KNN_MAX_K:
             raise ValueError('knn: k = %d above the kernel limit %d' % (self.k, ops.KNN_MAX_K))
         self.inv_temp = 1.0 / float(temp)
-        self.chunk_rows = max(1, min(MAX_CHUNK_ROWS, S_CHUNK_FLOATS // self.n_pad))
-
-    def similarities(self, q, out):
-        """out[m][n_pad] = q[m][d] bank^T on the conv engine (a linear layer whose packed weight is the bank)."""
-        m = q.shape[0]
-        ops.conv2d_fwd(q.view(m, 1, 1, self.d), self.bankT, None, self.n_pad, 1, 1, 1, 0, out=out.view(m, 1, 1, self.n_pad))
-        return out
+        self.chunk_rows = features.chunk_rows_of(self.n_pad)
 
     def predict(self, feats, neighbours=False):
         """(pred int32 [M], scores [M, n_classes]) of the query rows ``feats`` [M, d]; with ``neighbours`` also
@@ -140,15 +85,13 @@ class KNNClassifier(object):
                 or feats.shape[1] != self.d:
             raise RuntimeError('knn: queries must be a CUDA float32 [M, %d] matrix' % self.d)
         M, dev = feats.shape[0], feats.device
-        q = normalize_rows(feats) if self.normalize else feats.contiguous()
+        q = features.normalize_rows(feats) if self.normalize else feats.contiguous()
         pred = torch.empty(M, device=dev, dtype=torch.int32)
         scores = torch.empty(M, self.n_classes, device=dev)
         idx = torch.empty(M, self.k, device=dev, dtype=torch.int32) if neighbours else None
         val = torch.empty(M, self.k, device=dev) if neighbours else None
-        S = torch.empty(min(self.chunk_rows, max(M, 1)), self.n_pad, device=dev)
-        for i in range(0, M, self.chunk_rows):
-            m = min(self.chunk_rows, M - i)
-            Sc = self.similarities(q[i:i + m], S[:m])
+        for i, Sc in features.similarity_chunks(q, self.bankT, chunk_rows=self.chunk_rows):
+            m = Sc.shape[0]
             ci, cv, cs, cp = ops.knn_select(Sc, self.n, self.labels, self.n_classes, self.k, self.inv_temp)
             pred[i:i + m].copy_(cp)
             scores[i:i + m].copy_(cs)
@@ -180,9 +123,9 @@ def knn_accuracy(D, data, n_classes, k=200, temp=0.1, batch=500):
     n_train, n_test = data['x_train'].shape[0], data['x_test'].shape[0]
     if n_train < 1 or n_test < 1:
         raise ValueError('knn_accuracy: empty split (%d training, %d test images)' % (n_train, n_test))
-    bankT = extract_features(D, data['x_train'], batch, bankT=new_bank(n_train, D.d_penul, dev))
+    bankT = features.extract_features(D, data['x_train'], batch, bankT=features.new_bank(n_train, D.d_penul, dev))
     clf = KNNClassifier(bankT, data['y_train'], n_classes, k=k, temp=temp, normalize=False, transposed=True)
-    pred, _ = clf.predict(extract_features(D, data['x_test'], batch))
+    pred, _ = clf.predict(features.extract_features(D, data['x_test'], batch))
     hits = (pred.long() == data['y_test']).sum()
     return {'acc@1': 100.0 * int(hits.item()) / n_test, 'n_test': n_test}       # the one device-to-host read
 
@@ -206,11 +149,7 @@ class KNNMonitor(object):
         self.data = to_device(data, n_classes, device)                     # the uint8 sets go to the device once
         self.device = device
         self.path = os.path.join(logdir, 'knn_%d.csv' % eval_seed_of(seed))
-        with preserved_rng(device):                                        # the constructors draw the initial weights
-            _, D = get_architecture(architecture, image_size, P=P)
-        self.D = D.to(device).eval()
-        for p in self.D.parameters():
-            p.requires_grad_(False)
+        self.D = own_network('D', architecture, image_size, device, P)
         if not os.path.exists(self.path):                                  # (a resumed run appends to its file)
             with open(self.path, 'w') as f:
                 f.write('step,acc@1\n')
@@ -265,11 +204,7 @@ def main(argv=None):
         raise RuntimeError('no dataset reader is installed here: pass --data FILE.npz (x_train, y_train, x_test, '
                            'y_test) or --synthetic')
     image_size = tuple(data['x_train'].shape[1:])                          # the image size comes from the data
-    _, D = get_architecture(P.architecture, image_size)
-    D.load_state_dict(torch.load(P.model_path, map_location='cpu'))
-    D = D.to(dev).eval()
-    for p in D.parameters():
-        p.requires_grad_(False)
+    D = features.load_frozen(get_architecture(P.architecture, image_size)[1], P.model_path, dev)
     out = knn_accuracy(D, data, P.n_classes, P.k, P.temp, P.batch_size)
     out.update({'k': min(P.k, len(data['y_train'])), 'temp': P.temp, 'n_train': int(len(data['y_train']))})
     print('kNN (k %d, T %g): [Acc@1 %.3f] on %d test images, bank of %d' % (

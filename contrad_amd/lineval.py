@@ -31,6 +31,7 @@ from . import config, ops
 from .augment import SimCLRAugment
 from .captured import EagerFirst, capture
 from .evaluate.classifier import new_meters, summarize, test_classifier
+from .features import to_float_nchw
 from .hostio import THROTTLE, upload, upload_into
 from .models.gan import get_architecture
 from .models.gan.base import LinearWrapper
@@ -113,12 +114,6 @@ def save_checkpoint(D, epoch, path):
     torch.save({'epoch': epoch, 'state_dict': D.state_dict()}, path)
 
 
-def _to_float_nchw(x_u8, idx, out):
-    """out[i] = x_u8[idx[i]] as float NCHW in [0, 1] (ToTensor)."""
-    out.copy_(x_u8.index_select(0, idx).permute(0, 3, 1, 2))
-    return out.div_(255.0)
-
-
 class HeadStep(object):
     """One training iteration at a fixed batch size on static buffers: crop + flip, eval-mode trunk forward, launches
     1 - 3 of the head.  The eager form runs the body; with ``graph=True`` the body is captured at the second use of
@@ -146,7 +141,7 @@ class HeadStep(object):
             ops.linhead_wgrad_sgd(feats, self.dlogits, head.weight, head.bias, lr=self.lr)
 
     def __call__(self, x_u8, y_dev, idx):
-        _to_float_nchw(x_u8, idx, self.images)
+        to_float_nchw(x_u8, idx, self.images)
         self.labels.copy_(y_dev.index_select(0, idx))
         P, _cf, _ = self.aug.sample(self.n, self.images.shape[2], self.images.shape[3])     # (column 15: the colour-op order)
         upload_into(P, self.params)

@@ -1148,6 +1148,20 @@ def linhead_wgrad_sgd(feats, dlogits, weight=None, bias=None, lr=None, grad_weig
     return grad_weight, grad_bias
 
 
+# ---- similarity-matrix kernels: the checks csrc/knn.hip, prdc.hip and kid.hip share ----
+def _chk_S(S, n):
+    _chk(S, 'S')
+    if S.dim() != 2 or S.shape[0] < 1:
+        raise RuntimeError('contrad_hip: S must be a non-empty (M, ldS) matrix')
+    if not 1 <= int(n) <= S.shape[1]:
+        raise RuntimeError('contrad_hip: n = %d outside [1, %d] (the columns of S)' % (n, S.shape[1]))
+    return S.shape[0], _ld(S), int(n)
+
+
+def _as_int(t):
+    return ctypes.cast(_p(t), ctypes.POINTER(ctypes.c_int))                    # (the header's int* maps to a typed pointer)
+
+
 # ---- weighted kNN vote (csrc/knn.hip) ----
 KNN_MAX_K = 1024
 KNN_MAX_CLASSES = 1024
@@ -1158,13 +1172,8 @@ def knn_select(S, n, labels, n_classes, k, inv_temp):
     columns and their weighted class vote.  ``labels``: int64 CUDA vector of the n bank labels.  Returns
     (idx int32 (M, k), val (M, k), scores (M, n_classes), pred int32 (M,)): contrad_knn_select's contract
     (include/contrad_hip.h)."""
-    _chk(S, 'S')
-    if S.dim() != 2 or S.shape[0] < 1:
-        raise RuntimeError('contrad_hip: S must be a non-empty (M, ldS) matrix')
-    M, ldS = S.shape[0], _ld(S)
-    n, C, k = int(n), int(n_classes), int(k)
-    if not 1 <= n <= S.shape[1]:
-        raise RuntimeError('contrad_hip: n = %d outside [1, %d] (the columns of S)' % (n, S.shape[1]))
+    M, ldS, n = _chk_S(S, n)
+    C, k = int(n_classes), int(k)
     if not 1 <= k <= min(n, KNN_MAX_K):
         raise RuntimeError('contrad_hip: k = %d outside [1, min(n, %d)] with n = %d' % (k, KNN_MAX_K, n))
     if not 1 <= C <= KNN_MAX_CLASSES:
@@ -1181,22 +1190,12 @@ def knn_select(S, n, labels, n_classes, k, inv_temp):
     if nbytes < 0:
         raise RuntimeError('contrad_hip: bad kNN shape (%d)' % nbytes)
     ws = _workspace(nbytes, dev) if nbytes > 0 else None
-    as_int = lambda t: ctypes.cast(_p(t), ctypes.POINTER(ctypes.c_int))        # (the header's int* maps to a typed pointer)
-    lib().call('contrad_knn_select', _p(S), ctypes.c_longlong(ldS), M, n, _p(labels), C, k, float(inv_temp), as_int(idx),
-               _p(val), _p(scores), as_int(pred), _p(ws), ctypes.c_longlong(nbytes), _stream())
+    lib().call('contrad_knn_select', _p(S), ctypes.c_longlong(ldS), M, n, _p(labels), C, k, float(inv_temp), _as_int(idx),
+               _p(val), _p(scores), _as_int(pred), _p(ws), ctypes.c_longlong(nbytes), _stream())
     return idx, val, scores, pred
 
 
 # ---- precision / recall / density / coverage (csrc/prdc.hip) ----
-def _chk_S(S, n):
-    _chk(S, 'S')
-    if S.dim() != 2 or S.shape[0] < 1:
-        raise RuntimeError('contrad_hip: S must be a non-empty (M, ldS) matrix')
-    if not 1 <= int(n) <= S.shape[1]:
-        raise RuntimeError('contrad_hip: n = %d outside [1, %d] (the columns of S)' % (n, S.shape[1]))
-    return S.shape[0], _ld(S), int(n)
-
-
 def _chk_vec(t, name, numel, dtype):
     if t is None:
         return
@@ -1204,10 +1203,6 @@ def _chk_vec(t, name, numel, dtype):
             or not t.is_contiguous():
         raise RuntimeError('contrad_hip: %s must be a contiguous CUDA %s vector of %d elements'
                            % (name, str(dtype).replace('torch.', ''), numel))
-
-
-def _as_int(t):
-    return ctypes.cast(_p(t), ctypes.POINTER(ctypes.c_int))                    # (the header's int* maps to a typed pointer)
 
 
 def prdc_kth(S, n, k, self0=-1, out=None):

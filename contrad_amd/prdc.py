@@ -8,7 +8,7 @@ between checkpoints and runs evaluated with the same encoder file, not with Ince
     python test_prdc.py enc/dis.pt sndcgan --real cifar10.npz --gen <run>/gen.pt --n_fake 10000 --seed 7
 
 The definitions live in SIMILARITY space.  Features are ``D.penultimate`` in eval mode with L2-normalised rows
-(``knn.extract_features``); on the unit sphere ||a - b||^2 = 2 - 2 a.b, so "inside the k-NN ball" is "similarity >= a
+(``features.extract_features``); on the unit sphere ||a - b||^2 = 2 - 2 a.b, so "inside the k-NN ball" is "similarity >= a
 threshold" and every comparison is made on the fp32 similarities the conv engine writes: no squared distance is formed,
 nothing cancels.  (The papers use raw Euclidean distances of unnormalised features.)  With R the n_r real rows, F the n_f
 fake rows, S_XY = X Y^T:
@@ -18,8 +18,7 @@ fake rows, S_XY = X Y^T:
     precision = mean_j any_i hit_c     density = sum_j sum_i hit_c / (k n_f)     coverage = mean_i any_j hit_c
     recall = mean_i any_j hit_r
 
-  * the banks are kept transposed (``knn.new_bank``), S comes from ``ops.conv2d_fwd`` in row chunks of at most 64 MB, the
-    chunk rule of ``KNNClassifier``;
+  * banks and the row chunks of S: contrad_amd/features.py;
   * csrc/prdc.hip: ``prdc_kth`` per chunk of S_RR and S_FF (``self0`` = the chunk's first row), ``prdc_count`` per chunk of S_FR;
   * the four metrics are ratios of integers counted on the device; the host reads them once and divides in float64.
 
@@ -29,18 +28,15 @@ METRIC`` keeps ``gen_best.pt`` / ``dis_best.pt`` (/ ``gen_ema_best.pt``), the na
 checkpoints, for the best value of that metric.  ``--prdc_kid`` adds the kernel distance of contrad_amd/kid.py to every
 evaluation (``kid_<seed>.csv``; ``--prdc_best kid`` selects its minimum).
 """
-import json
 import os
-from argparse import SUPPRESS, ArgumentParser
-from pathlib import Path
+from argparse import SUPPRESS
 from types import SimpleNamespace
 
-import numpy as np
 import torch
 
-from . import ops
-from .evaluate.gan import eval_seed_of, fixed_latent, preserved_rng
-from .knn import MAX_CHUNK_ROWS, S_CHUNK_FLOATS, extract_features, new_bank, normalize_rows
+from . import features, ops
+from . import kid as kid_mod
+from .evaluate.gan import eval_seed_of, own_network, preserved_rng
 from .models.gan import get_architecture
 
 METRICS = ('precision', 'recall', 'density', 'coverage')
@@ -48,31 +44,17 @@ CSV_HEAD = 'step,' + ','.join(METRICS)
 BEST_CHOICES = METRICS + ('kid',)                                           # --prdc_best: kid (contrad_amd/kid.py) is minimised
 
 
+def _tracked(metric):
+    """Where ``PRDCMonitor`` finds a ``--prdc_best`` metric: (which of its csv files, the column, +1 maximised / -1 minimised)."""
+    return (1, 1, -1) if metric == 'kid' else (0, 1 + METRICS.index(metric), 1)
+
+
 def _rows(feats, what, normalize):
     if not torch.is_tensor(feats) or not feats.is_cuda or feats.dtype != torch.float32 or feats.dim() != 2:
         raise RuntimeError('prdc: the %s features must be a CUDA float32 (n, d) matrix' % what)
     if feats.shape[0] < 1:
         raise ValueError('prdc: empty %s set' % what)
-    return normalize_rows(feats) if normalize else feats.contiguous()
-
-
-def bank_of(rows):
-    """The transposed bank [d][round_up(n, 4)] of normalised rows [n, d]."""
-    n, d = rows.shape
-    bankT = new_bank(n, d, rows.device)
-    bankT[:, :n].copy_(rows.t())
-    return bankT
-
-
-def chunk_rows_of(n_pad):
-    return max(1, min(MAX_CHUNK_ROWS, S_CHUNK_FLOATS // n_pad))
-
-
-def similarities(q, bankT, out):
-    """out[m][n_pad] = q[m][d] bank^T on the conv engine (``KNNClassifier.similarities``)."""
-    m, (d, n_pad) = q.shape[0], bankT.shape
-    ops.conv2d_fwd(q.view(m, 1, 1, d), bankT, None, n_pad, 1, 1, 1, 0, out=out.view(m, 1, 1, n_pad))
-    return out
+    return features.normalize_rows(feats) if normalize else feats.contiguous()
 
 
 def check_k(k, n_real, n_fake):
@@ -86,13 +68,9 @@ def check_k(k, n_real, n_fake):
 def kth_similarity(rows, bankT, k):
     """t[i]: the k-th largest similarity of row i of ``rows`` [n, d] to the OTHER columns of its own bank."""
     n = rows.shape[0]
-    n_pad = bankT.shape[1]
-    chunk = chunk_rows_of(n_pad)
     thr = torch.empty(n, device=rows.device)
-    S = torch.empty(min(chunk, n), n_pad, device=rows.device)
-    for i in range(0, n, chunk):
-        m = min(chunk, n - i)
-        ops.prdc_kth(similarities(rows[i:i + m], bankT, S[:m]), n, k, self0=i, out=thr[i:i + m])
+    for i, S in features.similarity_chunks(rows, bankT):
+        ops.prdc_kth(S, n, k, self0=i, out=thr[i:i + S.shape[0]])
     return thr
 
 
@@ -100,7 +78,7 @@ def real_state_of(real_feats, k, normalize=True):
     """``(bankT, t_R)`` of a real set: what ``prdc`` needs of it, for a caller whose real set does not change."""
     rows = _rows(real_feats, 'real', normalize)
     check_k(k, rows.shape[0], rows.shape[0])
-    bankT = bank_of(rows)
+    bankT = features.bank_of(rows)
     return bankT, kth_similarity(rows, bankT, int(k))
 
 
@@ -114,7 +92,7 @@ def prdc(real_feats, fake_feats, k=5, real_state=None, normalize=True):
     if real_state is None:
         real = _rows(real_feats, 'real', normalize)
         check_k(k, real.shape[0], fake.shape[0])                           # (before the real set's GEMMs)
-        bankT = bank_of(real)
+        bankT = features.bank_of(real)
         real_state = (bankT, kth_similarity(real, bankT, k))
     bankT, t_R = real_state
     n_r, n_f, dev = t_R.numel(), fake.shape[0], fake.device
@@ -122,17 +100,13 @@ def prdc(real_feats, fake_feats, k=5, real_state=None, normalize=True):
     if bankT.shape[0] != fake.shape[1] or bankT.shape[1] != ops.round_up(n_r, 4):
         raise RuntimeError('prdc: a real bank of %s for %d thresholds and fake features of width %d'
                            % (tuple(bankT.shape), n_r, fake.shape[1]))
-    t_F = kth_similarity(fake, bank_of(fake), k)
-    n_pad = bankT.shape[1]
-    chunk = chunk_rows_of(n_pad)
+    t_F = kth_similarity(fake, features.bank_of(fake), k)
     row_hits = torch.empty(n_f, device=dev, dtype=torch.int32)
     col_c = torch.zeros(n_r, device=dev, dtype=torch.int32)
     col_r = torch.zeros(n_r, device=dev, dtype=torch.int32)
-    S = torch.empty(min(chunk, n_f), n_pad, device=dev)
-    for i in range(0, n_f, chunk):
-        m = min(chunk, n_f - i)
-        ops.prdc_count(similarities(fake[i:i + m], bankT, S[:m]), n_r, thr_row=t_F[i:i + m], thr_col=t_R,
-                       row_hits=row_hits[i:i + m], col_hits_c=col_c, col_hits_r=col_r)
+    for i, S in features.similarity_chunks(fake, bankT):
+        m = S.shape[0]
+        ops.prdc_count(S, n_r, thr_row=t_F[i:i + m], thr_col=t_R, row_hits=row_hits[i:i + m], col_hits_c=col_c, col_hits_r=col_r)
     counts = torch.stack([(row_hits > 0).sum(), row_hits.sum(dtype=torch.int64), (col_c > 0).sum(), (col_r > 0).sum()])
     n_prec, n_hits, n_cov, n_rec = (int(v) for v in counts.tolist())           # the one device-to-host read
     return {'precision': n_prec / n_f, 'recall': n_rec / n_r, 'density': n_hits / (k * n_f), 'coverage': n_cov / n_r,
@@ -140,87 +114,27 @@ def prdc(real_feats, fake_feats, k=5, real_state=None, normalize=True):
             'n_real': n_r, 'n_fake': n_f, 'k': k}
 
 
-def _check_u8(x, what):
-    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
-        raise RuntimeError('prdc: the %s images must be a CUDA uint8 [n, H, W, 3] tensor' % what)
-    if x.shape[0] < 1:
-        raise ValueError('prdc: empty %s set' % what)
-
-
 def real_state_of_images(encoder, real_u8, k, batch=500):
-    _check_u8(real_u8, 'real')
-    return real_state_of(extract_features(encoder, real_u8, batch), k, normalize=False)
+    features.check_u8(real_u8, 'real', 'prdc')
+    return real_state_of(features.extract_features(encoder, real_u8, batch), k, normalize=False)
 
 
 def prdc_of(encoder, real_u8, fake_u8, k=5, batch=500, real_state=None):
     """``prdc`` of device-resident uint8 [n, H, W, 3] sets through ``encoder`` (on the GPU, in eval mode), ``batch`` images
     per trunk forward.  ``real_state``: ``real_state_of_images`` of the real set (``real_u8`` is then not read)."""
-    _check_u8(fake_u8, 'fake')
+    features.check_u8(fake_u8, 'fake', 'prdc')
     if real_state is None:
-        _check_u8(real_u8, 'real')
+        features.check_u8(real_u8, 'real', 'prdc')
         if tuple(real_u8.shape[1:]) != tuple(fake_u8.shape[1:]):
             raise ValueError('prdc: the real images are %s, the fake ones %s' % (tuple(real_u8.shape[1:]), tuple(fake_u8.shape[1:])))
         check_k(k, real_u8.shape[0], fake_u8.shape[0])
         real_state = real_state_of_images(encoder, real_u8, k, batch)
-    return prdc(None, extract_features(encoder, fake_u8, batch), k, real_state=real_state, normalize=False)
-
-
-def sample_u8(G, n, batch=500, seed=0):
-    """``n`` images of ``G`` (in eval mode) at the fixed latents of ``seed`` as uint8 [n, H, W, 3] on G's device, quantised
-    by ``ops.images_u8`` -- the kernel test_gan_sample.py writes ``samples.npz`` with, so fakes and reals pass through the
-    same uint8 step.  The global random streams are left as they were (StyleGAN2's per-layer noise is drawn from a CUDA
-    stream seeded with ``seed`` and restored)."""
-    if G.training:
-        raise RuntimeError('prdc.sample_u8: G must be in eval mode')
-    if n < 1 or batch < 1:
-        raise ValueError('prdc.sample_u8: n and batch must be at least 1, got %r, %r' % (n, batch))
-    dev = next(G.parameters()).device
-    out = None
-    with torch.no_grad(), preserved_rng(dev):
-        torch.cuda.manual_seed(int(seed))
-        z = fixed_latent(G, n, seed)
-        for i in range(0, n, batch):
-            u8 = ops.images_u8(G(z[i:i + batch]).contiguous().float())
-            if out is None:
-                out = torch.empty((n,) + tuple(u8.shape[1:]), device=dev, dtype=torch.uint8)
-            out[i:i + u8.shape[0]].copy_(u8)
-    return out
-
-
-def load_images(path, key, n=None):
-    """uint8 [n, H, W, 3] images ``key`` of an npz, the first ``n`` of them."""
-    with np.load(path) as z:
-        if key not in z:
-            raise ValueError('%s holds no %s' % (path, key))
-        x = np.asarray(z[key])
-    if x.dtype != np.uint8 or x.ndim != 4 or x.shape[3] != 3:
-        raise ValueError('%s: %s must be uint8 [n, H, W, 3], got %s %s' % (path, key, x.dtype, x.shape))
-    if n is not None:
-        if n < 1:
-            raise ValueError('%s: asked for %d images of %s' % (path, n, key))
-        x = x[:n]
-    if len(x) < 1:
-        raise ValueError('%s: %s is empty' % (path, key))
-    return np.ascontiguousarray(x)
-
-
-def load_frozen(module, path, device):
-    module.load_state_dict(torch.load(path, map_location='cpu'))
-    module = module.to(device).eval()
-    for p in module.parameters():
-        p.requires_grad_(False)
-    return module
+    return prdc(None, features.extract_features(encoder, fake_u8, batch), k, real_state=real_state, normalize=False)
 
 
 def best_in_csv(path, metric, upto_step):
-    """The best value of ``metric`` among the rows of a ``prdc_<seed>.csv`` with step <= ``upto_step`` (None: no such row).
-    A resumed run passes the step of the checkpoint it starts from: a later row belongs to networks that were never saved
-    (the row is written before the checkpoint) or that this run is about to supersede."""
-    with open(path) as f:
-        rows = [ln.split(',') for ln in f.read().split()[1:]]
-    col = 1 + METRICS.index(metric)
-    kept = [float(r[col]) for r in rows if int(r[0]) <= upto_step]
-    return max(kept) if kept else None
+    """The largest ``metric`` among the rows of a ``prdc_<seed>.csv`` with step <= ``upto_step`` (None: no such row)."""
+    return features.best_in_csv(path, 1 + METRICS.index(metric), upto_step, max)
 
 
 def csv_line(step, out):
@@ -240,8 +154,7 @@ class PRDCMonitor(object):
 
     def __init__(self, logdir, architecture, image_size, device, seed, data_path, encoder_path, encoder_arch=None, k=5,
                  n_fake=10000, batch=500, best=None, resumed_step=0, P=None, kid=False):
-        from . import kid as kid_mod                                       # (kid.py is built on this module)
-        real = load_images(data_path, 'x_train')
+        real = features.load_images(data_path, 'x_train')
         if tuple(real.shape[1:]) != tuple(image_size):
             raise ValueError('%s: x_train holds %s images, the generator makes %s' % (data_path, tuple(real.shape[1:]), tuple(image_size)))
         check_k(k, len(real), n_fake)
@@ -256,60 +169,58 @@ class PRDCMonitor(object):
         self.path = os.path.join(logdir, 'prdc_%d.csv' % self.eval_seed)
         self.kid_path = os.path.join(logdir, 'kid_%d.csv' % self.eval_seed) if kid else None
         self.n_real = len(real)
+        self.G = own_network('G', architecture, image_size, device, P)
         with preserved_rng(device):                                        # the constructors draw the initial weights
-            G, _ = get_architecture(architecture, image_size, P=P)
-            _, E = get_architecture(encoder_arch or architecture, image_size)
-        self.G = G.to(device).eval()
-        for p in self.G.parameters():
-            p.requires_grad_(False)
-        self.E = load_frozen(E, encoder_path, device)
+            E = get_architecture(encoder_arch or architecture, image_size)[1]
+        self.E = features.load_frozen(E, encoder_path, device)
         with torch.no_grad(), preserved_rng(device):
             self.real_state = real_state_of_images(self.E, torch.from_numpy(real).to(device), self.k, self.batch)
+        self.files = [(self.path, CSV_HEAD, csv_line)] + ([(self.kid_path, kid_mod.CSV_HEAD, kid_mod.csv_line)] if kid else [])
         self.best = None
-        if not os.path.exists(self.path):                                  # (a resumed run appends to its file)
-            with open(self.path, 'w') as f:
-                f.write(CSV_HEAD + '\n')
-        elif best is not None and best != 'kid':
-            self.best = best_in_csv(self.path, best, resumed_step)
-        if kid and not os.path.exists(self.kid_path):
-            with open(self.kid_path, 'w') as f:
-                f.write(kid_mod.CSV_HEAD + '\n')
-        elif best == 'kid':
-            self.best = kid_mod.best_in_csv(self.kid_path, resumed_step)
+        for j, (path, head, _) in enumerate(self.files):
+            if not os.path.exists(path):                                   # (a resumed run appends to its file)
+                with open(path, 'w') as f:
+                    f.write(head + '\n')
+            elif best is not None and j == _tracked(best)[0]:
+                _, column, sign = _tracked(best)
+                self.best = features.best_in_csv(path, column, resumed_step, min if sign < 0 else max)
 
     def update(self, step, generator):
         """One evaluation of ``generator``'s weights (G, or g_ema in the StyleGAN2 loops) -> the metrics, with
         ``improved``: the tracked metric rose above (kid: fell below) the best so far (False without ``best``; a tie keeps
         the earlier).  With ``kid`` the kernel distance of the same fake features (contrad_amd/kid.py: the subsets of the
         eval seed, the same at every evaluation) comes as ``kid`` / ``kid_std`` and goes to ``kid_<eval_seed>.csv``."""
-        from . import kid as kid_mod
         with torch.no_grad(), preserved_rng(self.device):
             self.G.load_state_dict(generator.state_dict())
             self.G.eval()
-            fake = sample_u8(self.G, self.n_fake, self.batch, self.eval_seed)
-            _check_u8(fake, 'fake')
-            feats = extract_features(self.E, fake, self.batch)
+            fake = features.sample_u8(self.G, self.n_fake, self.batch, self.eval_seed)
+            features.check_u8(fake, 'fake', 'prdc')
+            feats = features.extract_features(self.E, fake, self.batch)
             out = prdc(None, feats, self.k, real_state=self.real_state, normalize=False)
             if self.kid_path is not None:                                  # the same fake features, the same real rows (bankT)
                 d = kid_mod.kid(None, feats, seed=self.eval_seed, normalize=False, real_bank=(self.real_state[0], self.n_real))
                 out['kid'], out['kid_std'] = d['kid'], d['kid_std']
-        line = csv_line(step, out)
-        with open(self.path, 'a') as f:
-            f.write(line + '\n')
-        if self.kid_path is not None:
-            kid_line = kid_mod.csv_line(step, out)
-            with open(self.kid_path, 'a') as f:
-                f.write(kid_line + '\n')
+        lines = []
+        for path, _, line_of in self.files:
+            lines.append(line_of(step, out))
+            with open(path, 'a') as f:
+                f.write(lines[-1] + '\n')
         out['improved'] = False
-        if self.metric == 'kid':
-            value = float(kid_line.split(',')[1])                          # as the csv keeps it; the smaller the better
-            if self.best is None or value < self.best:
-                self.best, out['improved'] = value, True
-        elif self.metric is not None:
-            value = float(line.split(',')[1 + METRICS.index(self.metric)])      # as the csv keeps it: a resumed run compares alike
-            if self.best is None or value > self.best:
+        if self.metric is not None:
+            j, column, sign = _tracked(self.metric)
+            value = float(lines[j].split(',')[column])                     # as the csv keeps it: a resumed run compares alike
+            if self.best is None or sign * value > sign * self.best:
                 self.best, out['improved'] = value, True
         return out
+
+    def log_lines(self, step, out):
+        """The lines of the training log for ``out`` of ``update``: ``[best ...]`` closes the line of the tracked metric."""
+        mark = lambda here: ' [best %s]' % self.metric if out['improved'] and here else ''
+        lines = ['[Steps %7d] [precision %.4f] [recall %.4f] [density %.4f] [coverage %.4f]%s' % (
+            step, out['precision'], out['recall'], out['density'], out['coverage'], mark(self.metric != 'kid'))]
+        if 'kid' in out:
+            lines.append('[Steps %7d] [kid %.6f +- %.6f]%s' % (step, out['kid'], out['kid_std'], mark(self.metric == 'kid')))
+        return lines
 
 
 HOOK_DEFAULTS = {'prdc_data': None, 'prdc_encoder': None, 'prdc_encoder_arch': None, 'prdc_k': 5, 'prdc_n': 10000, 'prdc_best': None,
@@ -362,59 +273,21 @@ def check_hook_arguments(P):
 
 
 def parse_args(argv=None):
-    parser = ArgumentParser(description='Testing script: precision / recall / density / coverage in the features of a '
-                                        'frozen discriminator (one process, one GPU)')
-    parser.add_argument('model_path', type=str, help='Path to the (discriminator) checkpoint used as the encoder')
-    parser.add_argument('architecture', type=str, help="The encoder's architecture")
-    parser.add_argument('--real', required=True, type=str, help='npz with x_train uint8 [n, H, W, 3]')
-    src = parser.add_mutually_exclusive_group(required=True)
-    src.add_argument('--fake', default=None, type=str, help='npz with images uint8 [n, H, W, 3] (samples.npz of test_gan_sample.py)')
-    src.add_argument('--gen', default=None, type=str, help='generator checkpoint to sample from at fixed latents of --seed')
-    parser.add_argument('--gen_arch', default=None, type=str, help="with --gen: the generator's architecture (default: the encoder's)")
-    parser.add_argument('--k', default=5, type=int, help='neighbours (default: 5)')
-    parser.add_argument('--n_real', default=None, type=int, help='use the first N images of x_train (default: all)')
-    parser.add_argument('--n_fake', default=None, type=int,
-                        help='use the first N of --fake (default: all) / sample N from --gen (default: min(n_real, 10000))')
-    parser.add_argument('--batch_size', default=500, type=int, help='images per forward (default: 500)')
-    parser.add_argument('--seed', default=None, type=int, help='file-name tag and seed of the latents of --gen (default: drawn)')
-    return parser.parse_args(argv)
+    return features.real_fake_parser(
+        'Testing script: precision / recall / density / coverage in the features of a frozen discriminator (one process, '
+        'one GPU)',
+        'file-name tag and seed of the latents of --gen (default: drawn)',
+        before_sizes=(('--k', dict(default=5, type=int, help='neighbours (default: 5)')),)).parse_args(argv)
 
 
 def main(argv=None):
     P = parse_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError('precision / recall / density / coverage run on the MI355X HIP path only (no CPU fallback)')
-    dev = torch.device('cuda', 0)
-    torch.cuda.set_device(dev)
-    seed = int(np.random.randint(10000)) if P.seed is None else P.seed
-    if P.batch_size < 1:
-        raise ValueError('--batch_size must be at least 1, got %r' % (P.batch_size,))
-    real = load_images(P.real, 'x_train', P.n_real)
-    image_size = tuple(real.shape[1:])                                     # the image size comes from the data
-    if P.fake:
-        fake = load_images(P.fake, 'images', P.n_fake)
-        if tuple(fake.shape[1:]) != image_size:
-            raise ValueError('%s holds %s images, %s holds %s' % (P.real, image_size, P.fake, tuple(fake.shape[1:])))
-        n_fake = len(fake)
-    else:
-        n_fake = min(len(real), 10000) if P.n_fake is None else P.n_fake
-        if n_fake < 1:
-            raise ValueError('--n_fake must be at least 1, got %r' % (n_fake,))
-    check_k(P.k, len(real), n_fake)
-    E = load_frozen(get_architecture(P.architecture, image_size)[1], P.model_path, dev)
-    if P.fake:
-        fake = torch.from_numpy(fake).to(dev)
-    else:
-        G = load_frozen(get_architecture(P.gen_arch or P.architecture, image_size)[0], P.gen, dev)
-        fake = sample_u8(G, n_fake, P.batch_size, seed)
-    with torch.no_grad():
-        out = prdc_of(E, torch.from_numpy(real).to(dev), fake, P.k, P.batch_size)
-    print('PRDC (k %d): [precision %.4f] [recall %.4f] [density %.4f] [coverage %.4f] on %d fake / %d real images' % (
-        out['k'], out['precision'], out['recall'], out['density'], out['coverage'], out['n_fake'], out['n_real']), flush=True)
-    path = os.path.join(Path(P.fake or P.gen).parent, 'prdc_%d.json' % seed)
-    with open(path, 'w') as f:
-        json.dump(out, f)
-    return path
+    return features.real_fake_main(
+        P, 'precision / recall / density / coverage run', lambda n_real, n_fake: check_k(P.k, n_real, n_fake),
+        lambda E, real, fake, seed: prdc_of(E, real, fake, P.k, P.batch_size),
+        lambda out: 'PRDC (k %d): [precision %.4f] [recall %.4f] [density %.4f] [coverage %.4f] on %d fake / %d real images' % (
+            out['k'], out['precision'], out['recall'], out['density'], out['coverage'], out['n_fake'], out['n_real']),
+        'prdc_%d.json')
 
 
 if __name__ == '__main__':

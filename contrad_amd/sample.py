@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .features import load_frozen
 from .hostio import write_png
 
 PNG_WORKERS = 8          # (fixed: a machine's CPU count says nothing about this process's share of it)
@@ -53,12 +54,7 @@ def image_size_of(logdir):
 
 def load_generator(model_path, architecture, dev):
     from .models.gan import get_architecture
-    G, _ = get_architecture(architecture, image_size_of(Path(model_path).parent))
-    G.load_state_dict(torch.load(model_path, map_location='cpu'))
-    G.to(dev).eval()
-    for p in G.parameters():
-        p.requires_grad_(False)
-    return G
+    return load_frozen(get_architecture(architecture, image_size_of(Path(model_path).parent))[0], model_path, dev)
 
 
 def main(argv=None):

@@ -286,12 +286,8 @@ def run_loop(run, iteration):
             tags = ('', f'_{step}') if step % P.save_every == 0 else ('',)
             if run.prdc_monitor is not None:
                 m = run.prdc_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)
-                log('[Steps %7d] [precision %.4f] [recall %.4f] [density %.4f] [coverage %.4f]%s' % (
-                    step, m['precision'], m['recall'], m['density'], m['coverage'],
-                    ' [best %s]' % run.prdc_monitor.metric if m['improved'] and run.prdc_monitor.metric != 'kid' else ''))
-                if 'kid' in m:
-                    log('[Steps %7d] [kid %.6f +- %.6f]%s' % (
-                        step, m['kid'], m['kid_std'], ' [best kid]' if m['improved'] and run.prdc_monitor.metric == 'kid' else ''))
+                for line in run.prdc_monitor.log_lines(step, m):
+                    log(line)
                 if m['improved']:                                   # the reference's best-checkpoint names: this step's networks
                     tags += ('_best',)
             for tag in tags:

@@ -210,11 +210,11 @@ def _sets(case, seed, shift=SHIFT):
 
 def _device_blocks(real_rows, fake_rows, idx_r, idx_f):
     """The three fp32 similarity blocks the device forms for one subset of normalised device rows, read back."""
-    from contrad_amd import kid
+    from contrad_amd import features, kid
     dev = fake_rows.device
     R_t, F_t, bank_R, bank_F = kid.gather_subset(real_rows, None, fake_rows, torch.from_numpy(idx_r).to(dev), torch.from_numpy(idx_f).to(dev))
     m = len(idx_r)
-    read = lambda q, bank: np.concatenate([S[:, :m].cpu().numpy() for _, S in kid.similarity_chunks(q, bank)])
+    read = lambda q, bank: np.concatenate([S[:, :m].cpu().numpy() for _, S in features.similarity_chunks(q, bank)])
     return read(R_t, bank_R), read(F_t, bank_F), read(F_t, bank_R)
 
 
@@ -238,20 +238,20 @@ def _check_sums_on_own_S(got, real_rows, fake_rows, tag):
 
 @pytest.mark.parametrize('case', OWN_S_CASES, ids=lambda c: 'd%d-%dx%d-m%d-t%d' % c)
 def test_kid_sums_on_the_devices_own_similarities(case):
-    from contrad_amd import kid, prdc
+    from contrad_amd import features, kid
     d, n_r, n_f, size, T = case
     _, _, Rd, Fd = _sets(case, 0)
     got = kid.kid(Rd, Fd, n_subsets=T, subset_size=size, seed=3)
     m = min(size, n_r, n_f)
     assert (got['n_subsets'], got['subset_size'], got['n_real'], got['n_fake'], got['gamma'], got['coef0'], got['degree'], got['seed']) == \
         (T, m, n_r, n_f, 1.0, 1.0, 3, 3)
-    Rn, Fn = kid.normalize_rows(Rd), kid.normalize_rows(Fd)
+    Rn, Fn = features.normalize_rows(Rd), features.normalize_rows(Fd)
     tag = 'kid own S d%d %dx%d m%d t%d' % case
     worst = _check_sums_on_own_S(got, Rn, Fn, tag)
     print('%s: kid %.6f +- %.6f; largest |device sum - fsum| / bound %.3g' % (tag, got['kid'], got['kid_std'], worst))
     assert kid.kid(Rd, Fd, n_subsets=T, subset_size=size, seed=3) == got                       # two calls: the same dict
     assert kid.kid(Rn, Fn, n_subsets=T, subset_size=size, seed=3, normalize=False) == got
-    banked = kid.kid(None, Fn, n_subsets=T, subset_size=size, seed=3, normalize=False, real_bank=(prdc.bank_of(Rn), n_r))
+    banked = kid.kid(None, Fn, n_subsets=T, subset_size=size, seed=3, normalize=False, real_bank=(features.bank_of(Rn), n_r))
     assert banked == got                                                # the hook's form of the real set: the same floats
     other = kid.kid(Rd, Fd, n_subsets=T, subset_size=size, seed=4)
     assert other['sums'] != got['sums']                                 # another seed: other subsets
@@ -296,15 +296,16 @@ def test_kid_on_features_against_float64(case, seed):
 
 
 def test_row_chunks_of_a_subset_stay_within_the_float64_bound(monkeypatch):
-    from contrad_amd import kid, prdc
+    from contrad_amd import features, kid
     case = FEATURE_CASES[0]
     d, n_r, n_f, size, T = case
     ref = _ref64(case, 1)
     _, _, Rd, Fd = _sets(case, 1)
-    monkeypatch.setattr(prdc, 'MAX_CHUNK_ROWS', 32)                     # 100 rows of a subset: 32 + 32 + 32 + 4
+    monkeypatch.setattr(features, 'MAX_CHUNK_ROWS', 32)                 # 100 rows of a subset: 32 + 32 + 32 + 4
+    assert features.chunk_rows_of(100) == 32                            # the patch reaches the rule (a subset's bank: 100 columns)
     got = kid.kid(Rd, Fd, n_subsets=T, subset_size=size, seed=1)
     assert abs(got['kid'] - ref['kid']) <= _feature_bound(d)
-    _check_sums_on_own_S(got, kid.normalize_rows(Rd), kid.normalize_rows(Fd), 'kid in chunks of 32 rows')
+    _check_sums_on_own_S(got, features.normalize_rows(Rd), features.normalize_rows(Fd), 'kid in chunks of 32 rows')
 
 
 def test_host_refusals_on_device_tensors():
@@ -325,7 +326,7 @@ def test_host_refusals_on_device_tensors():
 # ---- through a discriminator ----
 def test_kid_of_through_sndcgan_equals_the_yardstick_on_the_device_S():
     from contrad_amd import kid, lineval
-    from contrad_amd.knn import extract_features
+    from contrad_amd.features import extract_features
     import test_prdc_gpu as TP
     data = lineval.synthetic_set(3, 4, 256, 192)
     _, D = TP._encoder()
@@ -494,12 +495,12 @@ def test_resumed_monitor_reads_the_smallest_kid_up_to_its_checkpoint(tmp_path_fa
     and as a fresh run in the same directory; then one evaluation against each."""
     import shutil
     import test_prdc_gpu as TP
-    from contrad_amd import prdc
+    from contrad_amd import features, prdc
     from contrad_amd.models.gan import get_architecture
     d, hooked = TP._files(tmp_path_factory), _run(tmp_path_factory, True)
     rows = _kid_rows(hooked, TP.EVAL_SEED)
     dev = torch.device('cuda', 0)
-    G = prdc.load_frozen(get_architecture('sndcgan', (32, 32, 3))[0], os.path.join(hooked, 'gen_4.pt'), dev)
+    G = features.load_frozen(get_architecture('sndcgan', (32, 32, 3))[0], os.path.join(hooked, 'gen_4.pt'), dev)
 
     def monitor(resumed_step, sub):
         logdir = tmp_path / sub

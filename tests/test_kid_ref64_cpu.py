@@ -164,7 +164,7 @@ def test_python_layer_refusals():
 
 
 def test_best_in_csv_is_the_minimum_up_to_the_checkpoint(tmp_path):
-    from contrad_amd import kid
+    from contrad_amd import features, kid
     path = str(tmp_path / 'kid_7.csv')
     rows = [(2, dict(kid=0.5, kid_std=0.01)), (4, dict(kid=0.25, kid_std=0.02)), (6, dict(kid=-0.000125, kid_std=0.03)),
             (8, dict(kid=0.75, kid_std=0.04))]                         # step 8: written, its networks never saved
@@ -176,6 +176,9 @@ def test_best_in_csv_is_the_minimum_up_to_the_checkpoint(tmp_path):
     assert kid.best_in_csv(path, 8) == -0.000125 and kid.best_in_csv(path, 6) == -0.000125      # not clamped
     assert kid.best_in_csv(path, 5) == 0.25 and kid.best_in_csv(path, 4) == 0.25 and kid.best_in_csv(path, 2) == 0.5
     assert kid.best_in_csv(path, 1) is None and kid.best_in_csv(path, 0) is None
+    for upto in range(10):                                             # the one reader under both wrappers: column 1, min
+        assert features.best_in_csv(path, 1, upto, min) == kid.best_in_csv(path, upto)
+    assert features.best_in_csv(path, 1, 8, max) == 0.75 and features.best_in_csv(path, 2, 6, max) == 0.03
     with open(path, 'w') as f:
         f.write(kid.CSV_HEAD + '\n')
     assert kid.best_in_csv(path, 100) is None
@@ -206,3 +209,28 @@ def test_hook_flags_parse_and_are_refused_before_any_cuda_call(tmp_path):
         train_gan.main(common + ['--prdc_data', str(tmp_path / 'real.npz'), '--prdc_encoder', str(tmp_path / 'e.pt'), '--prdc_best', 'kid'])
     assert torch.cuda.is_initialized() == was_initialised and not os.path.exists(str(tmp_path / 'run'))
     assert prdc.METRICS == ('precision', 'recall', 'density', 'coverage') and prdc.CSV_HEAD == 'step,precision,recall,density,coverage'
+
+
+def test_the_evaluators_are_layered_on_features_not_on_each_other():
+    """kid.py stands on features.py alone (no import of prdc, no toolkit name reached through it); prdc.py imports kid at the
+    top of the file, not inside a function; the toolkit has one home (no copies or re-exports left in the old ones)."""
+    import ast
+    import inspect
+    from contrad_amd import features, kid, knn, prdc
+    toolkit = ('normalize_rows', 'new_bank', 'bank_of', 'S_CHUNK_FLOATS', 'MAX_CHUNK_ROWS', 'chunk_rows_of', 'similarities',
+               'similarity_chunks', 'check_u8', 'to_float_nchw', 'extract_features', 'load_frozen', 'load_images', 'sample_u8')
+    kid_src, prdc_src = inspect.getsource(kid), inspect.getsource(prdc)
+    assert 'from . import prdc' not in kid_src and 'from .prdc' not in kid_src and 'import prdc' not in kid_src
+    assert 'prdc.' not in kid_src.replace('contrad_amd/prdc.py', '').replace('``prdc.PRDCMonitor``', '')
+    imports = [n for n in ast.walk(ast.parse(kid_src)) if isinstance(n, (ast.Import, ast.ImportFrom))]
+    assert all('prdc' not in (getattr(n, 'module', None) or '') and all('prdc' not in a.name for a in n.names) for n in imports)
+    tree = ast.parse(prdc_src)
+    top = [n for n in tree.body if isinstance(n, (ast.Import, ast.ImportFrom))]
+    assert any(isinstance(n, ast.ImportFrom) and n.level == 1 and not n.module and any(a.name == 'kid' for a in n.names) for n in top)
+    nested = [n for f in ast.walk(tree) if isinstance(f, (ast.FunctionDef, ast.Lambda)) for n in ast.walk(f)
+              if isinstance(n, (ast.Import, ast.ImportFrom))]
+    assert not nested, [ast.dump(n) for n in nested]
+    for name in toolkit:
+        assert hasattr(features, name), name
+        for old_home in (knn, prdc, kid):
+            assert not hasattr(old_home, name), (old_home.__name__, name)

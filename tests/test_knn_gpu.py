@@ -219,7 +219,7 @@ def test_classifier_chunks_rows_and_clamps_k(margin):
 
 # ---- through a discriminator ----
 def _accuracy_both_ways(arch, margin, settle=0, k=200):
-    from contrad_amd import knn, lineval
+    from contrad_amd import features, knn, lineval
     from contrad_amd.models.gan import get_architecture
     data = lineval.synthetic_set(3, 4, 256, 64)
     torch.manual_seed(3)
@@ -239,7 +239,7 @@ def _accuracy_both_ways(arch, margin, settle=0, k=200):
     got = knn.knn_accuracy(D, data, 4, k=k, temp=TEMP, batch=100)
     assert got['n_test'] == 64
     dev = knn.to_device(data, 4, torch.device('cuda', 0))
-    f_train, f_test = knn.extract_features(D, dev['x_train'], 100), knn.extract_features(D, dev['x_test'], 100)
+    f_train, f_test = features.extract_features(D, dev['x_train'], 100), features.extract_features(D, dev['x_test'], 100)
     assert tuple(f_train.shape) == (256, D.d_penul)
     norms = f_train.double().norm(dim=1)
     margin('knn %s feature row norms' % arch, float((norms - 1).abs().max()), (D.d_penul / 2 + 4) * EPS)

@@ -290,11 +290,12 @@ def test_a_set_against_itself_and_the_cached_real_state():
 
 
 def test_chunked_rows_equal_one_chunk(monkeypatch):
-    from contrad_amd import prdc
+    from contrad_amd import features, prdc
     real, fake, _ = _feature_ref(FEATURE_CASES[0], 1)
     Rd, Fd = torch.from_numpy(real).float().cuda(), torch.from_numpy(fake).float().cuda()
     whole = prdc.prdc(Rd, Fd, 5)
-    monkeypatch.setattr(prdc, 'MAX_CHUNK_ROWS', 100)                 # 300 real rows: 3 chunks; 257 fake rows: 100 + 100 + 57
+    monkeypatch.setattr(features, 'MAX_CHUNK_ROWS', 100)             # 300 real rows: 3 chunks; 257 fake rows: 100 + 100 + 57
+    assert features.chunk_rows_of(300) == 100 and features.chunk_rows_of(260) == 100      # the patch reaches the rule
     assert prdc.prdc(Rd, Fd, 5) == whole
 
 
@@ -308,7 +309,7 @@ def _encoder(seed=3):
 
 def test_prdc_of_through_sndcgan_equals_the_yardstick_on_the_device_S():
     from contrad_amd import lineval, prdc
-    from contrad_amd.knn import extract_features
+    from contrad_amd.features import bank_of, extract_features, similarities
     data = lineval.synthetic_set(3, 4, 256, 192)
     _, D = _encoder()
     D = D.cuda().eval()
@@ -318,10 +319,10 @@ def test_prdc_of_through_sndcgan_equals_the_yardstick_on_the_device_S():
     got = prdc.prdc_of(D, real_u8, fake_u8, k=5, batch=100)
     fr, ff = extract_features(D, real_u8, 100), extract_features(D, fake_u8, 100)
     assert tuple(fr.shape) == (256, D.d_penul) and tuple(ff.shape) == (192, D.d_penul)
-    br, bf = prdc.bank_of(fr), prdc.bank_of(ff)
-    S_RR = prdc.similarities(fr, br, torch.empty(256, 256, device='cuda')).cpu().numpy()
-    S_FF = prdc.similarities(ff, bf, torch.empty(192, 192, device='cuda')).cpu().numpy()
-    S_FR = prdc.similarities(ff, br, torch.empty(192, 256, device='cuda')).cpu().numpy()
+    br, bf = bank_of(fr), bank_of(ff)
+    S_RR = similarities(fr, br, torch.empty(256, 256, device='cuda')).cpu().numpy()
+    S_FF = similarities(ff, bf, torch.empty(192, 192, device='cuda')).cpu().numpy()
+    S_FR = similarities(ff, br, torch.empty(192, 256, device='cuda')).cpu().numpy()
     ref = R.prdc_from_S(S_RR, S_FF, S_FR, 5)
     for name, v in ref.items():
         assert got[name] == v, (name, got[name], v)                  # exact: integers, and ratios of them in float64
@@ -341,12 +342,12 @@ _RUNS = {}
 
 def _sampled_reals(gen_paths, arch, n, path, seed=12345):
     """A real set that the fakes can hit: ``n`` images of each generator checkpoint in ``gen_paths`` at latents of their own."""
-    from contrad_amd import prdc
+    from contrad_amd import features
     from contrad_amd.models.gan import get_architecture
     sets = []
     for gen_path in gen_paths:
-        G = prdc.load_frozen(get_architecture(arch, (32, 32, 3))[0], gen_path, torch.device('cuda', 0))
-        sets.append(prdc.sample_u8(G, n, 500, seed).cpu().numpy())
+        G = features.load_frozen(get_architecture(arch, (32, 32, 3))[0], gen_path, torch.device('cuda', 0))
+        sets.append(features.sample_u8(G, n, 500, seed).cpu().numpy())
     np.savez(path, x_train=np.concatenate(sets))
 
 
@@ -513,13 +514,13 @@ def test_resumed_monitor_reads_the_best_value_up_to_its_checkpoint(tmp_path_fact
     """The monitor over the csv of the --graph run that tracks density (rows for steps 2 and 4), as a run resumed from step 4, from step 2
     and as a fresh run in the same directory; then one evaluation against each."""
     import shutil
-    from contrad_amd import prdc
+    from contrad_amd import features, prdc
     from contrad_amd.models.gan import get_architecture
     d, hooked = _files(tmp_path_factory), _run(tmp_path_factory, True, 'density')
     rows = _csv_rows(hooked)
     name = 'prdc_%d.csv' % EVAL_SEED
     dev = torch.device('cuda', 0)
-    G = prdc.load_frozen(get_architecture('sndcgan', (32, 32, 3))[0], os.path.join(hooked, 'gen_4.pt'), dev)
+    G = features.load_frozen(get_architecture('sndcgan', (32, 32, 3))[0], os.path.join(hooked, 'gen_4.pt'), dev)
 
     def monitor(resumed_step, sub):
         logdir = tmp_path / sub

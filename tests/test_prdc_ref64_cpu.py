@@ -144,7 +144,7 @@ def test_python_layer_argument_errors():
 
 
 def test_best_value_of_a_resumed_run_comes_from_rows_up_to_its_checkpoint(tmp_path):
-    from contrad_amd import prdc
+    from contrad_amd import features, prdc
     path = str(tmp_path / 'prdc_7.csv')
     rows = [(2, dict(precision=0.5, recall=0.25, density=0.75, coverage=0.125)),
             (4, dict(precision=0.25, recall=0.5, density=1.5, coverage=0.25)),
@@ -155,25 +155,29 @@ def test_best_value_of_a_resumed_run_comes_from_rows_up_to_its_checkpoint(tmp_pa
     assert prdc.best_in_csv(path, 'coverage', 5) == 0.25 and prdc.best_in_csv(path, 'precision', 4) == 0.5
     assert prdc.best_in_csv(path, 'density', 4) == 1.5 and prdc.best_in_csv(path, 'recall', 2) == 0.25
     assert prdc.best_in_csv(path, 'coverage', 1) is None and prdc.best_in_csv(path, 'coverage', 0) is None
+    for upto in range(8):                                              # the one reader under both wrappers: column 1 + index, max
+        for j, metric in enumerate(prdc.METRICS):
+            assert features.best_in_csv(path, 1 + j, upto, max) == prdc.best_in_csv(path, metric, upto)
+    assert features.best_in_csv(path, 3, 6, min) == 0.5                # (density: 0.75, 1.5, 0.5)
     with open(path, 'w') as f:
         f.write(prdc.CSV_HEAD + '\n')
     assert prdc.best_in_csv(path, 'coverage', 100) is None
 
 
 def test_command_line_refuses_bad_sets_on_the_host(tmp_path):
-    from contrad_amd import prdc
+    from contrad_amd import features
     r = np.random.RandomState(0)
     np.savez(str(tmp_path / 'real.npz'), x_train=r.randint(0, 255, (8, 32, 32, 3)).astype(np.uint8))
     np.savez(str(tmp_path / 'small.npz'), images=r.randint(0, 255, (8, 16, 16, 3)).astype(np.uint8))
     np.savez(str(tmp_path / 'empty.npz'), images=np.zeros((0, 32, 32, 3), np.uint8))
     np.savez(str(tmp_path / 'floats.npz'), images=np.zeros((8, 32, 32, 3), np.float32))
-    assert prdc.load_images(str(tmp_path / 'real.npz'), 'x_train', 5).shape == (5, 32, 32, 3)
+    assert features.load_images(str(tmp_path / 'real.npz'), 'x_train', 5).shape == (5, 32, 32, 3)
     with pytest.raises(ValueError, match='empty'):
-        prdc.load_images(str(tmp_path / 'empty.npz'), 'images')
+        features.load_images(str(tmp_path / 'empty.npz'), 'images')
     with pytest.raises(ValueError, match='uint8'):
-        prdc.load_images(str(tmp_path / 'floats.npz'), 'images')
+        features.load_images(str(tmp_path / 'floats.npz'), 'images')
     with pytest.raises(ValueError, match='holds no'):
-        prdc.load_images(str(tmp_path / 'real.npz'), 'images')
+        features.load_images(str(tmp_path / 'real.npz'), 'images')
 
 
 def _vp(a):

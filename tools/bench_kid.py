@@ -16,7 +16,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bench_knn import fmt, windows  # noqa: E402
-from contrad_amd import kid, ops, prdc  # noqa: E402
+from contrad_amd import features, kid, ops  # noqa: E402
 
 dev = torch.device('cuda', 0)
 HBM = 6.3e12
@@ -45,19 +45,19 @@ def whole(emit):
     emit('kid n_r = n_f = %d, d = %d, %d subsets of %d: %.6f +- %.6f' % (n, d, T, size, out['kid'], out['kid_std']))
     t = windows(lambda: kid.kid(real, fake, T, size), iters=1, reps=5, warm=1)
     emit(fmt('kid: all (normalise, %d x (gathers, three %d x %d x %d GEMMs, sums), one read)' % (T, size, size, d), t))
-    rows_r, rows_f = kid.normalize_rows(real), kid.normalize_rows(fake)
-    bank = prdc.bank_of(rows_r)
+    rows_r, rows_f = features.normalize_rows(real), features.normalize_rows(fake)
+    bank = features.bank_of(rows_r)
     t = windows(lambda: kid.kid(None, rows_f, T, size, normalize=False, real_bank=(bank, n)), iters=1, reps=5, warm=1)
     emit(fmt('  on normalised rows and the real bank: what --prdc_kid adds to a hooked evaluation', t))
     idx = torch.randperm(n, generator=g)[:size].to(dev)
     R_t, F_t, bank_R, bank_F = kid.gather_subset(rows_r, None, rows_f, idx, idx)
     m_pad = bank_R.shape[1]
-    S = torch.empty(min(prdc.chunk_rows_of(m_pad), size), m_pad, device=dev)
+    S = torch.empty(min(features.chunk_rows_of(m_pad), size), m_pad, device=dev)
     table = torch.zeros(3, dtype=torch.float64, device=dev)
 
     def gemms():
         for q, b in ((R_t, bank_R), (F_t, bank_F), (F_t, bank_R)):
-            for _ in kid.similarity_chunks(q, b, S):
+            for _ in features.similarity_chunks(q, b, S):
                 pass
 
     def sums():

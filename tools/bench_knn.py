@@ -15,7 +15,8 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from contrad_amd import knn, lineval, ops
+from contrad_amd import features, knn, lineval, ops
+from contrad_amd.evaluate.gan import freeze
 from contrad_amd.models.gan import get_architecture
 
 dev = torch.device('cuda', 0)
@@ -64,17 +65,15 @@ def accuracy(emit):
     data = lineval.synthetic_set(0, 10, 50000, 10000)
     torch.manual_seed(0)
     _, D = get_architecture('sndcgan', (32, 32, 3))
-    D = D.to(dev).eval()
-    for p in D.parameters():
-        p.requires_grad_(False)
+    D = freeze(D.to(dev))
     data = knn.to_device(data, 10, dev)
     t = windows(lambda: knn.knn_accuracy(D, data, 10, 200, 0.1, 500), iters=1, reps=5, warm=1)
     emit(fmt('knn_accuracy 50 000 / 10 000, sndcgan (d = 8192), k 200, batch 500: all', t))
-    bankT = knn.new_bank(50000, D.d_penul, dev)
-    t = windows(lambda: (knn.extract_features(D, data['x_train'], 500, bankT=bankT), knn.extract_features(D, data['x_test'], 500)),
-                iters=1, reps=5, warm=1)
+    bankT = features.new_bank(50000, D.d_penul, dev)
+    t = windows(lambda: (features.extract_features(D, data['x_train'], 500, bankT=bankT),
+                         features.extract_features(D, data['x_test'], 500)), iters=1, reps=5, warm=1)
     emit(fmt('  features: 60 000 eval-mode trunk forwards, normalise, bank transpose', t))
-    q = knn.extract_features(D, data['x_test'], 500)
+    q = features.extract_features(D, data['x_test'], 500)
     clf = knn.KNNClassifier(bankT, data['y_train'], 10, k=200, temp=0.1, normalize=False, transposed=True)
     t = windows(lambda: clf.predict(q), iters=1, reps=5, warm=1)
     emit(fmt('  predict: %d chunks of %d rows, GEMM then select per chunk' % (-(-10000 // clf.chunk_rows), clf.chunk_rows), t))
@@ -82,8 +81,8 @@ def accuracy(emit):
     chunks = [(i, min(clf.chunk_rows, 10000 - i)) for i in range(0, 10000, clf.chunk_rows)]
 
     def gemms():
-        for i, m in chunks:
-            clf.similarities(q[i:i + m], S[:m])
+        for _ in features.similarity_chunks(q, clf.bankT, S):
+            pass
 
     def selects():
         for i, m in chunks:

@@ -16,7 +16,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from bench_knn import fmt, windows  # noqa: E402
-from contrad_amd import ops, prdc  # noqa: E402
+from contrad_amd import features, ops, prdc  # noqa: E402
 
 dev = torch.device('cuda', 0)
 
@@ -54,9 +54,9 @@ def whole(emit):
     state = prdc.real_state_of(real, k)
     t = windows(lambda: prdc.prdc(None, fake, k, real_state=state), iters=1, reps=5, warm=1)
     emit(fmt('  with the cached real state (two GEMMs): what the training hook pays per evaluation', t))
-    rows = prdc.normalize_rows(fake)
-    bankT = prdc.bank_of(rows)
-    chunk = prdc.chunk_rows_of(bankT.shape[1])
+    rows = features.normalize_rows(fake)
+    bankT = features.bank_of(rows)
+    chunk = features.chunk_rows_of(bankT.shape[1])
     S = torch.empty(chunk, bankT.shape[1], device=dev)
     chunks = [(i, min(chunk, n - i)) for i in range(0, n, chunk)]
     thr = torch.empty(n, device=dev)
@@ -65,8 +65,8 @@ def whole(emit):
     rh = torch.empty(n, dtype=torch.int32, device=dev)
 
     def gemms():
-        for i, m in chunks:
-            prdc.similarities(rows[i:i + m], bankT, S[:m])
+        for _ in features.similarity_chunks(rows, bankT, S):
+            pass
 
     def kths():
         for i, m in chunks:
