@@ -27,7 +27,7 @@ CASES = [
     (2, 64, 32, 16, 64),      # non-square: 4 x 2 patches
     (1, 4, 8, 16, 64),        # 8 images per block, one present
     (3, 16, 32, 48, 192),     # one patch high, two wide (box 16 x 18); Cin = 48 (6 chunks), three cout blocks
-    (40, 16, 16, 16, 64),     # several items per block of the persistent grid (one chunk pair each)
+    (40, 16, 16, 16, 64),     # 40 items on 40 blocks (one chunk pair each): one item per block -- multi-item walks: test_wino_walks_gpu.py
     (9, 8, 16, 128, 64),      # 2 images per block (4 x 8 tiles each)
 ]
 
@@ -81,7 +81,7 @@ S2CASES = [
     (9, 16, 16, 16, 128),      # 8 x 8 grid: 8 images per block, ragged; two cout blocks
     (40, 8, 8, 32, 64),        # 4 x 4 grid: 32 images per block, ragged
     (2, 32, 16, 24, 64),       # non-square 16 x 8 grid (4 images per block); Cin = 24: three chunks per phase
-    (70, 8, 8, 16, 192),       # several items per block, three cout blocks
+    (70, 8, 8, 16, 192),       # three tile blocks x three cout blocks (data gradient: x four phases): 9 / 36 items, one per block
 ]
 
 
@@ -251,7 +251,7 @@ CASES44 = [
     (5, 8, 8, 64, 64),        # eight images per item, ragged: the half-waves of a pass sit in different images
     (2, 64, 32, 32, 64),      # non-square: four patches high
     (3, 16, 32, 64, 192),     # one patch per image, three cout blocks
-    (40, 16, 16, 32, 64),     # several items per block of the persistent grid
+    (40, 16, 16, 32, 64),     # 20 items on 24 blocks: one item per block, the blocks past an XCD's list idle
     (17, 8, 8, 32, 192),
     (1, 128, 64, 32, 64),     # 8 x 2 patches: boxes with real halos on every side
     (9, 16, 16, 128, 64),     # 16 chunks: eight pairs
@@ -298,7 +298,7 @@ CASES44N = [
     (9, 8, 8, 32, 32),        # eight images per item, ragged
     (2, 32, 64, 32, 96),      # patches of 16 x 32 pixels, 2 x 2 per image; three cout blocks
     (1, 128, 64, 64, 32),     # 8 x 2 patches: boxes with real halos on every side; eight chunks
-    (40, 16, 16, 32, 32),     # several items per block of the persistent grid
+    (40, 16, 16, 32, 32),     # 20 items on 24 blocks: one item per block, the blocks past an XCD's list idle
     (40, 4, 4, 32, 64),       # 4x4 maps (this variant whatever the cout count): a tile is an image, 32 per item, ragged; shared halos
     (70, 4, 4, 64, 96),       # three items per cout block, three cout blocks
 ]
@@ -366,7 +366,7 @@ S3CASES = [
     (40, 4, 16, 64),         # 4 x 4 grid: 32 images per item, ragged
     (2, 32, 16, 64),         # 32 x 32 grid: patches of 16 x 32 output pixels, 2 x 1 per image
     (1, 64, 32, 192),        # 4 x 2 patches per image, three cout blocks
-    (70, 8, 48, 64),         # several items per block; Cin = 48: six chunks per phase
+    (70, 8, 48, 64),         # 9 items on 16 blocks, one per block; Cin = 48: six chunks per phase
 ]
 
 
