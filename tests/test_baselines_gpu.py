@@ -66,9 +66,9 @@ def check(margin, family, what, out, ref):
 class Guard(object):
     """``shape`` inside NaN-filled storage with spare floats (a multiple of 4) on both sides."""
 
-    def __init__(self, shape, fill=None):
+    def __init__(self, shape, fill=None, shift=0):
         n = math.prod(shape)
-        self.pad = (math.prod(shape[1:]) + 3) // 4 * 4 + 4
+        self.pad = (math.prod(shape[1:]) + 3) // 4 * 4 + 4 + shift        # (shift: floats off 16-byte alignment)
         self.n = n
         self.buf = torch.full((n + 2 * self.pad,), NAN, device=DEV)
         self.view = self.buf[self.pad:self.pad + n].view(*shape)
@@ -79,9 +79,9 @@ class Guard(object):
         return bool(torch.isnan(self.buf[:self.pad]).all()) and bool(torch.isnan(self.buf[self.pad + self.n:]).all())
 
 
-def guarded(fn, x, params):
+def guarded(fn, x, params, out_shift=0):
     """fn(x, params, out=...) with all three operands in guard storage; returns the output on the host."""
-    gx, gp, go = Guard(tuple(x.shape), x), Guard(tuple(params.shape), params), Guard(tuple(x.shape))
+    gx, gp, go = Guard(tuple(x.shape), x), Guard(tuple(params.shape), params), Guard(tuple(x.shape), shift=out_shift)
     fn(gx.view, gp.view, go.view)
     torch.cuda.synchronize()
     assert gx.intact() and gp.intact() and go.intact(), 'a guard sentinel was overwritten'
@@ -113,6 +113,18 @@ def test_hfrt_forward_is_the_reference_bit_for_bit(tag, golden):
     for r in (0, F.shape[0] - 1):                          # B = 1 with a forced row
         out = guarded(lambda a, p, o: ops.hfrt(a, p, m, out=o), xf[r:r + 1].contiguous(), F[r:r + 1].contiguous())
         assert torch.equal(out, R.hfrt_forward(xf[r:r + 1], F[r:r + 1]))
+
+
+@pytest.mark.parametrize('W,m,shift', [(6, 5, 0), (7, 3, 0), (8, 7, 1), (32, 4, 2)])
+def test_hfrt_forward_one_pixel_per_thread_is_exact(W, m, shift):
+    """hfrt_fwd_kernel<false>: a width that is no multiple of 4, or an output off 16-byte alignment (the other instance makes
+    four columns per thread and stores them as one vector) -- the same index map, bit for bit, nothing else written."""
+    F = forced_hfrt_rows(m)
+    for B in (1, 5, F.shape[0]):
+        P = F[:B].contiguous() if B > 1 else F[-1:].contiguous()
+        x = torch.rand(B, 3, W, W, generator=torch.Generator().manual_seed(10 * W + B))
+        out = guarded(lambda a, p, o: ops.hfrt(a, p, m, out=o), x, P, out_shift=shift)
+        assert torch.equal(out, R.hfrt_forward(x, P)), (W, m, shift, B)
 
 
 @pytest.mark.parametrize('W,m', [(32, 4), (8, 7)])

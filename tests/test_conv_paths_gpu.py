@@ -12,6 +12,12 @@ ops.conv2d_wgrad with dbias -- and once with no epilogue at all.  Checked on the
     before and after (dwp: spare rows and columns past K; dbias: spare floats either side): every sentinel must stay NaN;
   * a Winograd-planned case (paths 7 - 11) gives BITWISE the result of the forced entry point of the family the path query
     names (ops.conv2d_wino / conv2d_wino_wgrad): the kernel that ran is the one the query reports.
+
+INSTANCE_CASES: inside a Winograd family the host picks a template instance by arithmetic no plan query reports (csrc/wino_host.h:
+the raw-box pieces per mover thread of wino22 / wino23, the raw-box width of wino44 / wino44n).  The instances that neither
+PATH_CASES nor the walks of tests/test_wino_walks_gpu.py launch (the record profiles/kernel_ledger.txt) run here through the
+forced entry point on the smallest geometry that selects them; tests/kernel_ledger.py restates the selection and
+tests/test_kernel_ledger_cpu.py holds each case to the instance it names.
 """
 import ctypes
 import math
@@ -21,6 +27,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_ref64 as R
+import kernel_ledger as L
 from contrad_amd import ops
 from contrad_amd._lib import lib
 
@@ -72,6 +79,14 @@ PATH_CASES = [
     (9, 0, False, 229, 8, 8, 32, 512, 3, 1, 1, 0, 1, 1, 'F(4x4,3x3) 8 x 8: 8 images per item, ragged last block'),
     (7, 0, False, 75, 8, 8, 16, 512, 3, 1, 1, 0, 1, 1, 'F(2x2,3x3) 8 x 8: 4 images per item, ragged last block'),
     (7, 1, False, 75, 8, 8, 512, 16, 3, 1, 1, 1, 0, 1, ''),
+]
+
+
+# the same layout with the path replaced by the family of the forced entry point and `what` by the instance the host selects:
+# one full image group and a ragged one (wino44n: 8 images per item on 8 x 8 maps; 32 x 32 maps: two items per image)
+INSTANCE_CASES = [
+    (11, 1, False, 11, 8, 8, 96, 32, 3, 1, 1, 1, 1, 1, 'wino44n::wino44n_kernel<1, 10>'),
+    (11, 1, False, 3, 32, 32, 96, 32, 3, 1, 1, 1, 1, 1, 'wino44n::wino44n_kernel<1, 34>'),
 ]
 
 
@@ -234,6 +249,42 @@ def test_conv_path_matches_float64(case, margin):
                 assert torch.equal(dwp[:, :K], dwb2[1:-1, :K]), 'the planned weight gradient is not the kernel path %d names' % P
                 if with_bias:
                     assert torch.equal(dbias, db2)
+
+
+@pytest.mark.parametrize('case', INSTANCE_CASES, ids=lambda c: c[14])
+def test_forced_winograd_instance_matches_float64(case, margin):
+    """A host-selected template instance on the forced entry point: float64 parity at the family's bound with every epilogue
+    term on and with none, sentinels intact, bitwise equal to a repeat."""
+    P, mode, _, N, H, W, C, K, k, s, p = case[:11]
+    assert L.wino_instance((N, H, W, C, K, k, s, p), mode, f44=P in (9, 11)) == case[14]
+    dev = torch.device('cuda')
+    ldx, ldy, ldw = case_lds(case)
+    d = case_desc(case)
+    Ho, Wo = d.Ho, d.Wo
+    g = torch.Generator().manual_seed(2000 + INSTANCE_CASES.index(case))
+    w, wp = _weights(case, g, dev)
+    if mode == 0:
+        inp, oshape, ldo = _input(N, H, W, C, ldx, g, dev), (N, Ho, Wo, K), ldy
+        bias = _rand((K,), g, dev, 0.3)
+    else:
+        inp, oshape, ldo = _input(N, Ho, Wo, K, ldy, g, dev), (N, H, W, C), ldx
+        bias = None
+    side = _input(*oshape, ldo, g, dev)                 # the forward's addend / the data gradient's activation reference
+    for epi in (True, False):
+        outs = []
+        for _rep in range(2):
+            out = Guarded(*oshape, ldo, float('nan'), dev)
+            _forced(P, mode, inp, wp, C, K, bias if epi else None, side if epi else None, SLOPE if epi else 1.0,
+                    GAIN if epi else 1.0, out.t)
+            torch.cuda.synchronize()
+            assert out.sentinels_intact(), '%s wrote outside its output' % case[14]
+            outs.append(out.t)
+        if mode == 0:
+            ref = R.fwd(inp, w, bias if epi else None, s, p, **(dict(slope=SLOPE, gain=GAIN, addend=side) if epi else {}))
+        else:
+            ref = R.dgrad(inp, w, (H, W), s, p, **(dict(act_ref=side, slope=SLOPE, gain=GAIN) if epi else {}))
+        check(margin, P, case[14], outs[0], ref)
+        assert torch.equal(outs[0], outs[1]), '%s is not repeatable' % case[14]
 
 
 def test_the_float64_references_agree():

@@ -685,3 +685,23 @@ def test_axpby(margin, n):
     torch.cuda.synchronize()
     assert gyy.intact() and gx.intact()
     check(margin, 'axpby', 'n=%d' % n, y, a * y0.double() + b * x.double())
+
+
+@pytest.mark.parametrize('n,pad', [(1, 4), (255, 4), (257, 1), (1024 * 256 + 3, 3)])
+def test_pull_host_is_a_copy_bit_for_bit(n, pad):
+    """contrad_pull_host (pull_kernel: the hand-over of the per-step draws, contrad_amd/hostio.py) reads device-mapped pinned
+    host memory and writes n floats: bit patterns (NaN payloads, -0, denormals) arrive unchanged, nothing else is written.
+    Sizes: one float, a ragged block, a misaligned destination, and one float more than the 1024 x 256 threads of the capped
+    grid move in their first trip."""
+    g = torch.Generator().manual_seed(n)
+    bits = torch.randint(-2 ** 31, 2 ** 31 - 1, (n,), generator=g, dtype=torch.int64).to(torch.int32)
+    bits[0] = -2 ** 31                                            # -0.0
+    if n > 3:
+        bits[1], bits[2], bits[3] = 0x7fc01234, 0x00000001, 0x7f800000          # a NaN payload, a denormal, +inf
+    src = bits.view(torch.float32).pin_memory()
+    gd, dst = flat((n,), pad=pad)
+    call('contrad_pull_host', src.data_ptr(), dst.data_ptr(), n, ops._stream())             # (as hostio._pull calls it)
+    torch.cuda.synchronize()
+    assert gd.intact()
+    assert torch.equal(dst.cpu().view(torch.int32), bits)
+    assert torch.equal(src.view(torch.int32), bits)               # the source is read only

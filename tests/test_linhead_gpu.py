@@ -15,6 +15,7 @@ import math
 import pytest
 import torch
 
+import kernel_ledger as L
 import linhead_ref64 as R
 from contrad_amd import ops
 from contrad_amd.evaluate.classifier import test_classifier as run_test_classifier
@@ -34,7 +35,7 @@ FAMILY_TOL = {                  # family: (max-norm, rel-L2)      observed worst
     'loss': (3.5e-7, 3.5e-7),                   # 6.6e-8 (a scalar: one figure)
     'dlogits': (7e-7, 3.7e-7),                  # 1.3e-7, 7.3e-8
     'gradW': (2.8e-6, 1.6e-6),                  # 5.6e-7, 3.2e-7
-    'gradb': (3.6e-6, 3.2e-6),                  # 7.2e-7, 6.5e-7
+    'gradb': (3.6e-6, 3.2e-6),                  # 7.2e-7, 6.5e-7   (a draw whose gradb cancels: see SEEDS)
     'W': (1e-6, 3.6e-7),                        # 2.0e-7, 7.2e-8
     'b': (2.4e-6, 1.4e-6),                      # 4.7e-7, 2.8e-7
     'traj_W': (2.8e-6, 6e-7),                   # 5.6e-7, 1.2e-7   (20 iterations)
@@ -131,43 +132,77 @@ def check_hits(meters, ref, y, N):
     assert m[3] == N
 
 
-# (N, K, C, ldf - K, c0, feature scale): launch form (K-splits, classes per thread, row tiles)
+# (N, K, C, ldf - K, c0, feature scale): launch form (K-splits, classes per thread, row tiles, classes per thread of the
+# weight gradient).  The two kernels are templates over the classes per thread -- linhead_logits_kernel<1..8>,
+# linhead_wgrad_kernel<1..4> -- and the cases below reach all twelve (tests/kernel_ledger.py).
 CASES = [
-    ((256, 8192, 10, 0, 0, 2.0), (128, 1, 4)),       # CIFAR-10 batch: one 64-wide chunk per split, 512 blocks
-    ((256, 8192, 100, 0, 0, 2.0), (64, 7, 4)),       # CIFAR-100 batch: two chunks per split (partials stay below F)
-    ((80, 8192, 10, 0, 0, 2.0), (128, 1, 2)),        # CIFAR's last train batch at 256: a partial second row tile
-    ((16, 8192, 100, 0, 0, 2.0), (64, 7, 1)),        # CIFAR's last test batch at 256
-    ((1, 8192, 10, 0, 0, 2.0), (128, 1, 1)),         # a single row
-    ((250, 512, 100, 0, 0, 2.0), (4, 7, 4)),         # snresnet18 features: few chunks, ragged last row tile
-    ((37, 300, 7, 0, 0, 2.0), (5, 1, 1)),            # K not a multiple of the chunk (ragged last chunk), odd C
-    ((5, 8192, 128, 0, 0, 2.0), (64, 8, 1)),         # the widest head
-    ((256, 8192, 10, 8, 4, 2.0), (128, 1, 4)),       # ldf > K, 16-byte aligned: vector loads on strided rows
-    ((37, 301, 7, 2, 1, 2.0), (5, 1, 1)),            # ldf > K, odd K and misaligned base: the scalar load path
-    ((256, 8192, 10, 0, 0, 90.0), (128, 1, 4)),      # unnormalised post-ReLU-like features (|x|^2 of about 4000)
+    ((256, 8192, 10, 0, 0, 2.0), (128, 1, 4, 1)),      # CIFAR-10 batch: one 64-wide chunk per split, 512 blocks
+    ((256, 8192, 100, 0, 0, 2.0), (64, 7, 4, 4)),      # CIFAR-100 batch: two chunks per split (partials stay below F)
+    ((80, 8192, 10, 0, 0, 2.0), (128, 1, 2, 1)),       # CIFAR's last train batch at 256: a partial second row tile
+    ((16, 8192, 100, 0, 0, 2.0), (64, 7, 1, 4)),       # CIFAR's last test batch at 256
+    ((1, 8192, 10, 0, 0, 2.0), (128, 1, 1, 1)),        # a single row
+    ((250, 512, 100, 0, 0, 2.0), (4, 7, 4, 4)),        # snresnet18 features: few chunks, ragged last row tile
+    ((37, 300, 7, 0, 0, 2.0), (5, 1, 1, 1)),           # K not a multiple of the chunk (ragged last chunk), odd C
+    ((5, 8192, 128, 0, 0, 2.0), (64, 8, 1, 4)),        # the widest head
+    ((256, 8192, 10, 8, 4, 2.0), (128, 1, 4, 1)),      # ldf > K, 16-byte aligned: vector loads on strided rows
+    ((37, 301, 7, 2, 1, 2.0), (5, 1, 1, 1)),           # ldf > K, odd K and misaligned base: the scalar load path
+    ((256, 8192, 10, 0, 0, 90.0), (128, 1, 4, 1)),     # unnormalised post-ReLU-like features (|x|^2 of about 4000)
+    # the template instances between the narrowest and the widest head: 70 rows (a ragged second row tile), K = 200 (a ragged
+    # last chunk), two or four K-splits
+    ((70, 200, 20, 0, 0, 2.0), (4, 2, 2, 1)),        # logits<2>
+    ((70, 200, 40, 0, 0, 2.0), (4, 3, 2, 2)),        # logits<3>, wgrad<2>
+    ((70, 200, 64, 0, 0, 2.0), (2, 4, 2, 2)),        # logits<4>: every class slot of the 16 x 4 layout is a class
+    ((70, 200, 72, 0, 0, 2.0), (2, 5, 2, 3)),        # logits<5>, wgrad<3>
+    ((70, 200, 72, 3, 1, 2.0), (2, 5, 2, 3)),        # ... on rows of odd stride from a misaligned base: the scalar loads
+    ((70, 200, 96, 0, 0, 2.0), (2, 6, 2, 3)),        # logits<6>
+    # fewer than five classes (AFHQ has three): every valid row is a top-5 hit; one class: loss 0 and dlogits 0 exactly
+    ((70, 200, 1, 0, 0, 2.0), (4, 1, 2, 1)),
+    ((70, 200, 2, 0, 0, 2.0), (4, 1, 2, 1)),
+    ((70, 200, 3, 0, 0, 2.0), (4, 1, 2, 1)),
 ]
+
+
+# Inputs are drawn with seed N + K + C, but for the draws named here.  (70, 200, 2) at its default seed 272 has a bias gradient
+# that cancels 221-fold (sum |dlogits| over the rows / |gradb|; the module's other draws stay below 8): against float64 the
+# kernel's gradb is then 7.4e-6 off in max-norm and the same sum in fp32 torch on the CPU 4.7e-6 (autograd) / 3.0e-6 (an explicit
+# column sum) -- the input's conditioning, not a property of the kernel, so the case draws a batch that cancels 3.4-fold
+# and the bound stays.  test_single_iteration asserts the cancellation of every 70-row draw from the float64 reference alone.
+SEEDS = {(70, 200, 2): 2}
+MAX_CANCELLATION = 8.0
 
 
 def test_launch_forms():
     for (N, K, C, _dl, _c0, _s), form in CASES:
-        assert ops.linhead_plan(N, K, C) == form, (N, K, C)
+        assert ops.linhead_plan(N, K, C) == form[:3], (N, K, C)
+        assert L.linhead_plan(N, K, C) == form, (N, K, C)            # (ct3 has no library query: the host rule restated)
         S = form[0]
         want = 4 * (64 + 4 * N + S * N * C)           # counter line, per-row scratch, partial sums
         assert ops.lib().raw('contrad_linhead_workspace_bytes')(N, K, C) == want
     assert ops.linhead_plan(256, 8192, 10) == ops.linhead_plan(256, 8192, 10)      # a pure function of (N, K, C)
 
 
-@pytest.mark.parametrize('case,form', CASES, ids=lambda v: 'x'.join(str(i) for i in v))
+# (ids: the case and the three plan-query figures of its form, as before the forms carried ct3)
+@pytest.mark.parametrize('case,form', CASES, ids=lambda v: 'x'.join(str(i) for i in (v[:3] if len(v) == 4 else v)))
 def test_single_iteration(case, form, margin):
     N, K, C, dld, c0, scale = case
-    assert ops.linhead_plan(N, K, C) == form
-    F, W, b, y = draw(N, K, C, seed=N + K + C, scale=scale)
+    assert ops.linhead_plan(N, K, C) == form[:3]
+    F, W, b, y = draw(N, K, C, seed=SEEDS.get((N, K, C), N + K + C), scale=scale)
     ref = R.head_ref64(F, W, b, y, lr=0.1)
+    if N == 70 and C > 1:
+        assert ref['dlogits'].abs().sum(0).max() < MAX_CANCELLATION * ref['gradb'].abs().max()
     Fd, G = run_iteration(F, W, b, y, 0.1, ldf=K + dld, c0=c0)
     for name in ('logits', 'dlogits', 'gradW', 'gradb', 'W', 'b'):
         check(margin, name, G[name].view, ref[name])
     m = G['meters'].view.cpu()
-    margin('linhead loss max-norm', abs(m[0].item() / N - ref['loss'].item()) / abs(ref['loss'].item()), FAMILY_TOL['loss'][0])
+    if C == 1:                                       # log-sum-exp of one logit is the logit: nothing to round
+        assert ref['loss'].item() == 0 and m[0].item() == 0 and bool((G['dlogits'].view == 0).all())
+    else:
+        margin('linhead loss max-norm', abs(m[0].item() / N - ref['loss'].item()) / abs(ref['loss'].item()), FAMILY_TOL['loss'][0])
+    if N < 100:                                      # check_hits allows no near-tie row below 100 rows: the draw has none
+        assert int(R.near_tie_rows(ref['logits'], y).sum()) == 0
     check_hits(G['meters'].view, ref, y, N)
+    if C < 5:                                        # at most four logits can be above the label's
+        assert ref['hits5'].sum().item() == N and m[2].item() == N
     for name, gd in G.items():
         assert gd.intact(), name
     assert float(G['lr'].view) == pytest.approx(0.1, rel=1e-7)

@@ -452,3 +452,70 @@ def test_minibatch_stddev(margin, case):
     check(margin, 'mbstd', what + ' mode 2 d/dgy', g2b.view, r2b)
     assert torch.equal(g2b.view[:, :, :C], gh.view)
     assert torch.equal(g2b.view[:, :, C + 1:], torch.zeros(B, P, Cp - C - 1, device=DEV))
+
+
+# ======================================================================================================================
+# modconv_tables_kernel, modconv_demod_kernel: the generator's weight tables and demodulation factors, one launch each
+# ======================================================================================================================
+U24 = 2.0 ** -24
+# (Cout, Cin, k, transposed, demodulate): ragged 32 x 32 tiles in both orientations, 1x1 and 3x3, a 3-channel ToRGB
+TABLE_CASES = [(64, 32, 3, False, True), (32, 64, 3, True, True), (3, 48, 1, True, False), (40, 36, 3, False, True),
+               (70, 33, 3, True, True), (128, 256, 1, False, False)]
+
+
+def test_modconv_tables_match_float64():
+    """contrad_modconv_tables (six layers, one launch).  A packed weight is one fp32 product w * scale: it must equal the
+    float64 product rounded once.  A demodulation table entry is a sum of T <= 9 squares of those products: all terms are
+    positive, so any order and fused or unfused multiply-adds stay within (T + 3) * 2^-24 of the float64 sum, relative, element
+    by element (one rounding of the product entering squared, one per square, T - 1 additions).  Packed weights are column
+    slices of wider NaN buffers with a spare row either side: every sentinel must survive."""
+    g = torch.Generator().manual_seed(8)
+    layers, refs, guards = [], [], []
+    for co, ci, k, tr, dm in TABLE_CASES:
+        w = torch.randn(co, ci, k, k, generator=g)
+        scale = float(torch.tensor(1.0 / math.sqrt(ci * k * k), dtype=torch.float32))
+        rows, cols = (k * k * co, ci) if tr else (k * k * ci, co)
+        wbuf = torch.full((rows + 2, cols + 8), NAN, device=DEV)
+        gq = Guard((ci, co)) if dm else None
+        gw = Guard(tuple(w.shape), fill=w.to(DEV))
+        layers.append((gw.view, wbuf[1:-1, 4:4 + cols], gq.view if dm else None, tr, scale))
+        ws = (w.double() * scale).float().double()                # the fp32 product, exactly
+        ref_wp = (ws.permute(2, 3, 0, 1).reshape(k * k * co, ci) if tr else ws.permute(2, 3, 1, 0).reshape(k * k * ci, co))
+        refs.append((ref_wp, ws.pow(2).sum((2, 3)).t() if dm else None, k * k))
+        guards.append((wbuf, gq, gw, w))
+    ops.modconv_tables(layers)
+    torch.cuda.synchronize()
+    for (wd, wp, wsq, tr, scale), (ref_wp, ref_wsq, T), (wbuf, gq, gw, w) in zip(layers, refs, guards):
+        assert torch.equal(wp.cpu().double(), ref_wp)
+        inner = torch.zeros_like(wbuf, dtype=torch.bool)
+        inner[1:-1, 4:4 + wp.shape[1]] = True
+        assert bool(torch.isnan(wbuf[~inner]).all()), 'a packed weight wrote outside its columns'
+        assert gw.intact() and torch.equal(wd.cpu(), w)
+        if wsq is not None:
+            assert gq.intact()
+            err = (wsq.cpu().double() - ref_wsq).abs() / ref_wsq
+            assert err.max().item() <= (T + 3) * U24, (tr, T, err.max().item())
+
+
+@pytest.mark.parametrize('B', [5, 16, 70])
+def test_modconv_demod_matches_float64(B):
+    """contrad_modconv_demod: out = rsqrt(style^2 @ wsq + eps) of six layers from one launch (ragged 64-channel output chunks,
+    ragged 16-sample blocks, Cin of exactly one 512-channel LDS chunk, two, and a ragged second one).  Every term of the sum
+    is non-negative, so in any order with fused or unfused multiply-adds it is within (Cin + 2) * 2^-24 of the float64 sum,
+    relative (one rounding per square, at most one per product, Cin - 1 additions, eps); the reciprocal square root halves that
+    and adds its own rounding and the hardware approximation's error, allowed 4 * 2^-24 here."""
+    g = torch.Generator().manual_seed(9)
+    jobs, refs, guards = [], [], []
+    for cin, k in [(512, 512), (32, 64), (100, 36), (1024, 300), (600, 70), (64, 3)]:
+        st = torch.randn(B, cin, generator=g)
+        wsq = torch.rand(cin, k, generator=g) / cin
+        gs, gw, go = Guard((B, cin), fill=st.to(DEV)), Guard((cin, k), fill=wsq.to(DEV)), Guard((B, k))
+        jobs.append((gs.view, gw.view, go.view))
+        refs.append((torch.rsqrt((st.double() ** 2) @ wsq.double() + 1e-8), cin))
+        guards.append((gs, gw, go))
+    ops.modconv_demod(jobs, 1e-8)
+    torch.cuda.synchronize()
+    for (st, wsq, out), (ref, cin), gds in zip(jobs, refs, guards):
+        assert all(gd.intact() for gd in gds)
+        err = (out.cpu().double() - ref).abs() / ref
+        assert torch.isfinite(out).all() and err.max().item() <= ((cin + 2) / 2 + 4) * U24, (cin, err.max().item())
