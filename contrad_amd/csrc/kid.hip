@@ -1,7 +1,9 @@
 // Kernel distance (KID) on a similarity matrix (gfx950): the one reduction of contrad_amd/kid.py.
 //
-//   kid_sums    sum over a block of S of (gamma * s + coef0)^3 with the column self0 + row left out of every row by
-//               index.  Every term is formed and added in float64.  A workgroup takes 4 * rpw rows x 256 columns
+//   kid_sums    sum over a block of S of k(s) with the column self0 + row left out of every row by index; k is chosen
+//               by the run-time `kind` (wave-uniform): 0, (gamma * s + coef0)^3; 1, the rational-quadratic mixture
+//               sum over alpha in {1/2, 1, 2} of (1 + u / (2 alpha))^-alpha at u = max(2 - 2 s, 0), the squared distance
+//               of two unit vectors (IEEE sqrt and division only).  Every term is formed and added in float64.  A workgroup takes 4 * rpw rows x 256 columns
 //               (rpw = 32, or 4 where that would leave fewer than 1024 workgroups: a 1000 x 1000 block is 252 of them
 //               instead of 32); a wave takes every fourth row of the tile, a lane four consecutive columns (one 16-byte
 //               load where the address allows), four rows in flight: prdc_count_kernel's shape.  A lane sums its terms
@@ -37,8 +39,20 @@ KidPlan kid_plan(int M, int n) {
   return p;
 }
 
+// One term in float64.  kind 1: a NaN stays a NaN through the comparison, an s slightly above 1 gives u = 0.
+__device__ __forceinline__ double kid_term(int kind, float s, double gamma, double coef0) {
+  if (kind == 0) {
+    const double x = gamma * (double)s + coef0;
+    return x * x * x;
+  }
+  double u = 2.0 - 2.0 * (double)s;
+  u = u < 0.0 ? 0.0 : u;
+  const double q = 1.0 + 0.25 * u;
+  return 1.0 / sqrt(1.0 + u) + 1.0 / (1.0 + 0.5 * u) + 1.0 / (q * q);
+}
+
 __global__ __launch_bounds__(KID_THREADS) void kid_sums_kernel(const float* __restrict__ S, long long ldS, int M, int n,
-                                                               long long self0, double gamma, double coef0,
+                                                               long long self0, int kind, double gamma, double coef0,
                                                                double* __restrict__ partial, int ctiles, int rpw, int vec_ok) {
   __shared__ double red[4];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -69,9 +83,9 @@ __global__ __launch_bounds__(KID_THREADS) void kid_sums_kernel(const float* __re
       const long long excl = self0 >= 0 ? self0 + r0 + 4 * (t0 + u) : -1;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const double x = gamma * (double)v[u][j] + coef0;
+        const double k = kid_term(kind, v[u][j], gamma, coef0);
         const bool in = live && c0 + j < n && c0 + j != excl;     // left out by index: a select, so a NaN there is not seen
-        acc += in ? x * x * x : 0.0;
+        acc += in ? k : 0.0;
       }
     }
   }
@@ -106,11 +120,13 @@ extern "C" long long contrad_kid_sums_workspace_bytes(int M, int n) {
   return p.blocks * (long long)sizeof(double);
 }
 
-extern "C" int contrad_kid_sums(const float* S, long long ldS, int M, int n, long long self0, double gamma, double coef0,
-                                int accumulate, double* out, void* workspace, long long workspace_bytes,
-                                contrad_stream_t stream) {
+namespace {
+
+int mmd_sums(const float* S, long long ldS, int M, int n, long long self0, int kind, double gamma, double coef0, int accumulate,
+             double* out, void* workspace, long long workspace_bytes, contrad_stream_t stream) {
   CONTRAD_ARG(S && out);
   CONTRAD_ARG(M >= 1 && n >= 1 && ldS >= n);
+  CONTRAD_ARG(kind == 0 || kind == 1);
   CONTRAD_ARG(isfinite(gamma) && isfinite(coef0));
   const KidPlan p = kid_plan(M, n);
   CONTRAD_ARG(p.blocks <= 0x7fffffffll);
@@ -119,10 +135,24 @@ extern "C" int contrad_kid_sums(const float* S, long long ldS, int M, int n, lon
   const int vec_ok = (ldS % 4 == 0 && ((uintptr_t)S & 15) == 0) ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;
   double* partial = (double*)workspace;
-  hipLaunchKernelGGL(kid_sums_kernel, dim3((unsigned)p.blocks), dim3(KID_THREADS), 0, st, S, ldS, M, n, self0, gamma, coef0,
-                     partial, (int)p.ctiles, p.rpw, vec_ok);
+  hipLaunchKernelGGL(kid_sums_kernel, dim3((unsigned)p.blocks), dim3(KID_THREADS), 0, st, S, ldS, M, n, self0, kind, gamma,
+                     coef0, partial, (int)p.ctiles, p.rpw, vec_ok);
   CONTRAD_CHECK_LAUNCH();
   hipLaunchKernelGGL(kid_final_kernel, dim3(1), dim3(KID_THREADS), 0, st, partial, (int)p.blocks, accumulate ? 1 : 0, out);
   CONTRAD_CHECK_LAUNCH();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int contrad_kid_sums(const float* S, long long ldS, int M, int n, long long self0, double gamma, double coef0,
+                                int accumulate, double* out, void* workspace, long long workspace_bytes,
+                                contrad_stream_t stream) {
+  return mmd_sums(S, ldS, M, n, self0, 0, gamma, coef0, accumulate, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int contrad_mmd_sums(const float* S, long long ldS, int M, int n, long long self0, int kind, double gamma,
+                                double coef0, int accumulate, double* out, void* workspace, long long workspace_bytes,
+                                contrad_stream_t stream) {
+  return mmd_sums(S, ldS, M, n, self0, kind, gamma, coef0, accumulate, out, workspace, workspace_bytes, stream);
 }

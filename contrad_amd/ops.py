@@ -1273,6 +1273,37 @@ def kid_sums(S, n, self0=-1, gamma=1.0, coef0=1.0, out=None, accumulate=False):
     return out
 
 
+MMD_KINDS = {'poly3': 0, 'rq': 1}                                           # contrad_mmd_sums's `kind`
+
+
+def mmd_sums(S, n, kind='poly3', self0=-1, gamma=1.0, coef0=1.0, out=None, accumulate=False):
+    """``kid_sums`` with the kernel chosen by ``kind``: 'poly3' (or 0), (gamma * s + coef0)^3, bit for bit ``kid_sums``;
+    'rq' (or 1), the rational-quadratic mixture 1 / sqrt(1 + u) + 1 / (1 + u / 2) + 1 / (1 + u / 4)^2 at
+    u = max(2 - 2 s, 0) -- S holds similarities of UNIT vectors; gamma and coef0 are not read but must be finite.
+    contrad_mmd_sums's contract (include/contrad_hip.h)."""
+    M, ldS, n = _chk_S(S, n)
+    if kind not in MMD_KINDS and kind not in MMD_KINDS.values():
+        raise RuntimeError('contrad_hip: mmd_sums kind %r (one of %s)' % (kind, ', '.join(MMD_KINDS)))
+    kind = MMD_KINDS.get(kind, kind)
+    gamma, coef0 = float(gamma), float(coef0)
+    if not (math.isfinite(gamma) and math.isfinite(coef0)):
+        raise RuntimeError('contrad_hip: mmd_sums needs a finite gamma and coef0, got %r, %r' % (gamma, coef0))
+    if out is None:
+        if accumulate:
+            raise RuntimeError('contrad_hip: mmd_sums with accumulate adds to `out`')
+        out = torch.empty((1,), device=S.device, dtype=torch.float64)
+    _chk_vec(out, 'out', 1, torch.float64)
+    if out.device != S.device:
+        raise RuntimeError('contrad_hip: out is on %s, S on %s' % (out.device, S.device))
+    nbytes = lib().raw('contrad_kid_sums_workspace_bytes')(M, n)
+    if nbytes < 0:
+        raise RuntimeError('contrad_hip: bad mmd_sums shape (%d)' % nbytes)
+    ws = _workspace(nbytes, S.device)
+    lib().call('contrad_mmd_sums', _p(S), ctypes.c_longlong(ldS), M, n, ctypes.c_longlong(int(self0)), int(kind), gamma, coef0,
+               1 if accumulate else 0, _p(out), _p(ws), ctypes.c_longlong(nbytes), _stream())
+    return out
+
+
 # ---- cDDLS sampling (csrc/cddls.hip) ----
 def _flat_f32(t, name):
     _chk(t, name)

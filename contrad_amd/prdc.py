@@ -26,7 +26,8 @@ fake rows, S_XY = X Y^T:
 which follows ``KNNMonitor``: modules of its own, so that the training trajectory does not move by a bit.  ``--prdc_best
 METRIC`` keeps ``gen_best.pt`` / ``dis_best.pt`` (/ ``gen_ema_best.pt``), the names the reference gives its best-FID
 checkpoints, for the best value of that metric.  ``--prdc_kid`` adds the kernel distance of contrad_amd/kid.py to every
-evaluation (``kid_<seed>.csv``; ``--prdc_best kid`` selects its minimum).
+evaluation (``kid_<seed>.csv``; ``--prdc_best kid`` selects its minimum); ``--prdc_kid_kernel rq`` makes that the
+rational-quadratic distance, in ``kid_rq_<seed>.csv``.
 """
 import os
 from argparse import SUPPRESS
@@ -150,10 +151,12 @@ class PRDCMonitor(object):
     t_R are computed once, here.  ``best``: one of METRICS; ``update`` then says whether the evaluation improved it (the
     caller writes the ``*_best.pt`` files); a run resumed from the checkpoint of step ``resumed_step`` reads the best value
     up to that step back from its csv (``best_in_csv``).  ``kid`` (``--prdc_kid``): each evaluation also appends
-    ``step,kid,kid_std`` to ``kid_<eval_seed>.csv`` (contrad_amd/kid.py); ``best`` may then be ``'kid'``, which is minimised."""
+    ``step,kid,kid_std`` to ``kid_<eval_seed>.csv`` (contrad_amd/kid.py); ``best`` may then be ``'kid'``, which is minimised.  ``kid_kernel``
+    (``--prdc_kid_kernel``): 'rq' computes the rational-quadratic distance instead, into ``kid_rq_<eval_seed>.csv`` (never into
+    ``kid_<eval_seed>.csv``: the two are different numbers), which ``best='kid'`` then tracks and reads back."""
 
     def __init__(self, logdir, architecture, image_size, device, seed, data_path, encoder_path, encoder_arch=None, k=5,
-                 n_fake=10000, batch=500, best=None, resumed_step=0, P=None, kid=False):
+                 n_fake=10000, batch=500, best=None, resumed_step=0, P=None, kid=False, kid_kernel='poly3'):
         real = features.load_images(data_path, 'x_train')
         if tuple(real.shape[1:]) != tuple(image_size):
             raise ValueError('%s: x_train holds %s images, the generator makes %s' % (data_path, tuple(real.shape[1:]), tuple(image_size)))
@@ -162,12 +165,16 @@ class PRDCMonitor(object):
             raise ValueError('--prdc_best %r (one of %s)' % (best, ', '.join(BEST_CHOICES)))
         if best == 'kid' and not kid:
             raise ValueError('--prdc_best kid needs --prdc_kid')
+        kid_mod.check_kernel_name(kid_kernel)
+        if kid_kernel != 'poly3' and not kid:
+            raise ValueError('--prdc_kid_kernel needs --prdc_kid')
         if kid:
             kid_mod.check_sizes(len(real), n_fake)
         self.k, self.n_fake, self.batch, self.device, self.metric = int(k), int(n_fake), int(batch), device, best
         self.eval_seed = eval_seed_of(seed)
         self.path = os.path.join(logdir, 'prdc_%d.csv' % self.eval_seed)
-        self.kid_path = os.path.join(logdir, 'kid_%d.csv' % self.eval_seed) if kid else None
+        self.kid_kernel = kid_kernel
+        self.kid_path = os.path.join(logdir, kid_csv_name(kid_kernel) % self.eval_seed) if kid else None
         self.n_real = len(real)
         self.G = own_network('G', architecture, image_size, device, P)
         with preserved_rng(device):                                        # the constructors draw the initial weights
@@ -198,7 +205,8 @@ class PRDCMonitor(object):
             feats = features.extract_features(self.E, fake, self.batch)
             out = prdc(None, feats, self.k, real_state=self.real_state, normalize=False)
             if self.kid_path is not None:                                  # the same fake features, the same real rows (bankT)
-                d = kid_mod.kid(None, feats, seed=self.eval_seed, normalize=False, real_bank=(self.real_state[0], self.n_real))
+                d = kid_mod.kid(None, feats, seed=self.eval_seed, normalize=False, real_bank=(self.real_state[0], self.n_real),
+                                kernel=self.kid_kernel)
                 out['kid'], out['kid_std'] = d['kid'], d['kid_std']
         lines = []
         for path, _, line_of in self.files:
@@ -219,12 +227,18 @@ class PRDCMonitor(object):
         lines = ['[Steps %7d] [precision %.4f] [recall %.4f] [density %.4f] [coverage %.4f]%s' % (
             step, out['precision'], out['recall'], out['density'], out['coverage'], mark(self.metric != 'kid'))]
         if 'kid' in out:
-            lines.append('[Steps %7d] [kid %.6f +- %.6f]%s' % (step, out['kid'], out['kid_std'], mark(self.metric == 'kid')))
+            lines.append('[Steps %7d] [%s %.6f +- %.6f]%s' % (step, 'kid' if self.kid_kernel == 'poly3' else 'kid_' + self.kid_kernel,
+                                                              out['kid'], out['kid_std'], mark(self.metric == 'kid')))
         return lines
 
 
 HOOK_DEFAULTS = {'prdc_data': None, 'prdc_encoder': None, 'prdc_encoder_arch': None, 'prdc_k': 5, 'prdc_n': 10000, 'prdc_best': None,
-                 'prdc_kid': False}
+                 'prdc_kid': False, 'prdc_kid_kernel': 'poly3'}
+
+
+def kid_csv_name(kid_kernel):
+    """``kid_%d.csv`` for the cubic kernel, ``kid_rq_%d.csv`` for the rational-quadratic one."""
+    return 'kid_%d.csv' if kid_kernel == 'poly3' else 'kid_' + kid_kernel + '_%d.csv'
 
 
 def add_hook_arguments(parser):
@@ -251,6 +265,10 @@ def add_hook_arguments(parser):
                         help='with --prdc_data: every evaluation also appends step,kid,kid_std to kid_<seed>.csv: the kernel '
                              'distance (cubic kernel, gamma = coef0 = 1, 100 subsets of up to 1000) of the same fake features '
                              'from the real set, comparable only under one --prdc_encoder file, never with Inception-based KID')
+    parser.add_argument('--prdc_kid_kernel', type=str, choices=kid_mod.KERNELS, **off,
+                        help='with --prdc_kid: poly3 (default), or rq: the rational-quadratic mixture (alpha = 1/2, 1, 2; a '
+                             'characteristic kernel) is computed instead and appended to kid_rq_<seed>.csv, never into '
+                             'kid_<seed>.csv; --prdc_best kid then tracks that file')
 
 
 def hook_options(P):
@@ -267,6 +285,8 @@ def check_hook_arguments(P):
     given = [name for name in HOOK_DEFAULTS if name != 'prdc_data' and hasattr(P, name)]
     if not H.prdc_data and given:
         raise ValueError('%s do%s nothing without --prdc_data FILE.npz' % (', '.join('--' + g for g in given), 'es' if len(given) == 1 else ''))
+    if hasattr(P, 'prdc_kid_kernel') and not H.prdc_kid:
+        raise ValueError('--prdc_kid_kernel needs --prdc_kid: without it no kernel distance is computed')
     if H.prdc_best == 'kid' and not H.prdc_kid:
         raise ValueError('--prdc_best kid needs --prdc_kid: without it no kernel distance is computed')
     return H

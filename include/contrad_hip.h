@@ -787,6 +787,17 @@ long long contrad_kid_sums_workspace_bytes(int M, int n);
  * ldS < n, a non-finite gamma or coef0, a workspace that is null, smaller than the query says or not 8-byte aligned. */
 int contrad_kid_sums(const float* S, long long ldS, int M, int n, long long self0, double gamma, double coef0,
                      int accumulate, double* out, void* workspace, long long workspace_bytes, contrad_stream_t stream);
+/* contrad_kid_sums with the kernel chosen by `kind`: out[0] = (accumulate ? out[0] : 0) + sum over i < M, j < n,
+ * j != self0 + i of k((double)S[i][j]), everything else (layout, exclusion by index, float64 terms and sums, the same
+ * workspace query contrad_kid_sums_workspace_bytes, no atomics, two calls bitwise equal) as above.
+ *   kind 0: k(s) = (gamma * s + coef0)^3 -- bit for bit contrad_kid_sums;
+ *   kind 1: the rational-quadratic mixture on unit vectors, u = 2 - 2 s clamped below at 0 (a NaN stays a NaN; an s
+ *           slightly above 1 gives u = 0), k(s) = 1 / sqrt(1 + u) + 1 / (1 + u / 2) + 1 / (1 + u / 4)^2, that is the sum
+ *           over alpha in {1/2, 1, 2} of (1 + u / (2 alpha))^-alpha; IEEE sqrt and division only.  gamma and coef0 are
+ *           not read but must still be finite.
+ * -EINVAL (before any GPU call) on everything contrad_kid_sums refuses and on a kind outside {0, 1}. */
+int contrad_mmd_sums(const float* S, long long ldS, int M, int n, long long self0, int kind, double gamma, double coef0,
+                     int accumulate, double* out, void* workspace, long long workspace_bytes, contrad_stream_t stream);
 
 #ifdef __cplusplus
 }
