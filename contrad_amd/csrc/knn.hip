@@ -14,10 +14,16 @@
 //   5. vote      idx / val out (val re-read from S: the very floats); labels and expf(val * inv_temp) staged in LDS;
 //                thread c adds the weights of class c in rank order; the block's argmax under the same key order.
 //
+// Leave-self-out (contrad_knn_select_loo): with self0 >= 0 row q of the launch is row self0 + q of the bank it is compared
+// with and leaves that column out BY INDEX (contrad_prdc_kth's convention; a duplicate elsewhere in the bank is a neighbour
+// like any other).  A run-time, block-uniform argument of the one kernel: the column takes part in no histogram and in
+// neither tally of the compaction, so steps 2 to 5 see a row of n - 1 columns.  self0 < 0 is the kernel as it was.
+//
 // The row is read five times (four digits and the compaction) and never staged: the caller hands over chunks of S small
 // enough to be served from cache (contrad_amd/knn.py), and at n = 50 000 a row is 200 KB, beyond the LDS of a CU.
 #include "../../include/contrad_hip.h"
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -38,10 +44,10 @@ __device__ __forceinline__ unsigned long long knn_word(unsigned key, unsigned co
 }
 
 __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(const float* __restrict__ S, long long ldS, int n,
-                                                                 const long long* __restrict__ labels, int C, int k,
-                                                                 int P, float inv_temp, int* __restrict__ idx,
-                                                                 float* __restrict__ val, float* __restrict__ scores,
-                                                                 int* __restrict__ pred) {
+                                                                 long long self0, const long long* __restrict__ labels,
+                                                                 int C, int k, int P, float inv_temp,
+                                                                 int* __restrict__ idx, float* __restrict__ val,
+                                                                 float* __restrict__ scores, int* __restrict__ pred) {
   __shared__ unsigned hist[4][256];
   __shared__ unsigned long long words[KNN_MAX_K];
   __shared__ int lab_s[KNN_MAX_K];
@@ -53,85 +59,98 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(const float* __
   const long long q = blockIdx.x;
   const float* __restrict__ row = S + q * ldS;
   const unsigned un = (unsigned)n;
+  // Leave-self-out (block-uniform): row q of the launch is global row self0 + q and never sees column `ex` of its own bank,
+  // whatever that column holds.  Steps 2 and 3 are written once and compiled twice: LOO = false is the row as it ever was,
+  // without a test per element; LOO = true skips `ex` in every histogram and in both tallies of the compaction.
+  const bool loo_row = self0 >= 0 && self0 + q < (long long)n;
+  const unsigned ex = loo_row ? (unsigned)(self0 + q) : 0xffffffffu;
+  unsigned T = 0u, cgt = 0u, krem = (unsigned)k;
 
-  // ---- 2. the k-th largest key: `prefix` after four digits; `krem` of the columns equal to it are neighbours ----
-  unsigned prefix = 0u, krem = (unsigned)k;
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 24 - 8 * pass;
-    const unsigned himask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
-    for (int i = tid; i < 4 * 256; i += KNN_THREADS) (&hist[0][0])[i] = 0u;
-    __syncthreads();
-    for (unsigned j = tid; j < un; j += KNN_THREADS) {
-      const unsigned key = knn_key(row[j]);
-      if ((key & himask) == prefix) atomicAdd(&hist[w][(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    const unsigned cnt = hist[0][tid] + hist[1][tid] + hist[2][tid] + hist[3][tid];   // thread t owns bin t
-    unsigned suf = cnt;                                                               // sum over the bins >= t of this wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_down(suf, o, 64);
-      if (lane + o < 64) suf += t;
-    }
-    if (lane == 0) wtot[0][w] = suf;
-    __syncthreads();
-    unsigned above = suf - cnt;                                                       // columns in higher bins
-    for (int ww = w + 1; ww < 4; ++ww) above += wtot[0][ww];
-    if (above < krem && krem <= above + cnt) {                                        // exactly one bin
-      sel[0] = (unsigned)tid;
-      sel[1] = krem - above;
-    }
-    __syncthreads();
-    prefix |= sel[0] << shift;
-    krem = sel[1];
-  }
-  const unsigned T = prefix, cgt = (unsigned)k - krem;                                // cgt columns have a key above T
-
-  // ---- 3. ordered compaction: words[0, cgt) keys above T, words[cgt, k) the first krem columns equal to T ----
-  for (int r = k + tid; r < P; r += KNN_THREADS) words[r] = 0ull;                     // padding sorts last
-  unsigned base_g = 0u, base_e = 0u;
-  int buf = 0;
-  for (unsigned c0 = 0u; c0 < un; c0 += KNN_CHUNK, buf ^= 1) {
-    const unsigned j0 = c0 + 4u * tid;
-    unsigned key4[4];
-    unsigned g = 0u, e = 0u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const bool in = j0 + i < un;
-      key4[i] = in ? knn_key(row[j0 + i]) : 0u;
-      g += (in && key4[i] > T) ? 1u : 0u;
-      e += (in && key4[i] == T) ? 1u : 0u;
-    }
-    const unsigned p = g | (e << 16);                  // both counts <= 1024 per round: the two scans share a word
-    unsigned inc = p;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wtot[buf][w] = inc;
-    __syncthreads();
-    unsigned off = inc - p, tot = 0u;
-    for (int ww = 0; ww < 4; ++ww) {
-      const unsigned t = wtot[buf][ww];
-      if (ww < w) off += t;
-      tot += t;
-    }
-    unsigned pg = base_g + (off & 0xffffu), pe = base_e + (off >> 16);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (j0 + i >= un) break;
-      if (key4[i] > T) {
-        words[pg++] = knn_word(key4[i], j0 + i);       // pg < cgt: exactly cgt columns lie above T
-      } else if (key4[i] == T) {
-        if (pe < krem) words[cgt + pe] = knn_word(key4[i], j0 + i);
-        ++pe;
+  auto select_and_compact = [&](auto loo) {
+    constexpr bool LOO = decltype(loo)::value;
+    // ---- 2. the k-th largest key: `prefix` after four digits; `krem` of the columns equal to it are neighbours ----
+    unsigned prefix = 0u;
+    for (int pass = 0; pass < 4; ++pass) {
+      const int shift = 24 - 8 * pass;
+      const unsigned himask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
+      for (int i = tid; i < 4 * 256; i += KNN_THREADS) (&hist[0][0])[i] = 0u;
+      __syncthreads();
+      for (unsigned j = tid; j < un; j += KNN_THREADS) {
+        const unsigned key = knn_key(row[j]);
+        if (!(LOO && j == ex) && (key & himask) == prefix) atomicAdd(&hist[w][(key >> shift) & 255u], 1u);
       }
+      __syncthreads();
+      const unsigned cnt = hist[0][tid] + hist[1][tid] + hist[2][tid] + hist[3][tid];   // thread t owns bin t
+      unsigned suf = cnt;                                                               // sum over the bins >= t of this wave
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_down(suf, o, 64);
+        if (lane + o < 64) suf += t;
+      }
+      if (lane == 0) wtot[0][w] = suf;
+      __syncthreads();
+      unsigned above = suf - cnt;                                                       // columns in higher bins
+      for (int ww = w + 1; ww < 4; ++ww) above += wtot[0][ww];
+      if (above < krem && krem <= above + cnt) {                                        // exactly one bin
+        sel[0] = (unsigned)tid;
+        sel[1] = krem - above;
+      }
+      __syncthreads();
+      prefix |= sel[0] << shift;
+      krem = sel[1];
     }
-    base_g += tot & 0xffffu;
-    base_e += tot >> 16;
-    if (base_g >= cgt && base_e >= krem) break;        // (uniform) the k neighbours are complete
-  }
+    T = prefix;
+    cgt = (unsigned)k - krem;                                                           // cgt columns have a key above T
+
+    // ---- 3. ordered compaction: words[0, cgt) keys above T, words[cgt, k) the first krem columns equal to T ----
+    for (int r = k + tid; r < P; r += KNN_THREADS) words[r] = 0ull;                     // padding sorts last
+    unsigned base_g = 0u, base_e = 0u;
+    int buf = 0;
+    for (unsigned c0 = 0u; c0 < un; c0 += KNN_CHUNK, buf ^= 1) {
+      const unsigned j0 = c0 + 4u * tid;
+      unsigned key4[4];
+      unsigned g = 0u, e = 0u;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool in = j0 + i < un && !(LOO && j0 + i == ex);   // the column left out is in neither tally
+        key4[i] = in ? knn_key(row[j0 + i]) : 0u;
+        g += (in && key4[i] > T) ? 1u : 0u;
+        e += (in && key4[i] == T) ? 1u : 0u;
+      }
+      const unsigned p = g | (e << 16);                  // both counts <= 1024 per round: the two scans share a word
+      unsigned inc = p;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+      }
+      if (lane == 63) wtot[buf][w] = inc;
+      __syncthreads();
+      unsigned off = inc - p, tot = 0u;
+      for (int ww = 0; ww < 4; ++ww) {
+        const unsigned t = wtot[buf][ww];
+        if (ww < w) off += t;
+        tot += t;
+      }
+      unsigned pg = base_g + (off & 0xffffu), pe = base_e + (off >> 16);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (j0 + i >= un) break;
+        if (LOO && j0 + i == ex) continue;               // never written (its key4 is 0, which a NaN threshold T equals)
+        if (key4[i] > T) {
+          words[pg++] = knn_word(key4[i], j0 + i);       // pg < cgt: exactly cgt columns lie above T
+        } else if (key4[i] == T) {
+          if (pe < krem) words[cgt + pe] = knn_word(key4[i], j0 + i);
+          ++pe;
+        }
+      }
+      base_g += tot & 0xffffu;
+      base_e += tot >> 16;
+      if (base_g >= cgt && base_e >= krem) break;        // (uniform) the k neighbours are complete: `ex` is in no count
+    }
+  };
+  if (loo_row) select_and_compact(std::true_type{});
+  else select_and_compact(std::false_type{});
 
   // ---- 4. bitonic sort, descending ----
   for (int size = 2; size <= P; size <<= 1) {
@@ -189,6 +208,24 @@ inline bool knn_shape_ok(int M, int n, int k, int C) {
   return M >= 1 && n >= 1 && k >= 1 && k <= n && k <= KNN_MAX_K && C >= 1 && C <= KNN_MAX_C;
 }
 
+// The one launcher.  With 0 <= self0 < n the shortest row keeps n - 1 columns: k <= n - 1, or the radix select would look
+// for a k-th place among fewer than k candidates.
+int knn_launch(const float* S, long long ldS, int M, int n, long long self0, const long long* labels, int C, int k,
+               float inv_temp, int* idx, float* val, float* scores, int* pred, void* workspace, long long workspace_bytes,
+               contrad_stream_t stream) {
+  CONTRAD_ARG(S && labels && idx && val && scores && pred);
+  CONTRAD_ARG(knn_shape_ok(M, n, k, C) && ldS >= n);
+  CONTRAD_ARG(!(self0 >= 0 && self0 < n) || k <= n - 1);
+  const long long need = contrad_knn_select_workspace_bytes(M, n, k, C);
+  CONTRAD_ARG(workspace_bytes >= need && (need == 0 || workspace != nullptr));
+  int P = 1;
+  while (P < k) P <<= 1;
+  hipLaunchKernelGGL(knn_select_kernel, dim3(M), dim3(KNN_THREADS), 0, (hipStream_t)stream, S, ldS, n, self0, labels, C, k,
+                     P, inv_temp, idx, val, scores, pred);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" long long contrad_knn_select_workspace_bytes(int M, int n, int k, int C) {
@@ -199,14 +236,11 @@ extern "C" long long contrad_knn_select_workspace_bytes(int M, int n, int k, int
 extern "C" int contrad_knn_select(const float* S, long long ldS, int M, int n, const long long* labels, int C, int k,
                                   float inv_temp, int* idx, float* val, float* scores, int* pred, void* workspace,
                                   long long workspace_bytes, contrad_stream_t stream) {
-  CONTRAD_ARG(S && labels && idx && val && scores && pred);
-  CONTRAD_ARG(knn_shape_ok(M, n, k, C) && ldS >= n);
-  const long long need = contrad_knn_select_workspace_bytes(M, n, k, C);
-  CONTRAD_ARG(workspace_bytes >= need && (need == 0 || workspace != nullptr));
-  int P = 1;
-  while (P < k) P <<= 1;
-  hipLaunchKernelGGL(knn_select_kernel, dim3(M), dim3(KNN_THREADS), 0, (hipStream_t)stream, S, ldS, n, labels, C, k, P,
-                     inv_temp, idx, val, scores, pred);
-  CONTRAD_CHECK_LAUNCH();
-  return 0;
+  return knn_launch(S, ldS, M, n, -1, labels, C, k, inv_temp, idx, val, scores, pred, workspace, workspace_bytes, stream);
+}
+
+extern "C" int contrad_knn_select_loo(const float* S, long long ldS, int M, int n, long long self0, const long long* labels,
+                                      int C, int k, float inv_temp, int* idx, float* val, float* scores, int* pred,
+                                      void* workspace, long long workspace_bytes, contrad_stream_t stream) {
+  return knn_launch(S, ldS, M, n, self0, labels, C, k, inv_temp, idx, val, scores, pred, workspace, workspace_bytes, stream);
 }

@@ -1,4 +1,4 @@
-"""The layer under the evaluators of a frozen discriminator's penultimate features (knn.py, prdc.py, kid.py; DESIGN.md
+"""The layer under the evaluators of a frozen discriminator's penultimate features (knn.py, prdc.py, kid.py, nearest.py; DESIGN.md
 section 15): images to normalised feature rows, rows to banks, banks to similarity chunks, and the checkpoints, image
 sets and command line that the evaluators of "a real set against a fake set" share.
 

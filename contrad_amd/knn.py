@@ -5,10 +5,14 @@ eval-mode trunk forward per image, one similarity GEMM, one select-and-vote laun
 
     python test_knn.py <run>/dis.pt sndcgan --n_classes 10 --data cifar10.npz
     python test_knn.py <run>/dis.pt sndcgan --synthetic --k 200 --temp 0.1
+    python test_knn.py <run>/dis.pt sndcgan --n_classes 3 --data afhq.npz --loo     # + leave-one-out on the training split alone
 
   * features, the transposed bank and the row chunks of ``S``: contrad_amd/features.py;
   * per chunk csrc/knn.hip reads ``S`` back five times (four radix digits and the compaction) while it is still cached;
-  * ``knn_accuracy`` reads the device once, at the end.
+  * ``knn_accuracy`` reads the device once, at the end;
+  * ``loo_accuracy`` (``--loo``) classifies every image of ONE labelled set by the others: the select kernel leaves the
+    query's own column out of its own bank by index (``self0``), so a set without a test split has
+    a kNN accuracy too.
 
 ``--knn_data`` of the training scripts runs ``knn_accuracy`` at every ``--evaluate_every`` through ``KNNMonitor``, which
 follows evaluate/gan.py's ``Monitor``: a discriminator of its own, so that the training trajectory does not move by a bit.
@@ -78,21 +82,31 @@ class KNNClassifier(object):
         self.inv_temp = 1.0 / float(temp)
         self.chunk_rows = features.chunk_rows_of(self.n_pad)
 
-    def predict(self, feats, neighbours=False):
+    def predict(self, feats, neighbours=False, leave_self_out=False):
         """(pred int32 [M], scores [M, n_classes]) of the query rows ``feats`` [M, d]; with ``neighbours`` also
-        (idx int32 [M, k], val [M, k])."""
+        (idx int32 [M, k], val [M, k]).  ``leave_self_out``: ``feats`` are the bank's own rows in the bank's order (M == n)
+        and row i does not vote for itself -- column i is left out by index (csrc/knn.hip's ``self0``), k is clamped to
+        n - 1."""
         if not torch.is_tensor(feats) or not feats.is_cuda or feats.dtype != torch.float32 or feats.dim() != 2 \
                 or feats.shape[1] != self.d:
             raise RuntimeError('knn: queries must be a CUDA float32 [M, %d] matrix' % self.d)
         M, dev = feats.shape[0], feats.device
+        k = self.k
+        if leave_self_out:
+            if M != self.n:
+                raise ValueError('knn: leave_self_out takes the rows of the bank itself (%d rows, a bank of %d)' % (M, self.n))
+            if self.n < 2:
+                raise ValueError('knn: leave_self_out needs a bank of at least 2 rows')
+            k = min(k, self.n - 1)
         q = features.normalize_rows(feats) if self.normalize else feats.contiguous()
         pred = torch.empty(M, device=dev, dtype=torch.int32)
         scores = torch.empty(M, self.n_classes, device=dev)
-        idx = torch.empty(M, self.k, device=dev, dtype=torch.int32) if neighbours else None
-        val = torch.empty(M, self.k, device=dev) if neighbours else None
+        idx = torch.empty(M, k, device=dev, dtype=torch.int32) if neighbours else None
+        val = torch.empty(M, k, device=dev) if neighbours else None
         for i, Sc in features.similarity_chunks(q, self.bankT, chunk_rows=self.chunk_rows):
             m = Sc.shape[0]
-            ci, cv, cs, cp = ops.knn_select(Sc, self.n, self.labels, self.n_classes, self.k, self.inv_temp)
+            ci, cv, cs, cp = ops.knn_select(Sc, self.n, self.labels, self.n_classes, k, self.inv_temp,
+                                            self0=i if leave_self_out else -1)
             pred[i:i + m].copy_(cp)
             scores[i:i + m].copy_(cs)
             if neighbours:
@@ -128,6 +142,25 @@ def knn_accuracy(D, data, n_classes, k=200, temp=0.1, batch=500):
     pred, _ = clf.predict(features.extract_features(D, data['x_test'], batch))
     hits = (pred.long() == data['y_test']).sum()
     return {'acc@1': 100.0 * int(hits.item()) / n_test, 'n_test': n_test}       # the one device-to-host read
+
+
+def loo_accuracy(D, x_u8, y, n_classes, k=200, temp=0.1, batch=500):
+    """Leave-one-out top-1 accuracy (percent) of the weighted kNN vote on ONE labelled set (no test split, as AFHQ has none):
+    every image is classified by the others, its own column left out of its row by index; k is clamped to n - 1.  ``x_u8``:
+    device-resident uint8 [n, H, W, 3]; ``y``: its labels (host array, range-checked here, or a CUDA tensor).  ``D``: on the
+    GPU, in eval mode."""
+    features.check_u8(x_u8, 'given', 'knn.loo_accuracy')
+    n, dev = x_u8.shape[0], x_u8.device
+    if n < 2:
+        raise ValueError('knn.loo_accuracy: %d image: leave-one-out needs at least 2' % n)
+    if not torch.is_tensor(y):
+        check_labels(y, n_classes, 'labels')
+        y = torch.from_numpy(np.asarray(y).astype(np.int64)).to(dev)
+    feats = features.extract_features(D, x_u8, batch)
+    clf = KNNClassifier(feats, y, n_classes, k=k, temp=temp, normalize=False)
+    pred, _ = clf.predict(feats, leave_self_out=True)
+    hits = (pred.long() == clf.labels).sum()
+    return {'acc@1': 100.0 * int(hits.item()) / n, 'n': n, 'k': min(clf.k, n - 1)}      # the one device-to-host read
 
 
 class KNNMonitor(object):
@@ -186,6 +219,10 @@ def parse_args(argv=None):
     parser.add_argument('--temp', default=0.1, type=float, help='vote temperature (default: 0.1)')
     parser.add_argument('--batch_size', default=500, type=int, help='images per trunk forward (default: 500)')
     parser.add_argument('--seed', default=None, type=int, help='file-name tag and seed of --synthetic (default: drawn)')
+    parser.add_argument('--loo', action='store_true',
+                        help='also the leave-one-out accuracy on the training split alone (every image classified by the '
+                             'others, k clamped to n - 1): the probe for a labelled set without a test split; adds the key '
+                             '"loo" to the json')
     return parser.parse_args(argv)
 
 
@@ -209,6 +246,11 @@ def main(argv=None):
     out.update({'k': min(P.k, len(data['y_train'])), 'temp': P.temp, 'n_train': int(len(data['y_train']))})
     print('kNN (k %d, T %g): [Acc@1 %.3f] on %d test images, bank of %d' % (
         out['k'], P.temp, out['acc@1'], out['n_test'], out['n_train']), flush=True)
+    if P.loo:
+        out['loo'] = loo_accuracy(D, torch.from_numpy(np.ascontiguousarray(data['x_train'])).to(dev), data['y_train'], P.n_classes,
+                                  P.k, P.temp, P.batch_size)
+        print('kNN leave-one-out (k %d, T %g): [Acc@1 %.3f] on the %d training images' % (
+            out['loo']['k'], P.temp, out['loo']['acc@1'], out['loo']['n']), flush=True)
     path = os.path.join(Path(P.model_path).parent, 'knn_%d.json' % seed)
     with open(path, 'w') as f:
         json.dump(out, f)

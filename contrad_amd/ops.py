@@ -1167,14 +1167,18 @@ KNN_MAX_K = 1024
 KNN_MAX_CLASSES = 1024
 
 
-def knn_select(S, n, labels, n_classes, k, inv_temp):
+def knn_select(S, n, labels, n_classes, k, inv_temp, self0=-1):
     """Per row of the similarity matrix ``S`` (M, ldS >= n; columns [0, n) are read) the k nearest of the n bank
-    columns and their weighted class vote.  ``labels``: int64 CUDA vector of the n bank labels.  Returns
-    (idx int32 (M, k), val (M, k), scores (M, n_classes), pred int32 (M,)): contrad_knn_select's contract
-    (include/contrad_hip.h)."""
+    columns and their weighted class vote.  ``labels``: int64 CUDA vector of the n bank labels.  ``self0``: column
+    ``self0 + i`` is left out of row i when it lies in [0, n) (``self0 < 0``: nothing is left out), by index.  Returns
+    (idx int32 (M, k), val (M, k), scores (M, n_classes), pred int32 (M,)): contrad_knn_select's contract, with ``self0``
+    contrad_knn_select_loo's (include/contrad_hip.h)."""
     M, ldS, n = _chk_S(S, n)
-    C, k = int(n_classes), int(k)
-    if not 1 <= k <= min(n, KNN_MAX_K):
+    C, k, self0 = int(n_classes), int(k), int(self0)
+    remain = n - 1 if 0 <= self0 < n else n
+    if not 1 <= k <= min(remain, KNN_MAX_K):
+        if remain != n:
+            raise RuntimeError('contrad_hip: k = %d outside [1, %d] (n = %d, self0 = %d)' % (k, min(remain, KNN_MAX_K), n, self0))
         raise RuntimeError('contrad_hip: k = %d outside [1, min(n, %d)] with n = %d' % (k, KNN_MAX_K, n))
     if not 1 <= C <= KNN_MAX_CLASSES:
         raise RuntimeError('contrad_hip: n_classes = %d outside [1, %d]' % (C, KNN_MAX_CLASSES))
@@ -1190,8 +1194,8 @@ def knn_select(S, n, labels, n_classes, k, inv_temp):
     if nbytes < 0:
         raise RuntimeError('contrad_hip: bad kNN shape (%d)' % nbytes)
     ws = _workspace(nbytes, dev) if nbytes > 0 else None
-    lib().call('contrad_knn_select', _p(S), ctypes.c_longlong(ldS), M, n, _p(labels), C, k, float(inv_temp), _as_int(idx),
-               _p(val), _p(scores), _as_int(pred), _p(ws), ctypes.c_longlong(nbytes), _stream())
+    lib().call('contrad_knn_select_loo', _p(S), ctypes.c_longlong(ldS), M, n, ctypes.c_longlong(self0), _p(labels), C, k,
+               float(inv_temp), _as_int(idx), _p(val), _p(scores), _as_int(pred), _p(ws), ctypes.c_longlong(nbytes), _stream())
     return idx, val, scores, pred
 
 

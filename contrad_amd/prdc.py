@@ -37,6 +37,7 @@ import torch
 
 from . import features, ops
 from . import kid as kid_mod
+from . import nearest
 from .evaluate.gan import eval_seed_of, own_network, preserved_rng
 from .models.gan import get_architecture
 
@@ -153,10 +154,13 @@ class PRDCMonitor(object):
     up to that step back from its csv (``best_in_csv``).  ``kid`` (``--prdc_kid``): each evaluation also appends
     ``step,kid,kid_std`` to ``kid_<eval_seed>.csv`` (contrad_amd/kid.py); ``best`` may then be ``'kid'``, which is minimised.  ``kid_kernel``
     (``--prdc_kid_kernel``): 'rq' computes the rational-quadratic distance instead, into ``kid_rq_<eval_seed>.csv`` (never into
-    ``kid_<eval_seed>.csv``: the two are different numbers), which ``best='kid'`` then tracks and reads back."""
+    ``kid_<eval_seed>.csv``: the two are different numbers), which ``best='kid'`` then tracks and reads back.  ``auth``
+    (``--prdc_auth``): the real features are extracted once for both states -- ``real_state_of`` and ``nearest.real_state_of``
+    on the same bank -- and each evaluation also appends ``step,authenticity,nearest_mean`` to ``auth_<eval_seed>.csv``
+    (contrad_amd/nearest.py: the memorisation check); it records only and is no ``best``."""
 
     def __init__(self, logdir, architecture, image_size, device, seed, data_path, encoder_path, encoder_arch=None, k=5,
-                 n_fake=10000, batch=500, best=None, resumed_step=0, P=None, kid=False, kid_kernel='poly3'):
+                 n_fake=10000, batch=500, best=None, resumed_step=0, P=None, kid=False, kid_kernel='poly3', auth=False):
         real = features.load_images(data_path, 'x_train')
         if tuple(real.shape[1:]) != tuple(image_size):
             raise ValueError('%s: x_train holds %s images, the generator makes %s' % (data_path, tuple(real.shape[1:]), tuple(image_size)))
@@ -170,19 +174,31 @@ class PRDCMonitor(object):
             raise ValueError('--prdc_kid_kernel needs --prdc_kid')
         if kid:
             kid_mod.check_sizes(len(real), n_fake)
+        if auth and len(real) < 2:
+            raise ValueError('--prdc_auth needs at least 2 real images (%d)' % len(real))
         self.k, self.n_fake, self.batch, self.device, self.metric = int(k), int(n_fake), int(batch), device, best
         self.eval_seed = eval_seed_of(seed)
         self.path = os.path.join(logdir, 'prdc_%d.csv' % self.eval_seed)
         self.kid_kernel = kid_kernel
         self.kid_path = os.path.join(logdir, kid_csv_name(kid_kernel) % self.eval_seed) if kid else None
+        self.auth_path = os.path.join(logdir, 'auth_%d.csv' % self.eval_seed) if auth else None
+        self.auth_state = None
         self.n_real = len(real)
         self.G = own_network('G', architecture, image_size, device, P)
         with preserved_rng(device):                                        # the constructors draw the initial weights
             E = get_architecture(encoder_arch or architecture, image_size)[1]
         self.E = features.load_frozen(E, encoder_path, device)
         with torch.no_grad(), preserved_rng(device):
-            self.real_state = real_state_of_images(self.E, torch.from_numpy(real).to(device), self.k, self.batch)
-        self.files = [(self.path, CSV_HEAD, csv_line)] + ([(self.kid_path, kid_mod.CSV_HEAD, kid_mod.csv_line)] if kid else [])
+            if not auth:
+                self.real_state = real_state_of_images(self.E, torch.from_numpy(real).to(device), self.k, self.batch)
+            else:                                                          # one extraction, one bank, both states
+                real_u8 = torch.from_numpy(real).to(device)
+                features.check_u8(real_u8, 'real', 'prdc')
+                feats = features.extract_features(self.E, real_u8, self.batch)
+                self.real_state = real_state_of(feats, self.k, normalize=False)
+                self.auth_state = nearest.real_state_of(feats, normalize=False, bankT=self.real_state[0])
+        self.files = [(self.path, CSV_HEAD, csv_line)] + ([(self.kid_path, kid_mod.CSV_HEAD, kid_mod.csv_line)] if kid else []) + \
+            ([(self.auth_path, nearest.CSV_HEAD, nearest.csv_line)] if auth else [])       # (after the files --prdc_best tracks)
         self.best = None
         for j, (path, head, _) in enumerate(self.files):
             if not os.path.exists(path):                                   # (a resumed run appends to its file)
@@ -208,6 +224,9 @@ class PRDCMonitor(object):
                 d = kid_mod.kid(None, feats, seed=self.eval_seed, normalize=False, real_bank=(self.real_state[0], self.n_real),
                                 kernel=self.kid_kernel)
                 out['kid'], out['kid_std'] = d['kid'], d['kid_std']
+            if self.auth_path is not None:                                 # the same fake features, the same real bank
+                a = nearest.authenticity(None, feats, real_state=self.auth_state, normalize=False)
+                out['authenticity'], out['nearest_mean'], out['real_nearest_mean'] = a['authenticity'], a['nearest_mean'], a['real_nearest_mean']
         lines = []
         for path, _, line_of in self.files:
             lines.append(line_of(step, out))
@@ -229,11 +248,14 @@ class PRDCMonitor(object):
         if 'kid' in out:
             lines.append('[Steps %7d] [%s %.6f +- %.6f]%s' % (step, 'kid' if self.kid_kernel == 'poly3' else 'kid_' + self.kid_kernel,
                                                               out['kid'], out['kid_std'], mark(self.metric == 'kid')))
+        if 'authenticity' in out:
+            lines.append('[Steps %7d] [authenticity %.4f] [nearest %.4f, real to real %.4f]' % (
+                step, out['authenticity'], out['nearest_mean'], out['real_nearest_mean']))
         return lines
 
 
 HOOK_DEFAULTS = {'prdc_data': None, 'prdc_encoder': None, 'prdc_encoder_arch': None, 'prdc_k': 5, 'prdc_n': 10000, 'prdc_best': None,
-                 'prdc_kid': False, 'prdc_kid_kernel': 'poly3'}
+                 'prdc_kid': False, 'prdc_kid_kernel': 'poly3', 'prdc_auth': False}
 
 
 def kid_csv_name(kid_kernel):
@@ -269,6 +291,12 @@ def add_hook_arguments(parser):
                         help='with --prdc_kid: poly3 (default), or rq: the rational-quadratic mixture (alpha = 1/2, 1, 2; a '
                              'characteristic kernel) is computed instead and appended to kid_rq_<seed>.csv, never into '
                              'kid_<seed>.csv; --prdc_best kid then tracks that file')
+    parser.add_argument('--prdc_auth', action='store_true', **off,
+                        help='with --prdc_data: every evaluation also appends step,authenticity,nearest_mean to auth_<seed>.csv: '
+                             'the memorisation check (contrad_amd/nearest.py), the share of the same fakes that is NOT closer to '
+                             'its nearest real image than that image is to its own nearest other real image, and the mean '
+                             'similarity of a fake to its nearest real.  It records only (no --prdc_best choice: not a quantity '
+                             'to maximise); read it against test_nearest.py --holdout, not against 1')
 
 
 def hook_options(P):

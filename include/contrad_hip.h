@@ -741,6 +741,20 @@ long long contrad_knn_select_workspace_bytes(int M, int n, int k, int C);
 int contrad_knn_select(const float* S, long long ldS, int M, int n, const long long* labels, int C, int k,
                        float inv_temp, int* idx, float* val, float* scores, int* pred, void* workspace,
                        long long workspace_bytes, contrad_stream_t stream);
+/* contrad_knn_select with the query's own column left out: row i of S[M][ldS] is row self0 + i of the bank it is compared
+ * with (contrad_prdc_kth's convention: a row chunk passes its first global row) and leaves column e = self0 + i out when
+ * self0 >= 0 and e < n; otherwise (self0 < 0, or e >= n) nothing is left out of that row, and self0 < 0 is
+ * contrad_knn_select bit for bit.  Exclusion is BY INDEX, whatever the column holds: a NaN or a +inf there is never seen
+ * and never written, while a duplicate of the query elsewhere in the bank is a neighbour like any other.  The neighbour
+ * order among the columns that remain, val, scores and pred are contrad_knn_select's.  Limits: those of
+ * contrad_knn_select, and k <= n - 1 when 0 <= self0 < n (the columns that remain in the shortest row; so n >= 2 there);
+ * -EINVAL (before any GPU call) on a null pointer, a violated limit or a workspace smaller than
+ * contrad_knn_select_workspace_bytes.  There is no label-free form: a caller without labels passes n zeros, C = 1 and
+ * inv_temp = 1.  One launch of the same kernel; no float atomics; every output element is written once; two calls are
+ * bitwise equal. */
+int contrad_knn_select_loo(const float* S, long long ldS, int M, int n, long long self0, const long long* labels, int C,
+                           int k, float inv_temp, int* idx, float* val, float* scores, int* pred, void* workspace,
+                           long long workspace_bytes, contrad_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Precision / recall / density / coverage on a similarity matrix (csrc/prdc.hip): k-th largest per row, hit counts.
