@@ -3,24 +3,23 @@
 //   kid_sums    sum over a block of S of k(s) with the column self0 + row left out of every row by index; k is chosen
 //               by the run-time `kind` (wave-uniform): 0, (gamma * s + coef0)^3; 1, the rational-quadratic mixture
 //               sum over alpha in {1/2, 1, 2} of (1 + u / (2 alpha))^-alpha at u = max(2 - 2 s, 0), the squared distance
-//               of two unit vectors (IEEE sqrt and division only).  Every term is formed and added in float64.  A workgroup takes 4 * rpw rows x 256 columns
-//               (rpw = 32, or 4 where that would leave fewer than 1024 workgroups: a 1000 x 1000 block is 252 of them
-//               instead of 32); a wave takes every fourth row of the tile, a lane four consecutive columns (one 16-byte
-//               load where the address allows), four rows in flight: prdc_count_kernel's shape.  A lane sums its terms
-//               in row order, the wave by a butterfly, the four waves in wave order: one float64 partial per workgroup
-//               into the workspace.
+//               of two unit vectors (IEEE sqrt and division only).  Every term is formed and added in float64.  The row-tile
+//               walk is csrc/simrow.h's (shared with prdc.hip), on 4 * rpw rows x 256 columns: rpw = 32, or 4 where
+//               that would leave fewer than 1024 workgroups (a 1000 x 1000 block is 252 of them instead of 32).  A
+//               lane sums its terms in row order, the wave by a butterfly, the four waves in wave order: one float64
+//               partial per workgroup into the workspace.
 //   kid_final   one workgroup adds the partials in a fixed order (thread t the partials t, t + 256, ...; then a tree
 //               in LDS) and one thread adds the old value last when `accumulate` is set.
 // No atomics: out[0] depends on no order of arrival, two calls are bitwise equal.
 #include "../../include/contrad_hip.h"
-#include "common.h"
+#include "simrow.h"
 
 #include <math.h>
 
 namespace {
 
-constexpr int KID_THREADS = 256;
-constexpr int KID_COLS = 256;                       // columns of a tile: 4 per lane
+constexpr int KID_THREADS = simrow::THREADS;
+constexpr int KID_COLS = simrow::COLS;
 constexpr int KID_RPW_MAX = 32;                     // rows per wave of a tile
 constexpr int KID_RPW_MIN = 4;
 constexpr long long KID_ENOUGH_BLOCKS = 1024;
@@ -60,23 +59,11 @@ __global__ __launch_bounds__(KID_THREADS) void kid_sums_kernel(const float* __re
   const long long c0 = (long long)ct * KID_COLS + 4 * lane;
   const long long r0 = (long long)rt * 4 * rpw + w;   // this wave's rows: r0, r0 + 4, ...
   const int rows = r0 < M ? (int)min((long long)rpw, (M - r0 + 3) >> 2) : 0;
-  const bool whole = vec_ok && c0 + 3 < n;
 
   double acc = 0.0;
-  for (int t0 = 0; t0 < rows; t0 += 4) {               // four rows in flight; a round's missing rows re-read the last one
+  for (int t0 = 0; t0 < rows; t0 += 4) {
     float v[4][4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long long i = r0 + 4 * min(t0 + u, rows - 1);
-      const float* __restrict__ row = S + i * ldS;
-      if (whole) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(row + c0);
-        v[u][0] = x.x; v[u][1] = x.y; v[u][2] = x.z; v[u][3] = x.w;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[u][j] = c0 + j < n ? row[c0 + j] : 0.f;
-      }
-    }
+    simrow::load_tile(v, S, ldS, r0, t0, rows, c0, n, vec_ok, 0.f, [](int, long long) {});
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const bool live = t0 + u < rows;                 // (uniform)

@@ -2,42 +2,32 @@
 // vote and the predicted class, in ONE launch, one 256-thread workgroup per row.  No float atomics; every output
 // element is written once and every float sum has a fixed order, so two calls are bitwise equal.
 //
-//   1. keys      a float becomes a 32-bit key whose unsigned order is the contract's order: NaN -> 0 (below every
-//                number), -0.0 -> +0.0, then the usual sign flip.  A neighbour is ranked by (key descending, column
-//                ascending), i.e. by the 64-bit word (key << 32 | ~column) descending.
-//   2. select    the k-th largest key by radix select, four 8-bit digits from the top: per digit an LDS histogram (one
-//                per wave, integer adds: the counts do not depend on the order of arrival) of the columns that match
-//                the digits fixed so far, a suffix sum over the 256 bins, the bin that holds the k-th place.
-//   3. compact   one ordered pass over the row (a thread takes 4 consecutive columns, a packed wave scan numbers them):
-//                every column above the threshold key and, in column order, the first k - count columns equal to it.
-//   4. sort      bitonic sort of the (at most 1024, padded to a power of two) 64-bit words in LDS.
-//   5. vote      idx / val out (val re-read from S: the very floats); labels and expf(val * inv_temp) staged in LDS;
-//                thread c adds the weights of class c in rank order; the block's argmax under the same key order.
+// The key order (NaN lowest, -0.0 == +0.0, ties by ascending column), the radix select of the k-th largest key and the
+// round scan of the ordered pass are csrc/simrow.h's, shared with prdc.hip.  This file owns what follows the threshold key:
+//
+//   compact   a neighbour is ranked by the 64-bit word (key << 32 | ~column) descending.  One ordered pass over the row
+//             (a thread takes 4 consecutive columns, one scan numbers both tallies, packed into one word): every column
+//             above the threshold key and, in column order, the first k - count columns equal to it.
+//   sort      bitonic sort of the (at most 1024, padded to a power of two) 64-bit words in LDS.
+//   vote      idx / val out (val re-read from S: the very floats); labels and expf(val * inv_temp) staged in LDS;
+//             thread c adds the weights of class c in rank order; the block's argmax under the same key order.
 //
 // Leave-self-out (contrad_knn_select_loo): with self0 >= 0 row q of the launch is row self0 + q of the bank it is compared
 // with and leaves that column out BY INDEX (contrad_prdc_kth's convention; a duplicate elsewhere in the bank is a neighbour
 // like any other).  A run-time, block-uniform argument of the one kernel: the column takes part in no histogram and in
-// neither tally of the compaction, so steps 2 to 5 see a row of n - 1 columns.  self0 < 0 is the kernel as it was.
+// neither tally of the compaction, so every step sees a row of n - 1 columns.  self0 < 0 is the kernel as it was.
 //
 // The row is read five times (four digits and the compaction) and never staged: the caller hands over chunks of S small
 // enough to be served from cache (contrad_amd/knn.py), and at n = 50 000 a row is 200 KB, beyond the LDS of a CU.
 #include "../../include/contrad_hip.h"
-#include "common.h"
+#include "simrow.h"
 #include <type_traits>
 
 namespace {
 
-constexpr int KNN_THREADS = 256;
+constexpr int KNN_THREADS = simrow::THREADS;
 constexpr int KNN_MAX_K = 1024;
 constexpr int KNN_MAX_C = 1024;
-constexpr unsigned KNN_CHUNK = 4 * KNN_THREADS;     // columns per round of the compaction
-
-__device__ __forceinline__ unsigned knn_key(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;   // NaN: below every number (the key of -inf is 0x007fffff)
-  if (u == 0x80000000u) u = 0u;                     // -0.0 == +0.0
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 __device__ __forceinline__ unsigned long long knn_word(unsigned key, unsigned col) {
   return ((unsigned long long)key << 32) | (unsigned long long)(0xffffffffu - col);
@@ -60,78 +50,36 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(const float* __
   const float* __restrict__ row = S + q * ldS;
   const unsigned un = (unsigned)n;
   // Leave-self-out (block-uniform): row q of the launch is global row self0 + q and never sees column `ex` of its own bank,
-  // whatever that column holds.  Steps 2 and 3 are written once and compiled twice: LOO = false is the row as it ever was,
-  // without a test per element; LOO = true skips `ex` in every histogram and in both tallies of the compaction.
+  // whatever that column holds.  Select and compaction are written once and compiled twice: LOO = false is the row as it
+  // ever was, without a test per element; LOO = true skips `ex` in every histogram and in both tallies of the compaction.
   const bool loo_row = self0 >= 0 && self0 + q < (long long)n;
   const unsigned ex = loo_row ? (unsigned)(self0 + q) : 0xffffffffu;
   unsigned T = 0u, cgt = 0u, krem = (unsigned)k;
 
   auto select_and_compact = [&](auto loo) {
     constexpr bool LOO = decltype(loo)::value;
-    // ---- 2. the k-th largest key: `prefix` after four digits; `krem` of the columns equal to it are neighbours ----
-    unsigned prefix = 0u;
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = 24 - 8 * pass;
-      const unsigned himask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
-      for (int i = tid; i < 4 * 256; i += KNN_THREADS) (&hist[0][0])[i] = 0u;
-      __syncthreads();
-      for (unsigned j = tid; j < un; j += KNN_THREADS) {
-        const unsigned key = knn_key(row[j]);
-        if (!(LOO && j == ex) && (key & himask) == prefix) atomicAdd(&hist[w][(key >> shift) & 255u], 1u);
-      }
-      __syncthreads();
-      const unsigned cnt = hist[0][tid] + hist[1][tid] + hist[2][tid] + hist[3][tid];   // thread t owns bin t
-      unsigned suf = cnt;                                                               // sum over the bins >= t of this wave
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_down(suf, o, 64);
-        if (lane + o < 64) suf += t;
-      }
-      if (lane == 0) wtot[0][w] = suf;
-      __syncthreads();
-      unsigned above = suf - cnt;                                                       // columns in higher bins
-      for (int ww = w + 1; ww < 4; ++ww) above += wtot[0][ww];
-      if (above < krem && krem <= above + cnt) {                                        // exactly one bin
-        sel[0] = (unsigned)tid;
-        sel[1] = krem - above;
-      }
-      __syncthreads();
-      prefix |= sel[0] << shift;
-      krem = sel[1];
-    }
-    T = prefix;
+    // ---- the k-th largest key T; `krem` of the columns equal to it are neighbours ----
+    T = simrow::kth_key<LOO, 4, 1>(row, un, ex, hist, wtot, sel, krem);
     cgt = (unsigned)k - krem;                                                           // cgt columns have a key above T
 
-    // ---- 3. ordered compaction: words[0, cgt) keys above T, words[cgt, k) the first krem columns equal to T ----
+    // ---- ordered compaction: words[0, cgt) keys above T, words[cgt, k) the first krem columns equal to T ----
     for (int r = k + tid; r < P; r += KNN_THREADS) words[r] = 0ull;                     // padding sorts last
     unsigned base_g = 0u, base_e = 0u;
     int buf = 0;
-    for (unsigned c0 = 0u; c0 < un; c0 += KNN_CHUNK, buf ^= 1) {
+    for (unsigned c0 = 0u; c0 < un; c0 += simrow::CHUNK, buf ^= 1) {
       const unsigned j0 = c0 + 4u * tid;
       unsigned key4[4];
       unsigned g = 0u, e = 0u;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const bool in = j0 + i < un && !(LOO && j0 + i == ex);   // the column left out is in neither tally
-        key4[i] = in ? knn_key(row[j0 + i]) : 0u;
+        key4[i] = in ? simrow::key(row[j0 + i]) : 0u;
         g += (in && key4[i] > T) ? 1u : 0u;
         e += (in && key4[i] == T) ? 1u : 0u;
       }
       const unsigned p = g | (e << 16);                  // both counts <= 1024 per round: the two scans share a word
-      unsigned inc = p;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-      }
-      if (lane == 63) wtot[buf][w] = inc;
-      __syncthreads();
-      unsigned off = inc - p, tot = 0u;
-      for (int ww = 0; ww < 4; ++ww) {
-        const unsigned t = wtot[buf][ww];
-        if (ww < w) off += t;
-        tot += t;
-      }
+      unsigned tot;
+      const unsigned off = simrow::round_scan(p, wtot[buf], tot);
       unsigned pg = base_g + (off & 0xffffu), pe = base_e + (off >> 16);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -152,7 +100,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(const float* __
   if (loo_row) select_and_compact(std::true_type{});
   else select_and_compact(std::false_type{});
 
-  // ---- 4. bitonic sort, descending ----
+  // ---- bitonic sort, descending ----
   for (int size = 2; size <= P; size <<= 1) {
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
       __syncthreads();
@@ -169,7 +117,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(const float* __
   }
   __syncthreads();
 
-  // ---- 5. outputs and the vote ----
+  // ---- outputs and the vote ----
   for (int r = tid; r < k; r += KNN_THREADS) {
     unsigned j = 0xffffffffu - (unsigned)(words[r] & 0xffffffffull);
     j = j < un ? j : un - 1u;                          // (always j < n; keeps every read inside the row regardless)
@@ -187,7 +135,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(const float* __
     for (int r = 0; r < k; ++r)
       if (lab_s[r] == c) s += w_s[r];
     scores[q * C + c] = s;
-    const unsigned long long cand = knn_word(knn_key(s), (unsigned)c);
+    const unsigned long long cand = knn_word(simrow::key(s), (unsigned)c);
     mine = cand > mine ? cand : mine;
   }
 #pragma unroll

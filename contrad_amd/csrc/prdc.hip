@@ -1,35 +1,25 @@
 // Precision / recall / density / coverage on a similarity matrix (gfx950): the two selection kernels of
 // contrad_amd/prdc.py.  Integer counts only: no float atomics, every sum is independent of the order of arrival, so two
-// calls are bitwise equal.
+// calls are bitwise equal.  The key order, the radix select, the round scan and the row-tile walk are csrc/simrow.h's
+// (shared with knn.hip and kid.hip); this file owns:
 //
-//   prdc_kth     per row the k-th largest value with the column self0 + row left out: csrc/knn.hip's radix select (keys
-//                in the contract's order, four 8-bit digits from the top, one LDS histogram per wave, a suffix sum over
-//                the 256 bins) without its compaction, sort and vote, so k is bound by the row only.  A key names its
-//                float except for the two keys that several bit patterns share (zero: -0.0 / +0.0; NaN): there one more
-//                ordered pass finds the column that holds the k-th place under "value descending, column ascending"
-//                and its float is written.  One 256-thread workgroup per row, the row read once per digit.
-//   prdc_count   one pass over S against a threshold per column (hit_c) and / or per row (hit_r).  A workgroup takes
-//                128 rows x 256 columns; a wave takes every fourth row of the tile, a lane four consecutive columns (one
-//                16-byte load where the address allows).  Row counts: ballots summed per wave, one lane per row keeps
-//                the count, one global add per row and tile.  Column counts: per-lane registers over the wave's rows, the
-//                four waves summed in LDS, one global add per column and tile.  Zero sums are not sent.
+//   prdc_kth     per row the k-th largest value with the column self0 + row left out: the radix select alone, so k is
+//                bound by the row only.  A key names its float except for the two keys that several bit patterns share
+//                (zero: -0.0 / +0.0; NaN): there one more ordered pass finds the column that holds the k-th place under
+//                "value descending, column ascending" and its float is written.  One 256-thread workgroup per row.
+//   prdc_count   one pass over S against a threshold per column (hit_c) and / or per row (hit_r), on row tiles of 128
+//                rows x 256 columns.  Row counts: ballots summed per wave, one lane per row keeps the count, one global
+//                add per row and tile.  Column counts: per-lane registers over the wave's rows, the four waves summed in
+//                LDS, one global add per column and tile.  Zero sums are not sent.
 #include "../../include/contrad_hip.h"
-#include "common.h"
+#include "simrow.h"
 
 namespace {
 
-constexpr int PRDC_THREADS = 256;
-constexpr unsigned PRDC_CHUNK = 4 * PRDC_THREADS;   // columns per round of the ordered pass
-constexpr int PRDC_COLS = 256;                      // columns of a count tile: 4 per lane
+constexpr int PRDC_THREADS = simrow::THREADS;
+constexpr int PRDC_COLS = simrow::COLS;
 constexpr int PRDC_RPW = 32;                        // rows per wave of a count tile
 constexpr int PRDC_ROWS = 4 * PRDC_RPW;
-
-__device__ __forceinline__ unsigned prdc_key(float f) {            // knn_key: NaN -> 0, -0.0 -> +0.0, sign flip
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 __global__ __launch_bounds__(PRDC_THREADS) void prdc_kth_kernel(const float* __restrict__ S, long long ldS, int n, int k,
                                                                 long long self0, float* __restrict__ thr) {
@@ -43,39 +33,9 @@ __global__ __launch_bounds__(PRDC_THREADS) void prdc_kth_kernel(const float* __r
   const long long self = self0 >= 0 ? self0 + q : -1;
   const unsigned excl = (self >= 0 && self < (long long)n) ? (unsigned)self : 0xffffffffu;      // (n < 2^31: no column)
 
-  // ---- the k-th largest key: `prefix` after four digits; it is the `krem`-th of the columns equal to it ----
-  unsigned prefix = 0u, krem = (unsigned)k;
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 24 - 8 * pass;
-    const unsigned himask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
-    for (int i = tid; i < 4 * 256; i += PRDC_THREADS) (&hist[0][0])[i] = 0u;
-    __syncthreads();
-#pragma unroll 4
-    for (unsigned j = tid; j < un; j += PRDC_THREADS) {
-      const unsigned key = prdc_key(row[j]);
-      if (j != excl && (key & himask) == prefix) atomicAdd(&hist[w][(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    const unsigned cnt = hist[0][tid] + hist[1][tid] + hist[2][tid] + hist[3][tid];   // thread t owns bin t
-    unsigned suf = cnt;                                                               // sum over the bins >= t of this wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_down(suf, o, 64);
-      if (lane + o < 64) suf += t;
-    }
-    if (lane == 0) wtot[0][w] = suf;
-    __syncthreads();
-    unsigned above = suf - cnt;                                                       // columns in higher bins
-    for (int ww = w + 1; ww < 4; ++ww) above += wtot[0][ww];
-    if (above < krem && krem <= above + cnt) {                                        // exactly one bin
-      sel[0] = (unsigned)tid;
-      sel[1] = krem - above;
-    }
-    __syncthreads();
-    prefix |= sel[0] << shift;
-    krem = sel[1];
-  }
-  const unsigned T = prefix;
+  // ---- the k-th largest key T; the k-th place is the `krem`-th of the columns equal to it ----
+  unsigned krem = (unsigned)k;
+  const unsigned T = simrow::kth_key<true, 1, 4>(row, un, excl, hist, wtot, sel, krem);
 
   if (T != 0u && T != 0x80000000u) {                   // one bit pattern has this key: the float itself
     if (tid == 0) thr[q] = __uint_as_float((T & 0x80000000u) ? (T & 0x7fffffffu) : ~T);
@@ -84,31 +44,19 @@ __global__ __launch_bounds__(PRDC_THREADS) void prdc_kth_kernel(const float* __r
   // ---- zero or NaN: the krem-th column equal to T in column order holds the k-th place ----
   unsigned base = 0u;
   int buf = 0;
-  for (unsigned c0 = 0u; c0 < un; c0 += PRDC_CHUNK, buf ^= 1) {
+  for (unsigned c0 = 0u; c0 < un; c0 += simrow::CHUNK, buf ^= 1) {
     const unsigned j0 = c0 + 4u * tid;
     unsigned e = 0u, mask = 0u;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const unsigned j = j0 + i;
-      if (j < un && j != excl && prdc_key(row[j]) == T) {
+      if (j < un && j != excl && simrow::key(row[j]) == T) {
         ++e;
         mask |= 1u << i;
       }
     }
-    unsigned inc = e;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wtot[buf][w] = inc;
-    __syncthreads();
-    unsigned before = base + inc - e, tot = 0u;
-    for (int ww = 0; ww < 4; ++ww) {
-      const unsigned t = wtot[buf][ww];
-      if (ww < w) before += t;
-      tot += t;
-    }
+    unsigned tot;
+    const unsigned before = base + simrow::round_scan(e, wtot[buf], tot);
     if (before < krem && krem <= before + e) {         // exactly one thread of one round
       unsigned need = krem - before;
 #pragma unroll
@@ -133,27 +81,15 @@ __global__ __launch_bounds__(PRDC_THREADS) void prdc_count_kernel(const float* _
   const int r0 = rt * PRDC_ROWS + w;                   // this wave's rows: r0, r0 + 4, ...
   const int rows = r0 < M ? min(PRDC_RPW, (M - r0 + 3) >> 2) : 0;
   const float nanf_ = __uint_as_float(0x7fc00000u);    // a column outside [0, n) hits nothing
-  const bool whole = vec_ok && c0 + 3 < n;
 
   float tc[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) tc[i] = (HC && c0 + i < n) ? thr_col[c0 + i] : nanf_;
   int cc[4] = {0, 0, 0, 0}, cr[4] = {0, 0, 0, 0}, mine = 0;
-  for (int t0 = 0; t0 < rows; t0 += 4) {               // four rows in flight; a round's missing rows re-read the last one
+  for (int t0 = 0; t0 < rows; t0 += 4) {
     float v[4][4], tr[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long long i = r0 + 4 * min(t0 + u, rows - 1);
-      const float* __restrict__ row = S + i * ldS;
-      if (whole) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(row + c0);
-        v[u][0] = x.x; v[u][1] = x.y; v[u][2] = x.z; v[u][3] = x.w;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[u][j] = c0 + j < n ? row[c0 + j] : nanf_;
-      }
-      tr[u] = HR ? thr_row[i] : nanf_;
-    }
+    simrow::load_tile(v, S, ldS, r0, t0, rows, c0, n, vec_ok, nanf_,
+                      [&](int u, long long i) __attribute__((always_inline)) { tr[u] = HR ? thr_row[i] : nanf_; });
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const bool live = t0 + u < rows;                 // (uniform)

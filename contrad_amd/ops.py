@@ -1162,6 +1162,17 @@ def _as_int(t):
     return ctypes.cast(_p(t), ctypes.POINTER(ctypes.c_int))                    # (the header's int* maps to a typed pointer)
 
 
+def _chk_k(k, n, self0, limit):
+    """1 <= k <= the shortest row of the launch (n - 1 columns where ``self0`` leaves one out) and the kernel's own
+    ``limit`` on k (None: the row alone)."""
+    remain = n - 1 if 0 <= self0 < n else n
+    top = remain if limit is None else min(remain, limit)
+    if not 1 <= k <= top:
+        if limit is not None and remain == n:
+            raise RuntimeError('contrad_hip: k = %d outside [1, min(n, %d)] with n = %d' % (k, limit, n))
+        raise RuntimeError('contrad_hip: k = %d outside [1, %d] (n = %d, self0 = %d)' % (k, top, n, self0))
+
+
 # ---- weighted kNN vote (csrc/knn.hip) ----
 KNN_MAX_K = 1024
 KNN_MAX_CLASSES = 1024
@@ -1175,11 +1186,7 @@ def knn_select(S, n, labels, n_classes, k, inv_temp, self0=-1):
     contrad_knn_select_loo's (include/contrad_hip.h)."""
     M, ldS, n = _chk_S(S, n)
     C, k, self0 = int(n_classes), int(k), int(self0)
-    remain = n - 1 if 0 <= self0 < n else n
-    if not 1 <= k <= min(remain, KNN_MAX_K):
-        if remain != n:
-            raise RuntimeError('contrad_hip: k = %d outside [1, %d] (n = %d, self0 = %d)' % (k, min(remain, KNN_MAX_K), n, self0))
-        raise RuntimeError('contrad_hip: k = %d outside [1, min(n, %d)] with n = %d' % (k, KNN_MAX_K, n))
+    _chk_k(k, n, self0, KNN_MAX_K)
     if not 1 <= C <= KNN_MAX_CLASSES:
         raise RuntimeError('contrad_hip: n_classes = %d outside [1, %d]' % (C, KNN_MAX_CLASSES))
     if not torch.is_tensor(labels) or not labels.is_cuda:
@@ -1215,9 +1222,7 @@ def prdc_kth(S, n, k, self0=-1, out=None):
     to write into.  contrad_prdc_kth's contract (include/contrad_hip.h)."""
     M, ldS, n = _chk_S(S, n)
     k, self0 = int(k), int(self0)
-    remain = n - 1 if 0 <= self0 < n else n
-    if not 1 <= k <= remain:
-        raise RuntimeError('contrad_hip: k = %d outside [1, %d] (n = %d, self0 = %d)' % (k, remain, n, self0))
+    _chk_k(k, n, self0, None)
     if out is None:
         out = torch.empty((M,), device=S.device, dtype=torch.float32)
     _chk_vec(out, 'out', M, torch.float32)
@@ -1252,32 +1257,42 @@ def prdc_count(S, n, thr_row=None, thr_col=None, row_hits=None, col_hits_c=None,
 
 
 # ---- kernel distance (csrc/kid.hip) ----
-def kid_sums(S, n, self0=-1, gamma=1.0, coef0=1.0, out=None, accumulate=False):
-    """out (1,) float64: the sum over rows i and columns j < n of ``S`` (M, ldS >= n), column ``self0 + i`` left out of row
-    i by index (``self0 < 0``: nothing is left out), of (gamma * S[i][j] + coef0)^3, every term in float64.  ``out``: a
-    float64 CUDA vector of one element to write into -- or, with ``accumulate``, to add to (a row chunk passes its first
-    row as ``self0``).  No atomics: two calls are bitwise equal.  contrad_kid_sums's contract (include/contrad_hip.h)."""
+MMD_KINDS = {'poly3': 0, 'rq': 1}                                           # contrad_mmd_sums's `kind`
+
+
+def _sums(who, S, n, kind, self0, gamma, coef0, out, accumulate):
+    """The one body of ``kid_sums`` and ``mmd_sums``; ``who`` names the caller in the messages and its entry point,
+    contrad_<who> (contrad_kid_sums is the kind = 0 entry point and takes no ``kind``)."""
     M, ldS, n = _chk_S(S, n)
+    if kind not in MMD_KINDS and kind not in MMD_KINDS.values():
+        raise RuntimeError('contrad_hip: %s kind %r (one of %s)' % (who, kind, ', '.join(MMD_KINDS)))
+    kind = MMD_KINDS.get(kind, kind)
     gamma, coef0 = float(gamma), float(coef0)
     if not (math.isfinite(gamma) and math.isfinite(coef0)):
-        raise RuntimeError('contrad_hip: kid_sums needs a finite gamma and coef0, got %r, %r' % (gamma, coef0))
+        raise RuntimeError('contrad_hip: %s needs a finite gamma and coef0, got %r, %r' % (who, gamma, coef0))
     if out is None:
         if accumulate:
-            raise RuntimeError('contrad_hip: kid_sums with accumulate adds to `out`')
+            raise RuntimeError('contrad_hip: %s with accumulate adds to `out`' % who)
         out = torch.empty((1,), device=S.device, dtype=torch.float64)
     _chk_vec(out, 'out', 1, torch.float64)
     if out.device != S.device:
         raise RuntimeError('contrad_hip: out is on %s, S on %s' % (out.device, S.device))
     nbytes = lib().raw('contrad_kid_sums_workspace_bytes')(M, n)
     if nbytes < 0:
-        raise RuntimeError('contrad_hip: bad kid_sums shape (%d)' % nbytes)
+        raise RuntimeError('contrad_hip: bad %s shape (%d)' % (who, nbytes))
     ws = _workspace(nbytes, S.device)
-    lib().call('contrad_kid_sums', _p(S), ctypes.c_longlong(ldS), M, n, ctypes.c_longlong(int(self0)), gamma, coef0,
+    kargs = (int(kind),) if who == 'mmd_sums' else ()
+    lib().call('contrad_' + who, _p(S), ctypes.c_longlong(ldS), M, n, ctypes.c_longlong(int(self0)), *kargs, gamma, coef0,
                1 if accumulate else 0, _p(out), _p(ws), ctypes.c_longlong(nbytes), _stream())
     return out
 
 
-MMD_KINDS = {'poly3': 0, 'rq': 1}                                           # contrad_mmd_sums's `kind`
+def kid_sums(S, n, self0=-1, gamma=1.0, coef0=1.0, out=None, accumulate=False):
+    """out (1,) float64: the sum over rows i and columns j < n of ``S`` (M, ldS >= n), column ``self0 + i`` left out of row
+    i by index (``self0 < 0``: nothing is left out), of (gamma * S[i][j] + coef0)^3, every term in float64.  ``out``: a
+    float64 CUDA vector of one element to write into -- or, with ``accumulate``, to add to (a row chunk passes its first
+    row as ``self0``).  No atomics: two calls are bitwise equal.  contrad_kid_sums's contract (include/contrad_hip.h)."""
+    return _sums('kid_sums', S, n, 0, self0, gamma, coef0, out, accumulate)
 
 
 def mmd_sums(S, n, kind='poly3', self0=-1, gamma=1.0, coef0=1.0, out=None, accumulate=False):
@@ -1285,27 +1300,7 @@ def mmd_sums(S, n, kind='poly3', self0=-1, gamma=1.0, coef0=1.0, out=None, accum
     'rq' (or 1), the rational-quadratic mixture 1 / sqrt(1 + u) + 1 / (1 + u / 2) + 1 / (1 + u / 4)^2 at
     u = max(2 - 2 s, 0) -- S holds similarities of UNIT vectors; gamma and coef0 are not read but must be finite.
     contrad_mmd_sums's contract (include/contrad_hip.h)."""
-    M, ldS, n = _chk_S(S, n)
-    if kind not in MMD_KINDS and kind not in MMD_KINDS.values():
-        raise RuntimeError('contrad_hip: mmd_sums kind %r (one of %s)' % (kind, ', '.join(MMD_KINDS)))
-    kind = MMD_KINDS.get(kind, kind)
-    gamma, coef0 = float(gamma), float(coef0)
-    if not (math.isfinite(gamma) and math.isfinite(coef0)):
-        raise RuntimeError('contrad_hip: mmd_sums needs a finite gamma and coef0, got %r, %r' % (gamma, coef0))
-    if out is None:
-        if accumulate:
-            raise RuntimeError('contrad_hip: mmd_sums with accumulate adds to `out`')
-        out = torch.empty((1,), device=S.device, dtype=torch.float64)
-    _chk_vec(out, 'out', 1, torch.float64)
-    if out.device != S.device:
-        raise RuntimeError('contrad_hip: out is on %s, S on %s' % (out.device, S.device))
-    nbytes = lib().raw('contrad_kid_sums_workspace_bytes')(M, n)
-    if nbytes < 0:
-        raise RuntimeError('contrad_hip: bad mmd_sums shape (%d)' % nbytes)
-    ws = _workspace(nbytes, S.device)
-    lib().call('contrad_mmd_sums', _p(S), ctypes.c_longlong(ldS), M, n, ctypes.c_longlong(int(self0)), int(kind), gamma, coef0,
-               1 if accumulate else 0, _p(out), _p(ws), ctypes.c_longlong(nbytes), _stream())
-    return out
+    return _sums('mmd_sums', S, n, kind, self0, gamma, coef0, out, accumulate)
 
 
 # ---- cDDLS sampling (csrc/cddls.hip) ----

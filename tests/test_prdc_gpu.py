@@ -106,6 +106,71 @@ def test_kth_kernel_on_a_given_S(shape, pad):
         assert np.isfinite(_raw_kth(_padded(S, pad), n + pad, M, n, 1, self0)).all()
 
 
+# ---- the two selects (csrc/simrow.h under prdc.hip and knn.hip) on the same S ----
+AGREE_SHAPES = [(3, 7, 6, 0), (5, 300, 5, 295), (2, 1025, 1, -1), (2, 1025, 1024, -1)]         # k <= 1024: knn_select's limit
+NANS = np.array([0x7fc00000, 0xffc00001, 0x7fc00123], np.uint32).view(np.float32)              # the very float must come back
+
+
+def _agree_inputs(shape):
+    """Rows on which the k-th place is decided by the tie rule.  `zeros-*`: Z columns of alternating -0.0 / +0.0 with fewer
+    than k columns above them and at least k down to their end, the own column (a -0.0 that must not count) right before the
+    run, in its middle or right behind it in column order -- where the row leaves no room on that side (a row without an own
+    column, an own column at either end), the run lies at the end, the middle or the start of the row.  `nans`: fewer than k
+    columns hold a number, so the k-th place is a NaN."""
+    M, n, k, self0 = shape
+    r = np.random.RandomState(2)
+    S = r.randn(M, n).astype(np.float32)
+    out = {'randn': S, 'equal': np.full((M, n), 0.25, np.float32)}
+    for where in ('before', 'inside', 'behind'):
+        x = np.empty((M, n), np.float32)
+        for i in range(M):
+            c = self0 + i if 0 <= self0 and self0 + i < n else None
+            cols = [j for j in range(n) if j != c]
+            at = len(cols) // 2 if c is None else sum(j < c for j in cols)       # cols[at] is the first column behind the own one
+            Z = min(max(len(cols) // 2, 2), 8)
+            above = min(max(k - Z // 2 - 1, 0), len(cols) - Z)                  # above < k <= above + Z
+            assert above < k <= above + Z
+            start = {'before': at, 'inside': at - Z // 2, 'behind': at - Z}[where]
+            if c is None:
+                start = {'before': len(cols) - Z, 'inside': at - Z // 2, 'behind': 0}[where]
+            start = min(max(start, 0), len(cols) - Z)
+            run = cols[start:start + Z]
+            rest = [cols[j] for j in r.permutation(len(cols)) if cols[j] not in run]
+            x[i, rest[:above]] = r.uniform(0.5, 1.5, above)
+            x[i, rest[above:]] = r.uniform(-1.5, -0.5, len(rest) - above)
+            x[i, run] = np.where(np.arange(Z) % 2 == i % 2, -0.0, 0.0)           # the k-th place is a -0.0 or a +0.0 by the row
+            if c is not None:
+                x[i, c] = -0.0
+        out['zeros-own-' + where] = x
+    x = S.copy()
+    for i in range(M):
+        c = self0 + i if 0 <= self0 and self0 + i < n else None
+        cols = np.array([j for j in range(n) if j != c])
+        holes = r.permutation(cols)[max(k - 2, 0):]                             # k - 2 numbers (none for k = 1): k reaches into the NaNs
+        x[i, holes] = NANS[np.arange(len(holes)) % 3]
+        if c is not None:
+            x[i, c] = NANS[0]
+    out['nans'] = x
+    return out
+
+
+@pytest.mark.parametrize('pad', [0, 3], ids=['dense', 'ld+3'])
+@pytest.mark.parametrize('shape', AGREE_SHAPES, ids=lambda s: 'x'.join(map(str, s)))
+def test_prdc_kth_equals_the_kth_value_of_knn_select_bit_for_bit(shape, pad):
+    """prdc_kth and knn_select share the key order and the radix select of csrc/simrow.h and each add a tie rule of their own
+    (prdc.hip's second ordered pass, knn.hip's compaction and sort): on the same S they must name the same float."""
+    from contrad_amd import ops
+    M, n, k, self0 = shape
+    labels = torch.zeros(n, dtype=torch.int64, device='cuda')
+    for name, S in _agree_inputs(shape).items():
+        S_dev = _padded(S, pad)
+        kth = ops.prdc_kth(S_dev, n, k, self0).cpu().numpy()
+        val = ops.knn_select(S_dev, n, labels, 1, k, 1.0, self0)[1][:, k - 1].cpu().numpy()
+        tag = 'kth against knn_select %s %s ld+%d' % ('x'.join(map(str, shape)), name, pad)
+        assert np.array_equal(kth.view(np.int32), val.view(np.int32)), (tag, kth, val)
+        assert np.array_equal(kth.view(np.int32), R.kth_exact(S, k, self0).view(np.int32)), tag      # ... and it is the right one
+
+
 # ---- prdc_count on a given S ----
 COUNT_SHAPES = [(1, 1), (3, 7), (65, 300), (257, 1025), (4, 70000)]
 
