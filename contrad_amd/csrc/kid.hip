@@ -8,6 +8,9 @@
 //               that would leave fewer than 1024 workgroups (a 1000 x 1000 block is 252 of them instead of 32).  A
 //               lane sums its terms in row order, the wave by a butterfly, the four waves in wave order: one float64
 //               partial per workgroup into the workspace.
+//               kind 2 (contrad_dot_sums only) takes a second operand T of the same shape, with a leading dimension and a
+//               vec_ok of its own, walked by the same load_tile behind the wave-uniform branch on `kind`: the term is
+//               (double)s * (double)t, exact in float64, and nothing is left out.  Kinds 0 and 1 load no T tile.
 //   kid_final   one workgroup adds the partials in a fixed order (thread t the partials t, t + 256, ...; then a tree
 //               in LDS) and one thread adds the old value last when `accumulate` is set.
 // No atomics: out[0] depends on no order of arrival, two calls are bitwise equal.
@@ -23,6 +26,7 @@ constexpr int KID_COLS = simrow::COLS;
 constexpr int KID_RPW_MAX = 32;                     // rows per wave of a tile
 constexpr int KID_RPW_MIN = 4;
 constexpr long long KID_ENOUGH_BLOCKS = 1024;
+constexpr int KID_KIND_DOT = 2;                     // internal: the product of two operands (contrad_dot_sums)
 
 struct KidPlan {
   long long ctiles, blocks;
@@ -50,17 +54,45 @@ __device__ __forceinline__ double kid_term(int kind, float s, double gamma, doub
   return 1.0 / sqrt(1.0 + u) + 1.0 / (1.0 + 0.5 * u) + 1.0 / (q * q);
 }
 
-__global__ __launch_bounds__(KID_THREADS) void kid_sums_kernel(const float* __restrict__ S, long long ldS, int M, int n,
-                                                               long long self0, int kind, double gamma, double coef0,
-                                                               double* __restrict__ partial, int ctiles, int rpw, int vec_ok) {
+// Kind 2, a wave's rows of a tile: the same walk on both operands, a lane's products added in row order.
+__device__ __forceinline__ double dot_rows(const float* __restrict__ S, long long ldS, const float* __restrict__ T, long long ldT,
+                                           long long r0, int rows, long long c0, int n, int vec_ok, int vec_ok_t) {
+  double acc = 0.0;
+  for (int t0 = 0; t0 < rows; t0 += 4) {
+    float v[4][4], t[4][4];
+    simrow::load_tile(v, S, ldS, r0, t0, rows, c0, n, vec_ok, 0.f, [](int, long long) {});
+    simrow::load_tile(t, T, ldT, r0, t0, rows, c0, n, vec_ok_t, 0.f, [](int, long long) {});
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const bool live = t0 + u < rows;                 // (uniform)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const double k = (double)v[u][j] * (double)t[u][j];       // 24 x 24 bits: exact
+        acc += live && c0 + j < n ? k : 0.0;
+      }
+    }
+  }
+  return acc;
+}
+
+// T may alias S (contrad_dot_sums with B = A): neither is written, so __restrict__ holds for both.
+__global__ __launch_bounds__(KID_THREADS) void kid_sums_kernel(const float* __restrict__ S, long long ldS,
+                                                               const float* __restrict__ T, long long ldT,
+                                                               int M, int n, long long self0, int kind, double gamma,
+                                                               double coef0, double* __restrict__ partial, int ctiles,
+                                                               int rpw, int vec_ok, int vec_ok_t) {
   __shared__ double red[4];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int ct = blockIdx.x % ctiles, rt = blockIdx.x / ctiles;
   const long long c0 = (long long)ct * KID_COLS + 4 * lane;
   const long long r0 = (long long)rt * 4 * rpw + w;   // this wave's rows: r0, r0 + 4, ...
-  const int rows = r0 < M ? (int)min((long long)rpw, (M - r0 + 3) >> 2) : 0;
+  int rows = r0 < M ? (int)min((long long)rpw, (M - r0 + 3) >> 2) : 0;
 
   double acc = 0.0;
+  if (kind == KID_KIND_DOT) {                          // (uniform) the T tile stays out of the loop of kinds 0 and 1
+    acc = dot_rows(S, ldS, T, ldT, r0, rows, c0, n, vec_ok, vec_ok_t);
+    rows = 0;
+  }
   for (int t0 = 0; t0 < rows; t0 += 4) {
     float v[4][4];
     simrow::load_tile(v, S, ldS, r0, t0, rows, c0, n, vec_ok, 0.f, [](int, long long) {});
@@ -109,21 +141,23 @@ extern "C" long long contrad_kid_sums_workspace_bytes(int M, int n) {
 
 namespace {
 
-int mmd_sums(const float* S, long long ldS, int M, int n, long long self0, int kind, double gamma, double coef0, int accumulate,
-             double* out, void* workspace, long long workspace_bytes, contrad_stream_t stream) {
+// T: the second operand of KID_KIND_DOT (null for the kinds of contrad_mmd_sums, which never read it).
+int mmd_sums(const float* S, long long ldS, const float* T, long long ldT, int M, int n, long long self0, int kind, double gamma,
+             double coef0, int accumulate, double* out, void* workspace, long long workspace_bytes, contrad_stream_t stream) {
   CONTRAD_ARG(S && out);
   CONTRAD_ARG(M >= 1 && n >= 1 && ldS >= n);
-  CONTRAD_ARG(kind == 0 || kind == 1);
+  CONTRAD_ARG(kind == 0 || kind == 1 || (kind == KID_KIND_DOT && T && ldT >= n));
   CONTRAD_ARG(isfinite(gamma) && isfinite(coef0));
   const KidPlan p = kid_plan(M, n);
   CONTRAD_ARG(p.blocks <= 0x7fffffffll);
   CONTRAD_ARG(workspace && workspace_bytes >= p.blocks * (long long)sizeof(double));
   CONTRAD_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)out & 7) == 0);
   const int vec_ok = (ldS % 4 == 0 && ((uintptr_t)S & 15) == 0) ? 1 : 0;
+  const int vec_ok_t = (T && ldT % 4 == 0 && ((uintptr_t)T & 15) == 0) ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;
   double* partial = (double*)workspace;
-  hipLaunchKernelGGL(kid_sums_kernel, dim3((unsigned)p.blocks), dim3(KID_THREADS), 0, st, S, ldS, M, n, self0, kind, gamma,
-                     coef0, partial, (int)p.ctiles, p.rpw, vec_ok);
+  hipLaunchKernelGGL(kid_sums_kernel, dim3((unsigned)p.blocks), dim3(KID_THREADS), 0, st, S, ldS, T, ldT, M, n, self0, kind,
+                     gamma, coef0, partial, (int)p.ctiles, p.rpw, vec_ok, vec_ok_t);
   CONTRAD_CHECK_LAUNCH();
   hipLaunchKernelGGL(kid_final_kernel, dim3(1), dim3(KID_THREADS), 0, st, partial, (int)p.blocks, accumulate ? 1 : 0, out);
   CONTRAD_CHECK_LAUNCH();
@@ -135,11 +169,18 @@ int mmd_sums(const float* S, long long ldS, int M, int n, long long self0, int k
 extern "C" int contrad_kid_sums(const float* S, long long ldS, int M, int n, long long self0, double gamma, double coef0,
                                 int accumulate, double* out, void* workspace, long long workspace_bytes,
                                 contrad_stream_t stream) {
-  return mmd_sums(S, ldS, M, n, self0, 0, gamma, coef0, accumulate, out, workspace, workspace_bytes, stream);
+  return mmd_sums(S, ldS, nullptr, 0, M, n, self0, 0, gamma, coef0, accumulate, out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int contrad_mmd_sums(const float* S, long long ldS, int M, int n, long long self0, int kind, double gamma,
                                 double coef0, int accumulate, double* out, void* workspace, long long workspace_bytes,
                                 contrad_stream_t stream) {
-  return mmd_sums(S, ldS, M, n, self0, kind, gamma, coef0, accumulate, out, workspace, workspace_bytes, stream);
+  CONTRAD_ARG(kind == 0 || kind == 1);                 // the two-operand kind is contrad_dot_sums's alone
+  return mmd_sums(S, ldS, nullptr, 0, M, n, self0, kind, gamma, coef0, accumulate, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int contrad_dot_sums(const float* A, long long ldA, const float* B, long long ldB, int M, int n, int accumulate,
+                                double* out, void* workspace, long long workspace_bytes, contrad_stream_t stream) {
+  CONTRAD_ARG(A && B);
+  return mmd_sums(A, ldA, B, ldB, M, n, -1, KID_KIND_DOT, 1.0, 0.0, accumulate, out, workspace, workspace_bytes, stream);
 }

@@ -1260,11 +1260,17 @@ def prdc_count(S, n, thr_row=None, thr_col=None, row_hits=None, col_hits_c=None,
 MMD_KINDS = {'poly3': 0, 'rq': 1}                                           # contrad_mmd_sums's `kind`
 
 
-def _sums(who, S, n, kind, self0, gamma, coef0, out, accumulate):
-    """The one body of ``kid_sums`` and ``mmd_sums``; ``who`` names the caller in the messages and its entry point,
-    contrad_<who> (contrad_kid_sums is the kind = 0 entry point and takes no ``kind``)."""
+def _sums(who, S, n, kind, self0, gamma, coef0, out, accumulate, T=None):
+    """The one body of ``kid_sums``, ``mmd_sums`` and ``dot_sums``; ``who`` names the caller in the messages and its entry
+    point, contrad_<who> (contrad_kid_sums is the kind = 0 entry point and takes no ``kind``; contrad_dot_sums takes the
+    second operand ``T`` and neither ``self0``, ``kind``, gamma nor coef0)."""
     M, ldS, n = _chk_S(S, n)
-    if kind not in MMD_KINDS and kind not in MMD_KINDS.values():
+    if T is not None:
+        _chk(T, 'B')
+        if T.dim() != 2 or T.shape[0] != M or T.shape[1] < n or T.device != S.device:
+            raise RuntimeError('contrad_hip: %s operands of %s and %s for n = %d (the same rows, at least n columns, one device)'
+                               % (who, tuple(S.shape), tuple(T.shape), n))
+    elif kind not in MMD_KINDS and kind not in MMD_KINDS.values():
         raise RuntimeError('contrad_hip: %s kind %r (one of %s)' % (who, kind, ', '.join(MMD_KINDS)))
     kind = MMD_KINDS.get(kind, kind)
     gamma, coef0 = float(gamma), float(coef0)
@@ -1281,9 +1287,12 @@ def _sums(who, S, n, kind, self0, gamma, coef0, out, accumulate):
     if nbytes < 0:
         raise RuntimeError('contrad_hip: bad %s shape (%d)' % (who, nbytes))
     ws = _workspace(nbytes, S.device)
+    tail = (1 if accumulate else 0, _p(out), _p(ws), ctypes.c_longlong(nbytes), _stream())
+    if T is not None:
+        lib().call('contrad_' + who, _p(S), ctypes.c_longlong(ldS), _p(T), ctypes.c_longlong(_ld(T)), M, n, *tail)
+        return out
     kargs = (int(kind),) if who == 'mmd_sums' else ()
-    lib().call('contrad_' + who, _p(S), ctypes.c_longlong(ldS), M, n, ctypes.c_longlong(int(self0)), *kargs, gamma, coef0,
-               1 if accumulate else 0, _p(out), _p(ws), ctypes.c_longlong(nbytes), _stream())
+    lib().call('contrad_' + who, _p(S), ctypes.c_longlong(ldS), M, n, ctypes.c_longlong(int(self0)), *kargs, gamma, coef0, *tail)
     return out
 
 
@@ -1301,6 +1310,16 @@ def mmd_sums(S, n, kind='poly3', self0=-1, gamma=1.0, coef0=1.0, out=None, accum
     u = max(2 - 2 s, 0) -- S holds similarities of UNIT vectors; gamma and coef0 are not read but must be finite.
     contrad_mmd_sums's contract (include/contrad_hip.h)."""
     return _sums('mmd_sums', S, n, kind, self0, gamma, coef0, out, accumulate)
+
+
+def dot_sums(A, B, n, out=None, accumulate=False):
+    """out (1,) float64: the sum over rows i and columns j < n of ``A[i][j] * B[i][j]`` on ``A`` (M, ldA >= n) and ``B``
+    (M, ldB >= n), each product exact in float64, added in ``kid_sums``'s fixed order (no atomics: two calls are bitwise
+    equal).  ``B`` may be ``A``: the sum of squares.  ``out`` / ``accumulate``: as in ``kid_sums``.  contrad_dot_sums's
+    contract (include/contrad_hip.h)."""
+    if B is None:
+        raise RuntimeError('contrad_hip: dot_sums needs two operands (pass A twice for the sum of squares)')
+    return _sums('dot_sums', A, n, 0, -1, 1.0, 0.0, out, accumulate, T=B)
 
 
 # ---- cDDLS sampling (csrc/cddls.hip) ----

@@ -27,7 +27,8 @@ which follows ``KNNMonitor``: modules of its own, so that the training trajector
 METRIC`` keeps ``gen_best.pt`` / ``dis_best.pt`` (/ ``gen_ema_best.pt``), the names the reference gives its best-FID
 checkpoints, for the best value of that metric.  ``--prdc_kid`` adds the kernel distance of contrad_amd/kid.py to every
 evaluation (``kid_<seed>.csv``; ``--prdc_best kid`` selects its minimum); ``--prdc_kid_kernel rq`` makes that the
-rational-quadratic distance, in ``kid_rq_<seed>.csv``.
+rational-quadratic distance, in ``kid_rq_<seed>.csv``.  ``--prdc_fd`` adds the Frechet distance of contrad_amd/fd.py
+(``fd_<seed>.csv``; it records only).
 """
 import os
 from argparse import SUPPRESS
@@ -35,6 +36,7 @@ from types import SimpleNamespace
 
 import torch
 
+from . import fd as fd_mod
 from . import features, ops
 from . import kid as kid_mod
 from . import nearest
@@ -157,10 +159,14 @@ class PRDCMonitor(object):
     ``kid_<eval_seed>.csv``: the two are different numbers), which ``best='kid'`` then tracks and reads back.  ``auth``
     (``--prdc_auth``): the real features are extracted once for both states -- ``real_state_of`` and ``nearest.real_state_of``
     on the same bank -- and each evaluation also appends ``step,authenticity,nearest_mean`` to ``auth_<eval_seed>.csv``
-    (contrad_amd/nearest.py: the memorisation check); it records only and is no ``best``."""
+    (contrad_amd/nearest.py: the memorisation check); it records only and is no ``best``.  ``fd`` (``--prdc_fd``): the real
+    state of contrad_amd/fd.py is made once from the same bank and each evaluation also appends
+    ``step,fd,mean_term,trace_fake,cross_term,tail`` to ``fd_<eval_seed>.csv``, the Frechet distance of the same fake
+    features after ``fd_iter`` Newton-Schulz steps (``--prdc_fd_iter``); it records only and is no ``best``."""
 
     def __init__(self, logdir, architecture, image_size, device, seed, data_path, encoder_path, encoder_arch=None, k=5,
-                 n_fake=10000, batch=500, best=None, resumed_step=0, P=None, kid=False, kid_kernel='poly3', auth=False):
+                 n_fake=10000, batch=500, best=None, resumed_step=0, P=None, kid=False, kid_kernel='poly3', auth=False, fd=False,
+                 fd_iter=fd_mod.N_ITER):
         real = features.load_images(data_path, 'x_train')
         if tuple(real.shape[1:]) != tuple(image_size):
             raise ValueError('%s: x_train holds %s images, the generator makes %s' % (data_path, tuple(real.shape[1:]), tuple(image_size)))
@@ -176,6 +182,8 @@ class PRDCMonitor(object):
             kid_mod.check_sizes(len(real), n_fake)
         if auth and len(real) < 2:
             raise ValueError('--prdc_auth needs at least 2 real images (%d)' % len(real))
+        if fd:
+            fd_mod.check_sizes(len(real), n_fake, fd_iter)
         self.k, self.n_fake, self.batch, self.device, self.metric = int(k), int(n_fake), int(batch), device, best
         self.eval_seed = eval_seed_of(seed)
         self.path = os.path.join(logdir, 'prdc_%d.csv' % self.eval_seed)
@@ -183,6 +191,8 @@ class PRDCMonitor(object):
         self.kid_path = os.path.join(logdir, kid_csv_name(kid_kernel) % self.eval_seed) if kid else None
         self.auth_path = os.path.join(logdir, 'auth_%d.csv' % self.eval_seed) if auth else None
         self.auth_state = None
+        self.fd_path = os.path.join(logdir, 'fd_%d.csv' % self.eval_seed) if fd else None
+        self.fd_state, self.fd_iter = None, int(fd_iter)
         self.n_real = len(real)
         self.G = own_network('G', architecture, image_size, device, P)
         with preserved_rng(device):                                        # the constructors draw the initial weights
@@ -197,8 +207,11 @@ class PRDCMonitor(object):
                 feats = features.extract_features(self.E, real_u8, self.batch)
                 self.real_state = real_state_of(feats, self.k, normalize=False)
                 self.auth_state = nearest.real_state_of(feats, normalize=False, bankT=self.real_state[0])
+            if fd:                                                         # the same bank: centred once, here
+                self.fd_state = fd_mod.real_state_of(self.real_state[0], self.n_real)
         self.files = [(self.path, CSV_HEAD, csv_line)] + ([(self.kid_path, kid_mod.CSV_HEAD, kid_mod.csv_line)] if kid else []) + \
-            ([(self.auth_path, nearest.CSV_HEAD, nearest.csv_line)] if auth else [])       # (after the files --prdc_best tracks)
+            ([(self.auth_path, nearest.CSV_HEAD, nearest.csv_line)] if auth else []) + \
+            ([(self.fd_path, fd_mod.CSV_HEAD, fd_mod.csv_line)] if fd else [])             # (after the files --prdc_best tracks)
         self.best = None
         for j, (path, head, _) in enumerate(self.files):
             if not os.path.exists(path):                                   # (a resumed run appends to its file)
@@ -227,6 +240,11 @@ class PRDCMonitor(object):
             if self.auth_path is not None:                                 # the same fake features, the same real bank
                 a = nearest.authenticity(None, feats, real_state=self.auth_state, normalize=False)
                 out['authenticity'], out['nearest_mean'], out['real_nearest_mean'] = a['authenticity'], a['nearest_mean'], a['real_nearest_mean']
+            if self.fd_path is not None:                                   # the same fake features, the real state made once
+                f = fd_mod.fd(None, feats, self.fd_iter, normalize=False, real_state=self.fd_state)
+                out['fd'] = f['fd']
+                for name in ('mean_term', 'trace_fake', 'cross_term', 'tail'):
+                    out['fd_' + name] = f[name]
         lines = []
         for path, _, line_of in self.files:
             lines.append(line_of(step, out))
@@ -251,11 +269,14 @@ class PRDCMonitor(object):
         if 'authenticity' in out:
             lines.append('[Steps %7d] [authenticity %.4f] [nearest %.4f, real to real %.4f]' % (
                 step, out['authenticity'], out['nearest_mean'], out['real_nearest_mean']))
+        if 'fd' in out:
+            lines.append('[Steps %7d] [fd %.6f] [means %.6f] [tr fake %.6f] [cross %.6f] [tail %.3e]' % (
+                step, out['fd'], out['fd_mean_term'], out['fd_trace_fake'], out['fd_cross_term'], out['fd_tail']))
         return lines
 
 
 HOOK_DEFAULTS = {'prdc_data': None, 'prdc_encoder': None, 'prdc_encoder_arch': None, 'prdc_k': 5, 'prdc_n': 10000, 'prdc_best': None,
-                 'prdc_kid': False, 'prdc_kid_kernel': 'poly3', 'prdc_auth': False}
+                 'prdc_kid': False, 'prdc_kid_kernel': 'poly3', 'prdc_auth': False, 'prdc_fd': False, 'prdc_fd_iter': fd_mod.N_ITER}
 
 
 def kid_csv_name(kid_kernel):
@@ -297,6 +318,13 @@ def add_hook_arguments(parser):
                              'its nearest real image than that image is to its own nearest other real image, and the mean '
                              'similarity of a fake to its nearest real.  It records only (no --prdc_best choice: not a quantity '
                              'to maximise); read it against test_nearest.py --holdout, not against 1')
+    parser.add_argument('--prdc_fd', action='store_true', **off,
+                        help='with --prdc_data: every evaluation also appends step,fd,mean_term,trace_fake,cross_term,tail to '
+                             'fd_<seed>.csv: the Frechet distance (contrad_amd/fd.py) of the same fake features from the real set, '
+                             'comparable only under one --prdc_encoder file, never with Inception-based FID.  It records only: '
+                             '--prdc_best gains no choice for it')
+    parser.add_argument('--prdc_fd_iter', type=int, **off,
+                        help='with --prdc_fd: Newton-Schulz steps per evaluation, fixed (default: %d)' % fd_mod.N_ITER)
 
 
 def hook_options(P):
@@ -317,6 +345,10 @@ def check_hook_arguments(P):
         raise ValueError('--prdc_kid_kernel needs --prdc_kid: without it no kernel distance is computed')
     if H.prdc_best == 'kid' and not H.prdc_kid:
         raise ValueError('--prdc_best kid needs --prdc_kid: without it no kernel distance is computed')
+    if hasattr(P, 'prdc_fd_iter') and not H.prdc_fd:
+        raise ValueError('--prdc_fd_iter needs --prdc_fd: without it no Frechet distance is computed')
+    if H.prdc_fd_iter < 1:
+        raise ValueError('--prdc_fd_iter must be at least 1, got %r' % (H.prdc_fd_iter,))
     return H
 
 

@@ -251,7 +251,8 @@ def build_run(P, script):
         prdc_monitor = prdc.PRDCMonitor(logdir, P.architecture, image_size, dev, P.seed, H.prdc_data, H.prdc_encoder,
                                         encoder_arch=H.prdc_encoder_arch, k=H.prdc_k, n_fake=H.prdc_n, best=H.prdc_best,
                                         resumed_step=starting_step - 1, P=P, kid=H.prdc_kid,
-                                        kid_kernel=H.prdc_kid_kernel, auth=H.prdc_auth)
+                                        kid_kernel=H.prdc_kid_kernel, auth=H.prdc_auth, fd=H.prdc_fd,
+                                        fd_iter=H.prdc_fd_iter)
     graphed, why_not = graph_gate(P, script)
     if why_not:
         log(why_not)

@@ -812,6 +812,17 @@ int contrad_kid_sums(const float* S, long long ldS, int M, int n, long long self
  * -EINVAL (before any GPU call) on everything contrad_kid_sums refuses and on a kind outside {0, 1}. */
 int contrad_mmd_sums(const float* S, long long ldS, int M, int n, long long self0, int kind, double gamma, double coef0,
                      int accumulate, double* out, void* workspace, long long workspace_bytes, contrad_stream_t stream);
+/* The sum kernel on two operands (contrad_amd/fd.py: traces, Frobenius norms and the nuclear-norm estimates of the
+ * Frechet distance): out[0] = (accumulate ? out[0] : 0) + sum over i < M, j < n of (double)A[i][j] * (double)B[i][j] on
+ * A[M][ldA] and B[M][ldB] (only columns [0, n) are read).  Every product is exact in float64 and added in float64; the
+ * walk, the workspace (contrad_kid_sums_workspace_bytes(M, n)), the fixed summation order and the second launch are
+ * contrad_kid_sums's: no atomics, two calls are bitwise equal.  B may alias A (the sum of squares).  Each operand takes
+ * 16-byte loads when it is 16-byte aligned and its leading dimension a multiple of 4, by itself.  A NaN or inf inside
+ * either block propagates.  -EINVAL (before any GPU call) on a null A, B or out, M < 1, n < 1, ldA < n, ldB < n, a
+ * workspace that is null, smaller than the query says or not 8-byte aligned, an out that is not 8-byte aligned.  This
+ * is the only way to the two-operand kind: contrad_mmd_sums refuses every kind outside {0, 1}. */
+int contrad_dot_sums(const float* A, long long ldA, const float* B, long long ldB, int M, int n, int accumulate, double* out,
+                     void* workspace, long long workspace_bytes, contrad_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -2,6 +2,7 @@
 another build's, both loaded side by side in one process.  Behind profiles/simrow.txt.
 
     python tools/ab_simrow.py PARENT.so PARENT_AGAIN.so [OUT.txt]
+    python tools/ab_simrow.py PARENT.so PARENT_AGAIN.so OUT.txt kid    # contrad_mmd_sums alone, at tools/bench_kid.py's shapes (profiles/fd.txt)
 
 PARENT.so: the library of the commit to compare with (the three sources of that commit compiled and linked with this tree's
 other objects, or a second checkout's library); PARENT_AGAIN.so: a copy of it under another name, so that the parent's own
@@ -32,6 +33,7 @@ for name, path in BUILDS:
 dev = torch.device('cuda', 0)
 LL = ctypes.c_longlong
 lines = []
+KID_ONLY = len(sys.argv) > 4 and sys.argv[4] == 'kid'
 
 
 def emit(s):
@@ -56,6 +58,8 @@ def one_run(fn):
 
 def ab(title, make_call, outputs):
     """make_call(lib) -> a function of no arguments that launches once and writes `outputs` (tensors)."""
+    if KID_ONLY and not title.startswith('mmd_sums'):
+        return True
     calls = [make_call(lb) for lb in libs]
     runs = [[] for _ in libs]
     for _ in range(7):
@@ -85,7 +89,7 @@ def ab(title, make_call, outputs):
 g = torch.Generator(device='cpu').manual_seed(0)
 M, n = 512, 50000
 S = (torch.randn(M, n, generator=g) * 0.1).to(dev)
-S1 = torch.randn(M, n, generator=g).clamp_(-1, 1).to(dev)
+S1 = torch.randn(4096 if KID_ONLY else M, n, generator=g).clamp_(-1, 1).to(dev)
 Ssm = torch.randn(1000, 1000, generator=g).clamp_(-1, 1).to(dev)
 labels = torch.randint(0, 10, (n,), generator=g).to(dev)
 st = ops._stream()
@@ -132,7 +136,7 @@ for title, tr_, tc_ in (('both thresholds', t_row, t_col), ('thr_col only', None
 
 # mmd_sums
 out = torch.empty((1,), device=dev, dtype=torch.float64)
-for X, name in ((Ssm, '1000 x 1000'), (S1, '512 x 50 000')):
+for X, name in ((Ssm, '1000 x 1000'), (S1, '%d x 50 000' % S1.shape[0])):
     m_, n_ = X.shape
     nbytes = libs[0].raw('contrad_kid_sums_workspace_bytes')(m_, n_)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
