@@ -11,14 +11,16 @@ that ``--graph`` captures once and replays ``n_steps - 1`` times:
 
     G forward (kept activations) -> x = G(z) + eps z2 -> D trunk + logit head forward -> [energy]
     -> logit-head dgrads (seed -1) -> feature seed (+ class row, lrelu') -> 6 trunk dgrads + RGB dgrad
+       [snresnet18: pooled seed -> per block, last to first: dgrads of conv2, conv1 and the shortcut conv, residual join
+        -> RGB dgrad]
     -> image end (gradient through tanh, z2 update) -> G backward (conv forward kernels on the same packed weights,
     eval BatchNorm+ReLU backward, 1x1 dgrad) -> latent update (advances the device-resident step counter)
 
 The noise comes from the in-kernel counter-based generator of csrc/cddls.hip: a draw depends on (seed, stream, step,
 element) only, the step is read from device memory, so eager and ``--graph`` runs write bitwise-equal images.
 
-Scope: ``sndcgan`` (any image size the modules accept).  The reference's ``clamp(z, -1, 1)`` belongs to SNDCGAN's uniform
-latent; other architectures raise NotImplementedError.
+Scope: ``sndcgan`` (any image size the modules accept) and ``snresnet18`` (G_SNDCGAN with D_SNResNet18, 32 x 32).  The
+reference's ``clamp(z, -1, 1)`` belongs to SNDCGAN's uniform latent; other architectures raise NotImplementedError.
 """
 import math
 import os
@@ -32,7 +34,7 @@ from .captured import EagerFirst, capture
 from .hostio import THROTTLE, to_uint8, write_png
 from .models.gan.sndcgan import _D_CONVS, _SLOPE, _flat_views
 
-IMPLEMENTED = ('sndcgan',)
+IMPLEMENTED = ('sndcgan', 'snresnet18')
 STREAM_INIT = 2          # stream id of the initial z2 (csrc/cddls.hip: CD_STREAM_INIT; 0 and 1 are drawn inside the update kernels)
 
 
@@ -76,16 +78,232 @@ def permute_class_row(w_row, hb, wb):
     return w_row.reshape(512, hb * wb).t().reshape(-1)
 
 
+class _DHalfSNDCGAN(object):
+    """The D half of a Langevin step on D_SNDCGAN: seven plain convs, the logit head on the 8192 NHWC-flat features.
+    Stateless: everything it prepares lives on the sampler ``S``."""
+
+    @staticmethod
+    def geometry(S):
+        S.hb, S.wb = S.D.s_hb, S.D.s_wb
+
+    @staticmethod
+    def class_row(S, w_row):
+        return permute_class_row(w_row, S.hb, S.wb)
+
+    @staticmethod
+    def prep(S):
+        D, dev, N = S.D, S.dev, S.n
+        head = D._head()
+        S.d_layers = [D.main[2 * i] for i in range(7)] + [head.l1, head.l2]
+        T = S.hb * S.wb
+        specs = [ops.SnSpec(m.weight_orig, m.weight_u, m.weight_v) for m in S.d_layers[:7]]
+        specs.append(ops.SnSpec(head.l1.weight_orig, head.l1.weight_u, head.l1.weight_v, view_kct=(S.dh, 512, T)))
+        specs.append(ops.SnSpec(head.l2.weight_orig, head.l2.weight_u, head.l2.weight_v))
+        sizes = [s.T * s.C * s.K for s in specs[:7]] + [S.feat * S.dh, S.dh * 4]
+        S.d_wbuf, v = _flat_views(sizes, dev)
+        S.d_wps = [v[i].view(s.T * s.C, s.K) for i, s in enumerate(specs[:7])]
+        S.d_wps += [v[7].view(S.feat, S.dh), v[8].view(S.dh, 4)]
+        ldws = [s.K for s in specs[:7]] + [S.dh, 4]
+        offs, scr_n = ops.sn_scratch_floats(specs)
+        scratch = torch.empty(scr_n, device=dev, dtype=torch.float32)
+        sigma = torch.empty(len(specs), device=dev, dtype=torch.float32)
+        ops.sn_weight_prep(specs, S.d_wps, ldws, False, scratch, offs, sigma)      # eval: stored u, v, no iteration
+        S.d_filters = None
+        if ops.FILTER_PREP:
+            reqs, hw = [], (8 * S.hb, 8 * S.wb)
+            for i in range(1, 7):
+                ci, co, k, s, p = _D_CONVS[i]
+                d = ops.fwd_desc((N, hw[0], hw[1], ci), S.d_wps[i], co, k, k, s, p)
+                reqs += [(0, d, S.d_wps[i]), (1, d, S.d_wps[i])]
+                hw = (d.Ho, d.Wo)
+            S.d_filters = ops.filter_prep(reqs, dev)
+
+    @staticmethod
+    def alloc(S, buf):
+        N, hw, dshapes = S.n, (8 * S.hb, 8 * S.wb), []
+        for ci, co, k, s, p in _D_CONVS:
+            hw = (ops.out_size(hw[0], k, s, p), ops.out_size(hw[1], k, s, p))
+            dshapes.append((N, hw[0], hw[1], co))
+        S.d_acts = [buf(*s) for s in dshapes]
+        S.d_grads = [buf(*s) for s in dshapes]
+        S.d_feats = S.d_acts[6]                     # the penultimate features, (N, hb, wb, 512) NHWC
+
+    @staticmethod
+    def forward(S):
+        N, w, L = S.n, S.d_wps, S.d_layers
+        ops.rgb_conv_fwd(S.x, w[0], L[0].bias, 64, 3, 2.0, -1.0, _SLOPE, 1.0, out=S.d_acts[0])
+        for i in range(1, 7):
+            ci, co, k, s, p = _D_CONVS[i]
+            ops.conv2d_fwd(S.d_acts[i - 1], w[i], L[i].bias, co, k, k, s, p, _SLOPE, 1.0, out=S.d_acts[i],
+                           filters=S.d_filters)
+        ops.conv2d_fwd(S.d_acts[6].view(N, 1, 1, S.feat), w[7], L[7].bias, S.dh, 1, 1, 1, 0, _SLOPE, 1.0,
+                       out=S.hidden)
+        ops.conv2d_fwd(S.hidden, w[8], L[8].bias, 1, 1, 1, 1, 0, out=S.logits)
+
+    @staticmethod
+    def backward(S):
+        N, w = S.n, S.d_wps
+        ops.conv2d_dgrad(S.neg_one, w[8], (N, 1, 1, S.dh), 1, 1, 1, 0, act_ref=S.hidden, slope=_SLOPE, gain=1.0,
+                         out=S.g_hidden)
+        g = S.d_grads[6]
+        ops.conv2d_dgrad(S.g_hidden, w[7], (N, 1, 1, S.feat), 1, 1, 1, 0, out=g.view(N, 1, 1, S.feat))
+        ops.cddls_feature_seed(g, S.c_row, S.d_acts[6], _SLOPE, out=g)
+        for i in range(6, 0, -1):
+            ci, co, k, s, p = _D_CONVS[i]
+            a = S.d_acts[i - 1]
+            g = ops.conv2d_dgrad(g, w[i], tuple(a.shape), k, k, s, p, act_ref=a, slope=_SLOPE, gain=1.0,
+                                 out=S.d_grads[i - 1], filters=S.d_filters)
+        ops.rgb_conv_dgrad(g, w[0], None, 3, 3, act=0, out_scale=2.0, out_shift=0.0, out=S.g_x)
+
+    @staticmethod
+    def regions(S):
+        return [(a > 0).permute(0, 3, 1, 2) for a in S.d_acts]
+
+
+class _DHalfSNResNet18(object):
+    """The D half on D_SNResNet18 (32 x 32): the stem, eight residual blocks, the 4 x 4 mean, the logit head on the 512
+    pooled features.  The backward walks the blocks last to first; the residual join and the pooled seed are index forms
+    of the feature-seed kernel (csrc/cddls.hip).  Stateless like _DHalfSNDCGAN."""
+
+    @staticmethod
+    def geometry(S):
+        S.hb, S.wb = S.G.s_hb, S.G.s_wb
+        if (8 * S.hb, 8 * S.wb) != (32, 32):
+            raise NotImplementedError('cDDLS sampling with D_SNResNet18: 32x32 images (its 4x4 average pool)')
+
+    @staticmethod
+    def class_row(S, w_row):
+        return w_row                                # pooled features are in channel order already
+
+    @staticmethod
+    def _blocks(D):
+        return [blk for li in range(1, 5) for blk in getattr(D, 'layer%d' % li)]
+
+    @staticmethod
+    def prep(S):
+        D, dev, N = S.D, S.dev, S.n
+        head = D._head()
+        blocks = _DHalfSNResNet18._blocks(D)
+        # (conv module, cin, cout, k, stride, pad, input map) of the trunk convs behind the stem, in execution order
+        S.d_blocks, convs, hw, cin = [], [], 32, 64
+        for blk in blocks:
+            p, s = blk.planes, blk.stride
+            ho = ops.out_size(hw, 3, s, 1)
+            ent = {'c1': len(convs) + 1, 'c2': len(convs) + 2, 'sc': None, 'in': (N, hw, hw, cin), 'out': (N, ho, ho, p),
+                   'planes': p, 'stride': s}
+            convs += [(blk.conv1, cin, p, 3, s, 1, hw), (blk.conv2, p, p, 3, 1, 1, ho)]
+            if len(blk.shortcut):
+                ent['sc'] = len(convs) + 1
+                convs.append((blk.shortcut[0], cin, p, 1, s, 0, hw))
+            S.d_blocks.append(ent)
+            hw, cin = ho, p
+        S.d_layers = [D.conv1] + [c[0] for c in convs] + [head.l1, head.l2]
+        specs = [ops.SnSpec(m.weight_orig, m.weight_u, m.weight_v) for m in S.d_layers]
+        ldws = [ops.round_up(s.K, 4) for s in specs]
+        S.d_wbuf, v = _flat_views([s.T * s.C * ld for s, ld in zip(specs, ldws)], dev)
+        S.d_wps = [v[i].view(s.T * s.C, ld) for i, (s, ld) in enumerate(zip(specs, ldws))]
+        offs, scr_n = ops.sn_scratch_floats(specs)
+        scratch = torch.empty(scr_n, device=dev, dtype=torch.float32)
+        sigma = torch.empty(len(specs), device=dev, dtype=torch.float32)
+        ops.sn_weight_prep(specs, S.d_wps, ldws, False, scratch, offs, sigma)      # eval: stored u, v, no iteration
+        S.d_filters = None
+        if ops.FILTER_PREP:
+            reqs = []
+            for i, (m, ci, co, k, s, p, h) in enumerate(convs, 1):
+                d = ops.fwd_desc((N, h, h, ci), S.d_wps[i], co, k, k, s, p)
+                reqs += [(0, d, S.d_wps[i]), (1, d, S.d_wps[i])]
+            S.d_filters = ops.filter_prep(reqs, dev)
+
+    @staticmethod
+    def alloc(S, buf):
+        N = S.n
+        S.d_stem = buf(N, 32, 32, 64)
+        S.d_c1 = [buf(*b['out']) for b in S.d_blocks]                       # conv1 outputs (post-LeakyReLU)
+        S.d_sc = [buf(*b['out']) if b['sc'] is not None else None for b in S.d_blocks]
+        S.d_outs = [buf(*b['out']) for b in S.d_blocks]                     # block outputs (post-LeakyReLU)
+        S.d_acts = [S.d_stem] + [t for pair in zip(S.d_c1, S.d_outs) for t in pair]     # the 17 LeakyReLU outputs
+        S.d_pre = buf(N * 32 * 32 * 64)                                     # a join's pre-activation, any block
+        S.d_gbufs = [buf(N * 32 * 32 * 64) for _ in range(3)]               # rotating gradient storage, any level
+        S.d_feats = buf(N, 512)                                             # the penultimate features (4 x 4 mean)
+        S.g_feats = buf(N, 512)
+
+    @staticmethod
+    def _view(flat, shape):
+        return flat[:math.prod(shape)].view(shape)
+
+    @staticmethod
+    def forward(S):
+        N, w, L, view = S.n, S.d_wps, S.d_layers, _DHalfSNResNet18._view
+        ops.rgb_conv_fwd(S.x, w[0], L[0].bias, 64, 3, 2.0, -1.0, _SLOPE, 1.0, out=S.d_stem)
+        h = S.d_stem
+        for j, b in enumerate(S.d_blocks):
+            i1, i2, isc, p, s = b['c1'], b['c2'], b['sc'], b['planes'], b['stride']
+            ops.conv2d_fwd(h, w[i1], L[i1].bias, p, 3, 3, s, 1, _SLOPE, 1.0, out=S.d_c1[j], filters=S.d_filters)
+            sc = h
+            if isc is not None:
+                sc = ops.conv2d_fwd(h, w[isc], L[isc].bias, p, 1, 1, s, 0, out=S.d_sc[j], filters=S.d_filters)
+            pre = view(S.d_pre, b['out'])
+            ops.conv2d_fwd(S.d_c1[j], w[i2], L[i2].bias, p, 3, 3, 1, 1, 1.0, 1.0, out=pre, addend=sc, filters=S.d_filters)
+            h = ops.fused_bias_act(pre, None, None, 3, 0, _SLOPE, 1.0, out=S.d_outs[j])
+        torch.mean(h, (1, 2), out=S.d_feats)
+        n = len(w)
+        ops.conv2d_fwd(S.d_feats.view(N, 1, 1, 512), w[n - 2], L[n - 2].bias, S.dh, 1, 1, 1, 0, _SLOPE, 1.0, out=S.hidden)
+        ops.conv2d_fwd(S.hidden, w[n - 1], L[n - 1].bias, 1, 1, 1, 1, 0, out=S.logits)
+
+    @staticmethod
+    def backward(S):
+        N, w, view, n = S.n, S.d_wps, _DHalfSNResNet18._view, len(S.d_wps)
+        ops.conv2d_dgrad(S.neg_one, w[n - 1], (N, 1, 1, S.dh), 1, 1, 1, 0, act_ref=S.hidden, slope=_SLOPE, gain=1.0,
+                         out=S.g_hidden)
+        ops.conv2d_dgrad(S.g_hidden, w[n - 2], (N, 1, 1, 512), 1, 1, 1, 0, out=S.g_feats.view(N, 1, 1, 512))
+        P, Q, R = S.d_gbufs
+        # gp: the gradient at the pre-activation of the join the walk stands at
+        gp = ops.cddls_pooled_seed(S.g_feats, S.c_row, S.d_outs[-1], _SLOPE, out=view(P, S.d_blocks[-1]['out']))
+        for j in range(len(S.d_blocks) - 1, -1, -1):
+            b = S.d_blocks[j]
+            i1, i2, isc, p, s = b['c1'], b['c2'], b['sc'], b['planes'], b['stride']
+            x_in = S.d_outs[j - 1] if j else S.d_stem
+            t = ops.conv2d_dgrad(gp, w[i2], b['out'], 3, 3, 1, 1, act_ref=S.d_c1[j], slope=_SLOPE, gain=1.0,
+                                 out=view(Q, b['out']), filters=S.d_filters)
+            gm = ops.conv2d_dgrad(t, w[i1], b['in'], 3, 3, s, 1, out=view(R, b['in']), filters=S.d_filters)
+            gs = gp                                 # identity shortcut: its branch gradient is the join's own
+            if isc is not None:
+                gs = ops.conv2d_dgrad(gp, w[isc], b['in'], 1, 1, s, 0, out=view(Q, b['in']), filters=S.d_filters)
+            gp = ops.cddls_join_bwd(gm, gs, x_in, _SLOPE, out=gm)
+            P, R = R, P
+        ops.rgb_conv_dgrad(gp, w[0], None, 3, 3, act=0, out_scale=2.0, out_shift=0.0, out=S.g_x)
+
+    @staticmethod
+    def regions(S):
+        return [(a > 0).permute(0, 3, 1, 2) for a in S.d_acts]
+
+
+def _d_half(D):
+    from .models.gan.sndcgan import D_SNDCGAN
+    from .models.gan.snresnet import D_SNResNet18
+    if isinstance(D, D_SNDCGAN):
+        return _DHalfSNDCGAN
+    if isinstance(D, D_SNResNet18):
+        return _DHalfSNResNet18
+    return None
+
+
 class CDDLSSampler(object):
-    """Langevin sampler for one batch size on static buffers.  ``G`` / ``D``: eval-mode SNDCGAN modules on the device;
-    ``weight`` / ``bias``: the linear-evaluation head (n_classes, d_penul) / (n_classes,)."""
+    """Langevin sampler for one batch size on static buffers.  ``G`` / ``D``: eval-mode modules on the device (G_SNDCGAN
+    with D_SNDCGAN or D_SNResNet18); ``weight`` / ``bias``: the linear-evaluation head (n_classes, d_penul) / (n_classes,).
+    The G half, the element-wise ends, the noise and the step counter are shared; the D half (prep, buffers, forward,
+    backward, linear regions) is _DHalfSNDCGAN or _DHalfSNResNet18, chosen by the type of ``D``."""
 
     def __init__(self, G, D, weight, bias, n, lbd=1.0, eps=0.01, sigma_n=0.1, seed=0, graph=False, energy=False):
-        from .models.gan.sndcgan import D_SNDCGAN, G_SNDCGAN
-        if not isinstance(G, G_SNDCGAN) or not isinstance(D, D_SNDCGAN):
+        from .models.gan.sndcgan import G_SNDCGAN
+        self.half = _d_half(D)
+        if not isinstance(G, G_SNDCGAN) or self.half is None:
             raise NotImplementedError('cDDLS sampling is implemented for: %s' % ', '.join(IMPLEMENTED))
         if G.training or D.training:
             raise RuntimeError('cDDLS samples from networks in eval mode')
+        self.weight, self.bias = weight.detach(), bias.detach()
+        if tuple(self.weight.shape[1:]) != (D.d_penul,):
+            raise RuntimeError('the linear head reads %d features, D has %d' % (self.weight.shape[1], D.d_penul))
         dev = next(D.parameters()).device
         if dev.type != 'cuda':
             raise RuntimeError('cDDLS sampling runs on the MI355X HIP path only (no CPU fallback)')
@@ -93,11 +311,8 @@ class CDDLSSampler(object):
         self.lbd, self.eps, self.sigma_n, self.seed = float(lbd), float(eps), float(sigma_n), int(seed)
         self.use_graph, self.want_energy = bool(graph), bool(energy)
         self.graph, self.first, self._scratch = None, EagerFirst(), {}
-        self.hb, self.wb = D.s_hb, D.s_wb
-        self.feat, self.dh = 512 * self.hb * self.wb, D.d_hidden
-        self.weight, self.bias = weight.detach(), bias.detach()
-        if tuple(self.weight.shape[1:]) != (self.feat,):
-            raise RuntimeError('the linear head reads %d features, D has %d' % (self.weight.shape[1], self.feat))
+        self.half.geometry(self)
+        self.feat, self.dh, self.d_feat = 512 * self.hb * self.wb, D.d_hidden, D.d_penul     # feat: G's first map, flat
         with torch.no_grad():
             self._prep_d()
             self._prep_g()
@@ -105,31 +320,7 @@ class CDDLSSampler(object):
 
     # ---- constant work ----
     def _prep_d(self):
-        D, dev, N = self.D, self.dev, self.n
-        head = D._head()
-        self.d_layers = [D.main[2 * i] for i in range(7)] + [head.l1, head.l2]
-        T = self.hb * self.wb
-        specs = [ops.SnSpec(m.weight_orig, m.weight_u, m.weight_v) for m in self.d_layers[:7]]
-        specs.append(ops.SnSpec(head.l1.weight_orig, head.l1.weight_u, head.l1.weight_v, view_kct=(self.dh, 512, T)))
-        specs.append(ops.SnSpec(head.l2.weight_orig, head.l2.weight_u, head.l2.weight_v))
-        sizes = [s.T * s.C * s.K for s in specs[:7]] + [self.feat * self.dh, self.dh * 4]
-        self.d_wbuf, v = _flat_views(sizes, dev)
-        self.d_wps = [v[i].view(s.T * s.C, s.K) for i, s in enumerate(specs[:7])]
-        self.d_wps += [v[7].view(self.feat, self.dh), v[8].view(self.dh, 4)]
-        ldws = [s.K for s in specs[:7]] + [self.dh, 4]
-        offs, scr_n = ops.sn_scratch_floats(specs)
-        scratch = torch.empty(scr_n, device=dev, dtype=torch.float32)
-        sigma = torch.empty(len(specs), device=dev, dtype=torch.float32)
-        ops.sn_weight_prep(specs, self.d_wps, ldws, False, scratch, offs, sigma)      # eval: stored u, v, no iteration
-        self.d_filters = None
-        if ops.FILTER_PREP:
-            reqs, hw = [], (8 * self.hb, 8 * self.wb)
-            for i in range(1, 7):
-                ci, co, k, s, p = _D_CONVS[i]
-                d = ops.fwd_desc((N, hw[0], hw[1], ci), self.d_wps[i], co, k, k, s, p)
-                reqs += [(0, d, self.d_wps[i]), (1, d, self.d_wps[i])]
-                hw = (d.Ho, d.Wo)
-            self.d_filters = ops.filter_prep(reqs, dev)
+        self.half.prep(self)
 
     def _prep_g(self):
         G, dev, N = self.G, self.dev, self.n
@@ -163,16 +354,11 @@ class CDDLSSampler(object):
         gshapes = [(N, hb, wb, 512), (N, 2 * hb, 2 * wb, 256), (N, 4 * hb, 4 * wb, 128), (N, H, W, 64)]
         self.g_acts = [buf(*s) for s in gshapes]
         self.g_grads = [buf(*s) for s in gshapes]
-        dshapes, hw = [], (H, W)
-        for ci, co, k, s, p in _D_CONVS:
-            hw = (ops.out_size(hw[0], k, s, p), ops.out_size(hw[1], k, s, p))
-            dshapes.append((N, hw[0], hw[1], co))
-        self.d_acts = [buf(*s) for s in dshapes]
-        self.d_grads = [buf(*s) for s in dshapes]
+        self.half.alloc(self, buf)
         self.hidden, self.g_hidden = buf(N, 1, 1, self.dh), buf(N, 1, 1, self.dh)
         self.logits = buf(N, 1, 1, 1)
         self.neg_one = torch.full((N, 1, 1, 1), -1.0, device=dev)      # d(-(d + lbd l)) / d d
-        self.c_row, self.bias_term = buf(self.feat), buf(1)
+        self.c_row, self.bias_term = buf(self.d_feat), buf(1)
         self.energy = buf(N)
         self.state = torch.zeros(4, dtype=torch.int32, device=dev)      # {step, arrival counter of the latent update}
         self.cls = None
@@ -180,7 +366,7 @@ class CDDLSSampler(object):
     # ---- per class / per batch ----
     def set_class(self, y):
         with torch.no_grad():
-            self.c_row.copy_(permute_class_row(self.weight[y], self.hb, self.wb)).mul_(-self.lbd)
+            self.c_row.copy_(self.half.class_row(self, self.weight[y])).mul_(-self.lbd)
             self.bias_term.copy_(self.bias[y:y + 1]).mul_(-self.lbd)
         self.cls = int(y)
 
@@ -211,29 +397,10 @@ class CDDLSSampler(object):
         ops.rgb_conv_dgrad(self.g_acts[3], w[4], G.main[9].bias, 3, 3, act=1, out_scale=0.5, out_shift=0.5, out=self.gout)
 
     def _d_forward(self):
-        N, w, L = self.n, self.d_wps, self.d_layers
-        ops.rgb_conv_fwd(self.x, w[0], L[0].bias, 64, 3, 2.0, -1.0, _SLOPE, 1.0, out=self.d_acts[0])
-        for i in range(1, 7):
-            ci, co, k, s, p = _D_CONVS[i]
-            ops.conv2d_fwd(self.d_acts[i - 1], w[i], L[i].bias, co, k, k, s, p, _SLOPE, 1.0, out=self.d_acts[i],
-                           filters=self.d_filters)
-        ops.conv2d_fwd(self.d_acts[6].view(N, 1, 1, self.feat), w[7], L[7].bias, self.dh, 1, 1, 1, 0, _SLOPE, 1.0,
-                       out=self.hidden)
-        ops.conv2d_fwd(self.hidden, w[8], L[8].bias, 1, 1, 1, 1, 0, out=self.logits)
+        self.half.forward(self)
 
     def _d_backward(self):
-        N, w = self.n, self.d_wps
-        ops.conv2d_dgrad(self.neg_one, w[8], (N, 1, 1, self.dh), 1, 1, 1, 0, act_ref=self.hidden, slope=_SLOPE, gain=1.0,
-                         out=self.g_hidden)
-        g = self.d_grads[6]
-        ops.conv2d_dgrad(self.g_hidden, w[7], (N, 1, 1, self.feat), 1, 1, 1, 0, out=g.view(N, 1, 1, self.feat))
-        ops.cddls_feature_seed(g, self.c_row, self.d_acts[6], _SLOPE, out=g)
-        for i in range(6, 0, -1):
-            ci, co, k, s, p = _D_CONVS[i]
-            a = self.d_acts[i - 1]
-            g = ops.conv2d_dgrad(g, w[i], tuple(a.shape), k, k, s, p, act_ref=a, slope=_SLOPE, gain=1.0,
-                                 out=self.d_grads[i - 1], filters=self.d_filters)
-        ops.rgb_conv_dgrad(g, w[0], None, 3, 3, act=0, out_scale=2.0, out_shift=0.0, out=self.g_x)
+        self.half.backward(self)
 
     def _g_backward(self):
         G, N, f, w = self.G, self.n, self.feat, self.g_wps
@@ -255,7 +422,7 @@ class CDDLSSampler(object):
             ops.cddls_compose(self.gout, self.z2, self.eps, out=self.x)
             self._d_forward()
             if self.want_energy:
-                ops.cddls_energy(self.logits.view(self.n, 1), self.d_acts[6], self.c_row, self.bias_term, self.z2,
+                ops.cddls_energy(self.logits.view(self.n, 1), self.d_feats, self.c_row, self.bias_term, self.z2,
                                  out=self.energy)
             self._d_backward()
             ops.cddls_image_end(self.g_x, self.gout, self.z2, self.g_lin, self.eps, self.sigma_n, noise=noise2,
@@ -298,12 +465,12 @@ class CDDLSSampler(object):
 
     def linear_region(self):
         """Test hook: the ReLU / LeakyReLU regions the last step ran on, as bool masks in the reference's layouts (G:
-        after norm_init (N, f) NCHW-flat, then three NCHW maps; D: seven NCHW maps; the logit head's hidden (N, dh))."""
+        after norm_init (N, f) NCHW-flat, then three NCHW maps; D: NCHW maps in execution order -- seven for sndcgan, 17
+        for snresnet18 (stem, then conv1 and join of every block); the logit head's hidden (N, dh))."""
         N = self.n
         g = [(self.g_acts[0] > 0).permute(0, 3, 1, 2).reshape(N, self.feat)]
         g += [(a > 0).permute(0, 3, 1, 2) for a in self.g_acts[1:]]
-        d = [(a > 0).permute(0, 3, 1, 2) for a in self.d_acts]
-        return {'g': g, 'd': d, 'hidden': (self.hidden > 0).view(N, self.dh)}
+        return {'g': g, 'd': self.half.regions(self), 'hidden': (self.hidden > 0).view(N, self.dh)}
 
 
 def load_networks(logdir, linear_path, architecture, n_classes, dev):

@@ -2,7 +2,10 @@
 // of one Langevin step that is not a convolution, plus the counter-based normal generator the step draws its noise from.
 //
 //   cddls_feature_seed_kernel      g = (g_head + c) * lrelu'(a6): the gradient entering D's trunk, from the logit head's
-//                                  data gradient and the class row of the linear-evaluation head (one broadcast row)
+//                                  data gradient and the class row of the linear-evaluation head (one broadcast row);
+//                                  two more index forms of the same arithmetic serve the residual D (snresnet18): the
+//                                  pooled seed ((g[n][c] + c[c]) / T over the T pixels of the average pool) and the
+//                                  residual join ((g_main + g_shortcut) * lrelu'(block input), two full tensors)
 //   cddls_bn_relu_bwd_eval_kernel  dx = dy * [y > 0] * gamma / sqrt(running_var + eps): eval-mode BatchNorm + ReLU backward
 //   cddls_compose_kernel           x = G(z) + eps * z2 (optionally clamped to [0, 1]: the final images)
 //   cddls_image_end_kernel         gradient entering G's last transposed conv (through 0.5 tanh + 0.5) and the z2 update
@@ -118,24 +121,83 @@ __global__ __launch_bounds__(CD_THREADS) void cddls_normal_fill_kernel(float* __
   }
 }
 
-__global__ __launch_bounds__(CD_THREADS) void cddls_feature_seed_kernel(const float* g_head,
-                                                                        const float* __restrict__ c_row,
-                                                                        const float* __restrict__ act, float* out,
-                                                                        long long N, int F, float slope) {
-  // F % 4 == 0 and 16-byte aligned rows (checked by the launcher): a quad never straddles two samples
+// The three index forms of the join kernel (the arithmetic is one: (first + second) * lrelu'(act)); `form` is a launch
+// argument, so the branch between them is wave-uniform and each loop keeps its own registers.  Any values and any order of
+// the tests are correct.  These were kept because, with the compiler this was developed on, they put the seed loop right
+// behind the entry block; nothing checks that layout, and that it is worth anything to the ~10 us seed launch is only
+// supposed.
+enum CddlsJoinForm { CD_FORM_JOIN = 0, CD_FORM_POOLED = 1, CD_FORM_SEED = 2 };
+
+__device__ __forceinline__ float4 lrelu_bwd4(const float4 s, const float4 a, float slope) {
+  float4 o;
+  o.x = s.x * (a.x > 0.f ? 1.f : slope);
+  o.y = s.y * (a.y > 0.f ? 1.f : slope);
+  o.z = s.z * (a.z > 0.f ? 1.f : slope);
+  o.w = s.w * (a.w > 0.f ? 1.f : slope);
+  return o;
+}
+
+// seed: act / out (N, F); first g[n][f], second the row c[f]
+__device__ __forceinline__ void join_seed_form(const float* g_head, const float* __restrict__ c_row,
+                                               const float* __restrict__ act, float* out, long long N, int F,
+                                               float slope, long long q0, long long stride) {
   const int fq = F / 4;
   const long long nq = N * fq;
-  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
+  for (long long q = q0; q < nq; q += stride) {
     const int j = (int)(q % fq);
     const float4 g = *reinterpret_cast<const float4*>(g_head + 4 * q);
     const float4 c = *reinterpret_cast<const float4*>(c_row + 4 * j);
     const float4 a = *reinterpret_cast<const float4*>(act + 4 * q);
-    float4 o;
-    o.x = (g.x + c.x) * (a.x > 0.f ? 1.f : slope);
-    o.y = (g.y + c.y) * (a.y > 0.f ? 1.f : slope);
-    o.z = (g.z + c.z) * (a.z > 0.f ? 1.f : slope);
-    o.w = (g.w + c.w) * (a.w > 0.f ? 1.f : slope);
-    *reinterpret_cast<float4*>(out + 4 * q) = o;
+    *reinterpret_cast<float4*>(out + 4 * q) = lrelu_bwd4(make_float4(g.x + c.x, g.y + c.y, g.z + c.z, g.w + c.w), a, slope);
+  }
+}
+
+// pooled seed: act / out (N, T, C) NHWC-flat; first g[n][c] spread over the T pixels of an average pool, second the row c[c]
+__device__ __forceinline__ void join_pooled_form(const float* __restrict__ g, const float* __restrict__ c_row,
+                                                 const float* __restrict__ act, float* __restrict__ out, long long N,
+                                                 int T, int C, float slope, long long q0, long long stride) {
+  const int cq = C / 4;
+  const long long per = (long long)T * cq, nq = N * per;
+  const float inv_T = 1.0f / (float)T;
+  for (long long q = q0; q < nq; q += stride) {
+    const long long n = q / per;
+    const int j = (int)((q - n * per) % cq);
+    const float4 h = *reinterpret_cast<const float4*>(g + 4 * (n * cq + j));
+    const float4 c = *reinterpret_cast<const float4*>(c_row + 4 * j);
+    const float4 a = *reinterpret_cast<const float4*>(act + 4 * q);
+    const float4 s = make_float4((h.x + c.x) * inv_T, (h.y + c.y) * inv_T, (h.z + c.z) * inv_T, (h.w + c.w) * inv_T);
+    *reinterpret_cast<float4*>(out + 4 * q) = lrelu_bwd4(s, a, slope);
+  }
+}
+
+// join: flat tensors of 4 nq floats; first a[i], second b[i]
+__device__ __forceinline__ void join_flat_form(const float* a, const float* __restrict__ b,
+                                               const float* __restrict__ act, float* out, long long nq, float slope,
+                                               long long q0, long long stride) {
+  for (long long q = q0; q < nq; q += stride) {
+    const float4 u = *reinterpret_cast<const float4*>(a + 4 * q);
+    const float4 v = *reinterpret_cast<const float4*>(b + 4 * q);
+    const float4 x = *reinterpret_cast<const float4*>(act + 4 * q);
+    *reinterpret_cast<float4*>(out + 4 * q) = lrelu_bwd4(make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w), x, slope);
+  }
+}
+
+// out may be `first` in the seed and join forms (every quad is read before it is written, by the thread that writes it)
+__global__ __launch_bounds__(CD_THREADS) void cddls_feature_seed_kernel(const float* first,
+                                                                        const float* __restrict__ second,
+                                                                        const float* __restrict__ act, float* out,
+                                                                        long long N, int T, int F, float slope,
+                                                                        int form) {
+  // F % 4 == 0 and 16-byte aligned bases (checked by the launchers): a quad never straddles two rows or two pixels
+  // the launch geometry is read once, ahead of the branch: read inside each form, the block size became a dependent vector
+  // load at the head of every form (0.6 us on the 10.7 us seed launch)
+  const long long q0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+  if (form == CD_FORM_POOLED) {
+    join_pooled_form(first, second, act, out, N, T, F, slope, q0, stride);
+  } else if (form == CD_FORM_SEED) {
+    join_seed_form(first, second, act, out, N, F, slope, q0, stride);
+  } else {
+    join_flat_form(first, second, act, out, N, slope, q0, stride);        // N: the quad count
   }
 }
 
@@ -303,7 +365,27 @@ extern "C" int contrad_cddls_feature_seed(const float* g_head, const float* c_ro
   CONTRAD_ARG(g_head && c_row && act && out && N >= 1 && F >= 4 && (F & 3) == 0);
   CONTRAD_ARG(al16(g_head) && al16(c_row) && al16(act) && al16(out));
   hipLaunchKernelGGL(cddls_feature_seed_kernel, dim3(quad_grid(N * (F / 4))), dim3(CD_THREADS), 0, (hipStream_t)stream,
-                     g_head, c_row, act, out, N, F, slope);
+                     g_head, c_row, act, out, N, 1, F, slope, (int)CD_FORM_SEED);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int contrad_cddls_pooled_seed(const float* g, const float* c_row, const float* act, float* out, long long N,
+                                         int T, int C, float slope, contrad_stream_t stream) {
+  CONTRAD_ARG(g && c_row && act && out && out != g && N >= 1 && T >= 1 && C >= 4 && (C & 3) == 0);
+  CONTRAD_ARG(al16(g) && al16(c_row) && al16(act) && al16(out));
+  hipLaunchKernelGGL(cddls_feature_seed_kernel, dim3(quad_grid(N * T * (C / 4))), dim3(CD_THREADS), 0,
+                     (hipStream_t)stream, g, c_row, act, out, N, T, C, slope, (int)CD_FORM_POOLED);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int contrad_cddls_join_bwd(const float* a, const float* b, const float* act, float* out, long long n,
+                                      float slope, contrad_stream_t stream) {
+  CONTRAD_ARG(a && b && act && out && n >= 1 && (n & 3) == 0);
+  CONTRAD_ARG(al16(a) && al16(b) && al16(act) && al16(out));
+  hipLaunchKernelGGL(cddls_feature_seed_kernel, dim3(quad_grid(n / 4)), dim3(CD_THREADS), 0, (hipStream_t)stream, a, b,
+                     act, out, n / 4, 1, 4, slope, (int)CD_FORM_JOIN);
   CONTRAD_CHECK_LAUNCH();
   return 0;
 }

@@ -835,12 +835,15 @@ def upfirdn2d_fused(x, kernel, up=1, down=1, pad=(0, 0, 0, 0), addend=None, act_
     return out, out2
 
 
-def fused_bias_act(x, bias, ref, act, grad, alpha, scale, channels_last_size=None):
-    """Elementwise on a contiguous tensor whose LAST dim is the channel (NHWC / (M,K))."""
-    _chk(x, 'x'); _chk(bias, 'bias'); _chk(ref, 'ref')
+def fused_bias_act(x, bias, ref, act, grad, alpha, scale, channels_last_size=None, out=None):
+    """Elementwise on a contiguous tensor whose LAST dim is the channel (NHWC / (M,K)).  ``out``: a contiguous tensor of
+    x's size that is not x (static-buffer callers)."""
+    _chk(x, 'x'); _chk(bias, 'bias'); _chk(ref, 'ref'); _chk(out, 'out')
     if not x.is_contiguous() or (ref is not None and not ref.is_contiguous()):
         raise RuntimeError('contrad_hip: fused_bias_act needs contiguous tensors')
-    y = torch.empty_like(x)
+    if out is not None and (not out.is_contiguous() or out.numel() != x.numel() or out.data_ptr() == x.data_ptr()):
+        raise RuntimeError('contrad_hip: fused_bias_act writes a contiguous tensor of x\'s size other than x')
+    y = torch.empty_like(x) if out is None else out
     C = x.shape[-1]
     lib().call('contrad_fused_bias_act', _p(x), _p(bias), _p(ref), _p(y), ctypes.c_longlong(x.numel()), 1, C,
                int(act), int(grad), float(alpha), float(scale), _stream())
@@ -1364,6 +1367,40 @@ def cddls_feature_seed(g_head, c_row, act, slope, out=None):
         raise RuntimeError('contrad_hip: out must match g_head')
     lib().call('contrad_cddls_feature_seed', _p(g_head), _p(c_row), _p(act), _p(out), ctypes.c_longlong(N), F,
                float(slope), _stream())
+    return out
+
+
+def cddls_pooled_seed(g, c_row, act, slope, out=None):
+    """((g + c_row) / T) * lrelu'(act): ``g`` (N, C) is the gradient at a mean over the T pixels of ``act`` (N, ..., C) NHWC;
+    ``out`` (act's shape) must not be ``g``."""
+    _flat_f32(g, 'g'); _flat_f32(c_row, 'c_row'); _flat_f32(act, 'act')
+    C = c_row.numel()
+    N = g.numel() // C
+    if N < 1 or g.numel() != N * C or act.numel() % (N * C):
+        raise RuntimeError('contrad_hip: g must hold N x %d floats and act N x T x %d' % (C, C))
+    T = act.numel() // (N * C)
+    if out is None:
+        out = torch.empty_like(act)
+    _flat_f32(out, 'out')
+    if out.numel() != act.numel():
+        raise RuntimeError('contrad_hip: out must match act')
+    lib().call('contrad_cddls_pooled_seed', _p(g), _p(c_row), _p(act), _p(out), ctypes.c_longlong(N), T, C, float(slope),
+               _stream())
+    return out
+
+
+def cddls_join_bwd(a, b, act, slope, out=None):
+    """(a + b) * lrelu'(act) over equal-size tensors (the backward of a residual join); ``out`` may be ``a``."""
+    _flat_f32(a, 'a'); _flat_f32(b, 'b'); _flat_f32(act, 'act')
+    if b.numel() != a.numel() or act.numel() != a.numel():
+        raise RuntimeError('contrad_hip: a, b and act must have the same size')
+    if out is None:
+        out = torch.empty_like(a)
+    _flat_f32(out, 'out')
+    if out.numel() != a.numel():
+        raise RuntimeError('contrad_hip: out must match a')
+    lib().call('contrad_cddls_join_bwd', _p(a), _p(b), _p(act), _p(out), ctypes.c_longlong(a.numel()), float(slope),
+               _stream())
     return out
 
 

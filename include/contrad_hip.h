@@ -657,6 +657,14 @@ int contrad_cddls_normal_fill(float* out, unsigned* words, long long n, long lon
 /* out[N,F] = (g_head[N,F] + c_row[F]) * (act[N,F] > 0 ? 1 : slope); F % 4 == 0, 16-byte aligned; out may be g_head. */
 int contrad_cddls_feature_seed(const float* g_head, const float* c_row, const float* act, float* out, long long N, int F,
                                float slope, contrad_stream_t stream);
+/* The same kernel on the two index forms of a residual trunk (d = act > 0 ? 1 : slope; 16-byte aligned pointers):
+ * pooled seed  out[N,T,C] = ((g[N,C] + c_row[C]) * (1.0f / T)) * d(act[N,T,C]): the gradient through a mean over T pixels
+ *              (NHWC-flat act / out, C % 4 == 0); out must not be g.
+ * join         out[n] = (a[n] + b[n]) * d(act[n]), n % 4 == 0: the residual join's backward; out may be a. */
+int contrad_cddls_pooled_seed(const float* g, const float* c_row, const float* act, float* out, long long N, int T, int C,
+                              float slope, contrad_stream_t stream);
+int contrad_cddls_join_bwd(const float* a, const float* b, const float* act, float* out, long long n, float slope,
+                           contrad_stream_t stream);
 /* Backward of contrad_bn_relu_apply in eval mode (running statistics are constants):
  * dx[r,c] = dy[r,p(c)] * [y[r,p(c)] > 0] * gamma[c] / sqrt(running_var[c] + eps), with y / dy in the layout the apply
  * kernel wrote (row stride ldy; perm_hw > 1: p(ch * perm_hw + hw) = hw * (K / perm_hw) + ch) and dx in x's (row stride

@@ -7,9 +7,11 @@ configuration per process.
     python tools/bench_cddls.py step             # whole step, host-driven
     python tools/bench_cddls.py step-graph       # whole step, hipGraph replay
     python tools/bench_cddls.py kernels          # 30 eager steps, for `rocprofv3 --kernel-trace --stats -- python tools/bench_cddls.py kernels`
+    python tools/bench_cddls.py dhalf snresnet18 # any mode on G_SNDCGAN + D_SNResNet18 (second argument, default sndcgan)
 
-Times are HIP-event medians over repeated windows with the min - max spread.  The autograd baseline differentiates the
-logit alone (no classifier term): it is a lower bound of what composing the existing modules would cost per step.
+Times are HIP-event medians over repeated windows with the min - max spread.  For sndcgan the autograd baseline
+differentiates the logit alone (no classifier term): it is a lower bound of what composing the existing modules would cost
+per step.  For snresnet18 it is the whole composition: D(x) with the penultimate features, the class logit, backward.
 """
 import os
 import statistics
@@ -43,9 +45,9 @@ def windows(fn, iters=20, reps=9, warm=10):
     return statistics.median(out), min(out), max(out)
 
 
-def networks():
+def networks(arch='sndcgan'):
     torch.manual_seed(0)
-    G, D = get_architecture('sndcgan', (32, 32, 3))
+    G, D = get_architecture(arch, (32, 32, 3))
     G.to(dev); D.to(dev)
     with torch.no_grad():           # fresh u, v are random: a few train-mode passes make them what a checkpoint holds
         D.train()
@@ -74,15 +76,21 @@ def run_length(t_ms):
     return '   default run (10 classes x 2 batches x 1000 steps): %.1f min' % (20000 * t_ms / 60e3)
 
 
-def main(mode):
-    G, D = networks()
+def main(mode, arch='sndcgan'):
+    G, D = networks(arch)
     if mode == 'dhalf-autograd':
         x = torch.rand(BATCH, 3, 32, 32, device=dev).requires_grad_()
+        w_y = 0.01 * torch.randn(D.d_penul, device=dev)
 
         def fn():
             x.grad = None
-            D(x).sum().backward()
-        report('D half, autograd node (weight prep + filter prep + 3 heads), batch %d' % BATCH, windows(fn))
+            if arch == 'sndcgan':
+                D(x).sum().backward()
+            else:
+                d, aux = D(x, penultimate=True)
+                (-(d.view(-1) + aux['penultimate'] @ w_y)).sum().backward()
+        report('D half, autograd %s, batch %d' % ('node (weight prep + filter prep + 3 heads)' if arch == 'sndcgan'
+                                                  else 'composition with the class logit, ' + arch, BATCH), windows(fn))
         return
     S = sampler(G, D, graph=(mode == 'step-graph'))
     if mode in ('dhalf', 'dhalf-graph'):
@@ -94,16 +102,16 @@ def main(mode):
                 S._d_forward()
                 S._d_backward()
         if mode == 'dhalf':
-            report('D half, sampler (forward + input gradient + feature seed), batch %d' % BATCH, windows(fn))
+            report('D half, sampler (forward + input gradient + feature seed), %s, batch %d' % (arch, BATCH), windows(fn))
         else:
             g, scratch = torch.cuda.CUDAGraph(), {}
             with ops.private_workspace(scratch), torch.cuda.graph(g):
                 fn()
             torch.cuda.synchronize()
-            report('D half, sampler, hipGraph replay, batch %d' % BATCH, windows(g.replay))
+            report('D half, sampler, hipGraph replay, %s, batch %d' % (arch, BATCH), windows(g.replay))
     elif mode in ('step', 'step-graph'):
         t = windows(S.step)
-        report('whole step, %s, batch %d' % ('hipGraph replay' if mode == 'step-graph' else 'host-driven', BATCH), t,
+        report('whole step, %s, %s, batch %d' % ('hipGraph replay' if mode == 'step-graph' else 'host-driven', arch, BATCH), t,
                run_length(t[0]))
     elif mode == 'kernels':
         for _ in range(30):
@@ -115,4 +123,4 @@ def main(mode):
 
 
 if __name__ == '__main__':
-    main(sys.argv[1] if len(sys.argv) > 1 else 'step')
+    main(sys.argv[1] if len(sys.argv) > 1 else 'step', sys.argv[2] if len(sys.argv) > 2 else 'sndcgan')
