@@ -334,13 +334,12 @@ class CDDLSSampler(object):
                 d = ops.dgrad_desc((N, H, W, co), self.g_wps[1 + j], ci, k, k, s, p)
                 reqs += [(1, d, self.g_wps[1 + j]), (0, d, self.g_wps[1 + j])]       # forward = dgrad, backward = fwd
             self.g_filters = ops.filter_prep(reqs, dev)
-        # eval-mode BatchNorm through the batch-statistics apply kernel: "one sample" whose sums give mean =
-        # running_mean - conv bias (the transposed conv runs without its bias) and variance = running_var
+        # eval-mode BatchNorm through the as-is form of the apply kernel (ops.bn_relu_apply_eval): mean = running_mean -
+        # conv bias (the transposed conv runs without its bias), made once here; the variance is running_var itself, the
+        # tensor the backward kernel reads, so the step's backward is the derivative of its forward
         self.g_bns = [G.norm_init] + [G.main[3 * j + 1] for j in range(3)]
-        self.g_stats = []
-        for bn, cb in zip(self.g_bns, [None] + [G.main[3 * j].bias for j in range(3)]):
-            mean = bn.running_mean if cb is None else bn.running_mean - cb
-            self.g_stats.append(torch.stack([mean, bn.running_var + mean * mean]).contiguous())
+        self.g_means = [ops.bn_eval_mean(bn, cb).clone()
+                        for bn, cb in zip(self.g_bns, [None] + [G.main[3 * j].bias for j in range(3)])]
 
     def _alloc(self):
         N, dev, hb, wb = self.n, self.dev, self.hb, self.wb
@@ -386,14 +385,14 @@ class CDDLSSampler(object):
         G, N, f, w = self.G, self.n, self.feat, self.g_wps
         ops.conv2d_fwd(self.z.view(N, 1, 1, G.nz), w[0], G.linear.bias, f, 1, 1, 1, 0, out=self.h0.view(N, 1, 1, f))
         bn = self.g_bns[0]
-        ops.bn_relu_apply(self.h0, self.g_acts[0].view(N, f), self.g_stats[0], 1.0, bn.weight, bn.bias, bn.eps,
-                          self.hb * self.wb)
+        ops.bn_relu_apply_eval(self.h0, self.g_acts[0].view(N, f), self.g_means[0], bn.running_var, bn.weight, bn.bias,
+                               bn.eps, self.hb * self.wb)
         for j in range(3):
             ci, co, k, s, p = G._CONVT[j]
             y = self.g_acts[j + 1]
             ops.conv2d_dgrad(self.g_acts[j], w[1 + j], tuple(y.shape), k, k, s, p, out=y, filters=self.g_filters)
             bn, y2 = self.g_bns[j + 1], ops.as_rows(y)
-            ops.bn_relu_apply(y2, y2, self.g_stats[j + 1], 1.0, bn.weight, bn.bias, bn.eps)
+            ops.bn_relu_apply_eval(y2, y2, self.g_means[j + 1], bn.running_var, bn.weight, bn.bias, bn.eps)
         ops.rgb_conv_dgrad(self.g_acts[3], w[4], G.main[9].bias, 3, 3, act=1, out_scale=0.5, out_shift=0.5, out=self.gout)
 
     def _d_forward(self):

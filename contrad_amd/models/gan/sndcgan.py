@@ -514,11 +514,10 @@ class G_SNDCGAN(nn.Module):
     def _bn(self, x2d, bn, conv_bias, out2d, perm_hw=1):
         if not self.training:
             # eval mode (sampling from a checkpoint, train_gan.py:181): the running statistics normalise.  Same apply
-            # kernel, fed with "one sample" whose sum / sum of squares reproduce mean = running_mean - conv bias (x2d is
-            # the transposed conv WITHOUT its bias) and biased variance = running_var
-            mean = bn.running_mean if conv_bias is None else bn.running_mean - conv_bias
-            stats = torch.stack([mean, bn.running_var + mean * mean]).contiguous()
-            ops.bn_relu_apply(x2d, out2d, stats, 1.0, bn.weight, bn.bias, bn.eps, perm_hw)
+            # kernel in its as-is form: mean = running_mean - conv bias (x2d is the transposed conv WITHOUT its bias),
+            # variance = running_var, neither passed through sums
+            ops.bn_relu_apply_eval(x2d, out2d, ops.bn_eval_mean(bn, conv_bias), bn.running_var, bn.weight, bn.bias,
+                                   bn.eps, perm_hw)
             return
         count = float(x2d.shape[0])
         if ops.BN_FUSED and not _sync_on(self.sync_bn):

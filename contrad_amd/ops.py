@@ -665,6 +665,22 @@ def bn_relu_apply(x2d, y2d, stats, count, gamma, beta, eps=1e-5, perm_hw=1):
     return y2d
 
 
+def bn_relu_apply_eval(x2d, y2d, mean, var, gamma, beta, eps=1e-5, perm_hw=1):
+    """Eval-mode BatchNorm + ReLU: ``mean`` (see bn_eval_mean) and ``var`` (the running variance) are used as they are."""
+    M, K = x2d.shape
+    if mean.numel() != K or var.numel() != K:
+        raise RuntimeError('contrad_hip: bn_relu_apply_eval takes one mean and one variance per column')
+    lib().call('contrad_bn_relu_apply_eval', _p(x2d), _p(y2d), ctypes.c_longlong(M), K, _ld(x2d), _ld(y2d), _p(mean),
+               _p(var), _p(gamma), _p(beta), float(eps), int(perm_hw), _stream())
+    return y2d
+
+
+def bn_eval_mean(bn, conv_bias=None):
+    """The mean an eval-mode BatchNorm subtracts from the output of a layer that ran WITHOUT its bias: running_mean -
+    conv bias, rounded once per channel (shared by G_SNDCGAN._bn and CDDLSSampler._prep_g)."""
+    return bn.running_mean if conv_bias is None else bn.running_mean - conv_bias
+
+
 def bn_running_update(stats, count, conv_bias, momentum, running_mean, running_var, num_batches_tracked=None):
     K = running_mean.numel()
     if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or not num_batches_tracked.is_cuda):

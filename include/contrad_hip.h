@@ -358,6 +358,12 @@ int contrad_colstats(const float* x, long long M, int K, int ld, int with_sq, fl
 int contrad_bn_relu_apply(const float* x, float* y, long long M, int K, int ldx, int ldy, const float* stats,
                           float count, const float* gamma, const float* beta, float eps, int perm_hw,
                           contrad_stream_t stream);
+/* The same in eval mode (G_SNDCGAN sampling from a checkpoint, cDDLS): mean[K] (running_mean minus the bias of the
+ * producing layer when that layer ran without it) and var[K] (running_var) are used as they are, by the same kernel:
+ * y = relu((x - mean) * rsqrt(var + eps) * gamma + beta).  -EINVAL on bad arguments before any GPU call. */
+int contrad_bn_relu_apply_eval(const float* x, float* y, long long M, int K, int ldx, int ldy, const float* mean,
+                               const float* var, const float* gamma, const float* beta, float eps, int perm_hw,
+                               contrad_stream_t stream);
 /* Backward of BatchNorm(train)+ReLU: out2k = {S1[c] = sum dyM, S2[c] = sum dyM*xhat} (dyM = dy*[bn(x) > 0]);
  * for SyncBatchNorm all-reduce out2k and use the global count; then dx = gamma*rstd*(dyM - S1/n - xhat*S2/n).
  * d gamma = S2, d beta = S1.  `x` is the pre-normalisation activation, `stats` the forward {sum, sumsq}. */

@@ -80,13 +80,17 @@ def normals64(n, seed, stream, step):
 
 
 # ---- the networks in eval mode ----
-def g_eval_forward(sd, z, image_hw=32, masks=None):
+def g_eval_forward(sd, z, image_hw=32, masks=None, acts=None):
     """G_SNDCGAN in eval mode (== O.sndcgan_g_forward(training=False) without masks); ``masks``: four bool tensors, the
-    ReLU regions after norm_init ((N, f)) and after the three BatchNorms (NCHW), imposed instead of sign(pre-act)."""
+    ReLU regions after norm_init ((N, f)) and after the three BatchNorms (NCHW), imposed instead of sign(pre-act).
+    ``acts``: a list that receives the four post-ReLU activations (NCHW)."""
     hb = image_hw // 8
 
     def relu(h, m):
-        return F.relu(h) if m is None else h * m.to(h.dtype)
+        h = F.relu(h) if m is None else h * m.to(h.dtype)
+        if acts is not None:
+            acts.append(h.view(h.size(0), 512, hb, hb) if h.dim() == 2 else h)
+        return h
 
     def bn(prefix, h):
         return F.batch_norm(h, sd[prefix + '.running_mean'], sd[prefix + '.running_var'], sd[prefix + '.weight'],
@@ -151,6 +155,35 @@ def fixture_networks(image_hw=32):
             for _ in range(POWER_ITERATIONS):
                 O.spectral_norm_weight(dsd, k[:-len('.weight_orig')], training=True)
     return gsd, dsd
+
+
+def trained_like_networks(bias_shift=1.0, image_hw=16, n_latents=64):
+    """fixture_networks with a generator whose BatchNorm state looks like a trained one's: linear.weight x 0.2 and
+    linear.bias + ``bias_shift`` (channels whose mean is far above their spread), and every running mean / variance set to
+    the float64 population statistics of this generator's own pre-BatchNorm activations over ``n_latents`` latents, layer
+    by layer, rounded to float32 (what a checkpoint stores).  -> (gsd, dsd), float64 copies of the float32 values."""
+    gsd, dsd = fixture_networks(image_hw)
+    gsd['linear.weight'] = (gsd['linear.weight'] * 0.2).float().double()
+    gsd['linear.bias'] = (gsd['linear.bias'] + bias_shift).float().double()
+    z = (torch.rand(n_latents, 128, generator=torch.Generator().manual_seed(64), dtype=torch.float64) * 2 - 1)
+    hb = image_hw // 8
+
+    def settle(prefix, h):              # h: pre-BN activation, channels in dim 1
+        dims = [d for d in range(h.dim()) if d != 1]
+        gsd[prefix + '.running_mean'] = h.mean(dims).float().double()
+        gsd[prefix + '.running_var'] = h.var(dims, unbiased=False).float().double()
+        return F.relu(F.batch_norm(h, gsd[prefix + '.running_mean'], gsd[prefix + '.running_var'], gsd[prefix + '.weight'],
+                                   gsd[prefix + '.bias'], False, 0.1, 1e-5))
+    h = settle('norm_init', F.linear(z, gsd['linear.weight'], gsd['linear.bias'])).view(-1, 512, hb, hb)
+    for j, (ci, co, k, s, p) in enumerate(O.SNDCGAN_G_CONVT[:3]):
+        h = settle('main.%d' % (3 * j + 1),
+                   F.conv_transpose2d(h, gsd['main.%d.weight' % (3 * j)], gsd['main.%d.bias' % (3 * j)], stride=s, padding=p))
+    return gsd, dsd
+
+
+def bn_state_ratio(gsd, prefix):
+    """max over channels of running_mean^2 / running_var of one BatchNorm of a state dict."""
+    return float((gsd[prefix + '.running_mean'] ** 2 / gsd[prefix + '.running_var']).max())
 
 
 # ---- the fixture (tests/golden/cddls.npz) ----

@@ -157,6 +157,89 @@ def bn_relu_bwd(dy2d, x2d, gamma, beta, eps, mask=None):
     return gamma * rstd * (g - s1 / M - xh * s2 / M), s2, s1
 
 
+def bn_relu_eval(x2d, conv_bias, running_mean, running_var, gamma, beta, eps, perm_hw=1):
+    """Eval-mode BatchNorm + ReLU on (M, K) rows of a layer that ran without its bias ``conv_bias`` (None: no bias):
+    relu(((x + cb) - rm) / sqrt(rv + eps) * gamma + beta); the output column permutation is that of bn_relu."""
+    x = _d(x2d)
+    if conv_bias is not None:
+        x = x + _d(conv_bias)
+    y = ((x - _d(running_mean)) / torch.sqrt(_d(running_var) + eps) * _d(gamma) + _d(beta)).clamp_min(0)
+    if perm_hw > 1:
+        M, K = y.shape
+        y = y.reshape(M, K // perm_hw, perm_hw).transpose(1, 2).reshape(M, K)
+    return y
+
+
+# Regimes of eval-mode statistics: (scale of |running_mean - conv_bias|, scale of running_var, the max over 128 channels of
+# mean^2 / var the draw below is meant to reach).  |mean| is scale * U(0.5, 1.5) with a random sign (A: 0.1 * randn, as
+# O.det_fill draws it), var is scale * U(0.5, 2), so the largest ratio is about 2.8 scale_m^2 / scale_v.
+BN_EVAL_REGIMES = {
+    'A': (0.1, 1.0, 0.13),          # today's fixtures
+    'B': (10.0, 1.0, 2.8e2),
+    'C': (1.0, 1e-4, 2.8e4),
+    'D': (10.0, 1e-4, 2.8e6),
+    'E': (1.0, 1e-8, 2.8e8),        # var below one ulp of mean^2, and below eps
+    'F': (1.0, None, 2.8e12),       # var exactly 0 / 1e-12 / 1e-4 by channel % 3; the ratio is over the channels with var > 0
+    'G': (1.0, 1.0, 2.8),           # running_mean and conv_bias both near 100, their difference near 1
+}
+BN_EVAL_NEEDS_BIAS = ('G',)
+
+
+def bn_eval_inputs(regime, M, K, seed, with_bias=True, device='cpu'):
+    """-> dict(x (M, K), rm, rv, cb (or None), gamma, beta), all float32 on ``device``: x = (rm - cb) + sqrt(rv) * randn
+    formed in float64 from the ROUNDED statistics and rounded once.  Drawn on the CPU generator: the same values on every
+    device."""
+    ms, vs, _ = BN_EVAL_REGIMES[regime]
+    assert with_bias or regime not in BN_EVAL_NEEDS_BIAS
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.rand(*s, generator=g, dtype=f64)
+    n = lambda *s: torch.randn(*s, generator=g, dtype=f64)
+    sign = torch.where(r(K) < 0.5, -1.0, 1.0).to(f64)
+    mean = 0.1 * n(K) if regime == 'A' else ms * (0.5 + r(K)) * sign
+    if regime == 'F':
+        rv = torch.tensor([0.0, 1e-12, 1e-4], dtype=f64)[torch.arange(K) % 3]
+        r(K)
+    else:
+        rv = vs * (0.5 + 1.5 * r(K))
+    cb = (100.0 + n(K)) if regime == 'G' else 0.1 * n(K)
+    gamma, beta, z = r(K) + 0.5, 0.3 * n(K), n(M, K)
+    cb = cb.float() if with_bias else None
+    rm = (mean + (cb.double() if with_bias else 0)).float()
+    rv = rv.float()
+    x = (rm.double() - (cb.double() if with_bias else 0)) + torch.sqrt(rv.double()) * z
+    out = dict(x=x.float(), rm=rm, rv=rv, cb=cb, gamma=gamma.float(), beta=beta.float())
+    return {k: (None if v is None else v.to(device)) for k, v in out.items()}
+
+
+def bn_eval_ratio(inp):
+    """max over channels (with var > 0) of (rm - cb)^2 / rv."""
+    mean = _d(inp['rm']) - (0 if inp['cb'] is None else _d(inp['cb']))
+    rv = _d(inp['rv'])
+    return float((mean * mean / rv)[rv > 0].max())
+
+
+def bn_relu_eval_fp32(inp, eps, perm_hw=1):
+    """Plain fp32 torch on the same tensors, on their device: F.relu(F.batch_norm(x + cb, rm, rv, gamma, beta)) -- the
+    yardstick's own fp32 error sets the bound of the kernel (see bn_eval_bound)."""
+    x = inp['x'].contiguous()
+    if inp['cb'] is not None:
+        x = x + inp['cb']
+    y = F.relu(F.batch_norm(x, inp['rm'], inp['rv'], inp['gamma'], inp['beta'], False, 0.0, eps))
+    if perm_hw > 1:
+        M, K = y.shape
+        y = y.reshape(M, K // perm_hw, perm_hw).transpose(1, 2).reshape(M, K)
+    return y
+
+
+def bn_eval_bound(family_tol, torch_errors, regime=None):
+    """(max-norm, rel-L2) bounds of an eval BatchNorm output: max(the bn_fwd family bound, 2 x the error of plain fp32 torch
+    on the same inputs).  The factor 2 covers the different rounding order (rsqrt against sqrt and divide; rm - cb rounded
+    once per channel against x + cb rounded per element).  Regime A is held to the family bound alone."""
+    if regime == 'A':
+        return tuple(family_tol)
+    return tuple(max(t, 2.0 * e) for t, e in zip(family_tol, torch_errors))
+
+
 def bn_running(running_mean, running_var, x2d, conv_bias, momentum):
     """nn.BatchNorm's running update from the batch of the conv output WITHOUT its bias (folded in here)."""
     x = _d(x2d)

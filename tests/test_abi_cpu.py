@@ -41,6 +41,19 @@ def test_argument_errors_are_reported_without_gpu(built):
     assert built.raw('contrad_conv2d_wgrad_workspace_bytes')(ctypes.byref(d)) >= 3 * 3 * 4 * 8 * 4
 
 
+def test_bn_relu_apply_eval_refuses_bad_arguments_without_gpu(built):
+    """contrad_bn_relu_apply_eval (the eval-mode form of the BatchNorm apply kernel) returns -EINVAL before any GPU call."""
+    fn = built.raw('contrad_bn_relu_apply_eval')
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    good = [p, p, ctypes.c_longlong(4), 8, 8, 8, p, p, p, p, 1e-5, 1, None]
+    for i, bad in ((0, None), (1, None), (6, None), (7, None), (8, None), (9, None), (2, ctypes.c_longlong(0)), (3, 0),
+                   (4, 7), (5, 7), (10, -1.0), (11, 0), (11, 3)):
+        args = list(good)
+        args[i] = bad
+        assert fn(*args) == -22, (i, bad)
+
+
 def _desc(N, H, C, K, k, s, p):
     Ho = (H + 2 * p - k) // s + 1
     return _lib.ConvDesc(N, H, H, C, C, Ho, Ho, K, K, k, k, s, p, (K + 3) // 4 * 4)

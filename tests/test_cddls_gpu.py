@@ -250,6 +250,91 @@ def test_one_step(margin, nets, N):
     assert int(S.state[0]) == 1 and int(S.state[1]) == 0
 
 
+_TRAINED_LIKE = {}
+
+
+def trained_like(shift):
+    """R.trained_like_networks(shift) at 16 x 16 images: norm_init with mean^2 / var up to 3.8e3 (shift 1) or 3.3e4 (shift 3)
+    and running variances of 3e-4 .. 1e-3, as float64 state dicts and as eval-mode modules on the device."""
+    if shift not in _TRAINED_LIKE:
+        from contrad_amd.models.gan import get_architecture
+        gsd, dsd = R.trained_like_networks(shift, 16)
+        G, D = get_architecture('sndcgan', (16, 16, 3))
+        full = dict(G.state_dict())
+        full.update({k: v.float() for k, v in gsd.items()})
+        G.load_state_dict(full)
+        D.load_state_dict({k: v.float() for k, v in dsd.items()})
+        G.to(dev()).eval(); D.to(dev()).eval()
+        for p in list(G.parameters()) + list(D.parameters()):
+            p.requires_grad_(False)
+        _TRAINED_LIKE[shift] = (gsd, dsd, G, D)
+    return _TRAINED_LIKE[shift]
+
+
+@pytest.mark.parametrize('shift', [1.0, 3.0])
+def test_g_forward_on_a_trained_like_state(margin, shift):
+    """The sampler's norm_init output at N = 3 against float64, end to end from z and on the kernel's own input (h0), each
+    under the rule of test_dstep_kernels_gpu.test_bn_relu_eval: max(FAMILY_TOL['bn_fwd'], 2 x the error of plain fp32 torch
+    on the same device tensors)."""
+    import torch.nn.functional as F
+    import dstep_ref64 as K
+    from contrad_amd.cddls import CDDLSSampler
+    BN_FWD = (1.3e-6, 7e-7)             # FAMILY_TOL['bn_fwd'] of test_dstep_kernels_gpu.py
+    gsd, dsd, G, D = trained_like(shift)
+    N, g = 3, gen(int(shift))
+    W, b = 0.05 * torch.randn(10, 2048, generator=g), 0.1 * torch.randn(10, generator=g)
+    z = (torch.rand(N, 128, generator=g) * 2 - 1).to(dev())
+    S = CDDLSSampler(G, D, W.to(dev()), b.to(dev()), N)
+    S.set_class(1)
+    S.start(z)
+    S._g_forward()
+    got = S.g_acts[0].permute(0, 3, 1, 2)                    # NHWC -> NCHW
+    bn = G.norm_init
+    sd32 = {k: v.to(dev()) for k, v in G.state_dict().items()}
+    sd64 = {k: v.double() for k, v in sd32.items()}
+    tag = 'cddls g_forward trained-like state +%g norm_init ' % shift
+    # end to end from z
+    a64, a32 = [], []
+    R.g_eval_forward(sd64, z.double(), 16, acts=a64)
+    R.g_eval_forward(sd32, z, 16, acts=a32)
+    bound = K.bn_eval_bound(BN_FWD, K.errors(a32[0], a64[0]))
+    emax, el2 = K.errors(got, a64[0])
+    margin(tag + 'from z max-norm', emax, bound[0])
+    margin(tag + 'from z rel-L2', el2, bound[1])
+    # the BatchNorm alone, on the fp32 linear output the kernel read
+    inp = dict(x=S.h0, cb=None, rm=bn.running_mean, rv=bn.running_var, gamma=bn.weight, beta=bn.bias)
+    ref = K.bn_relu_eval(S.h0, None, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, 4)
+    bound = K.bn_eval_bound(BN_FWD, K.errors(K.bn_relu_eval_fp32(inp, bn.eps, 4), ref))
+    emax, el2 = K.errors(S.g_acts[0].view(N, -1), ref)
+    margin(tag + 'from h0 max-norm', emax, bound[0])
+    margin(tag + 'from h0 rel-L2', el2, bound[1])
+    assert float(ref.max()) > 1.0 and F.relu(ref).count_nonzero() > ref.numel() // 4
+
+
+def test_one_step_on_a_trained_like_state(margin):
+    """test_one_step on the first trained-like state (16 x 16, N = 3): the running variances of 3e-4 .. 1e-3 scale the backward
+    by up to 60 x per layer; g_z, g_x and the energy on the kernel's own linear region at the unchanged TOL."""
+    from contrad_amd.cddls import CDDLSSampler
+    gsd, dsd, G, D = trained_like(1.0)
+    N, g = 3, gen(103)
+    W, b = 0.05 * torch.randn(10, 2048, generator=g), 0.1 * torch.randn(10, generator=g)
+    z0, z2_0 = torch.rand(N, 128, generator=g) * 2 - 1, torch.randn(N, 3, 16, 16, generator=g)
+    n, n2 = torch.randn(N, 128, generator=g), torch.randn(N, 3, 16, 16, generator=g)
+    y = 4
+    S = CDDLSSampler(G, D, W.to(dev()), b.to(dev()), N, lbd=LBD, eps=EPS, sigma_n=SIGMA_N, energy=True)
+    S.set_class(y)
+    S.start(z0.to(dev()), z2=z2_0.to(dev()))
+    S.step(noise=n.to(dev()), noise2=n2.to(dev()))
+    region = cpu_region(S.linear_region())
+    same = R.langevin_step(gsd, dsd, W[y].double(), b[y].double(), z0.double(), z2_0.double(), n.double(), n2.double(), EPS,
+                           LBD, SIGMA_N, image_hw=16, region=region)
+    tag = 'cddls step trained-like state N=%d ' % N
+    margin(tag + 'g_z same region', rel_l2(S.g_z, same['g_z']), TOL)
+    margin(tag + 'g_x same region', rel_l2(S.g_x, same['g_x']), TOL)
+    margin(tag + 'energy same region', float(((S.energy.double().cpu() - same['e']).abs() / same['e'].abs()).max()), TOL)
+    assert int(S.state[0]) == 1 and float(same['g_z'].abs().max()) > 0
+
+
 @pytest.mark.parametrize('yi', [0, 1])
 def test_trajectory_against_reference(margin, nets, fx, yi):
     """Three steps on the reference's recorded draws: increments of z and z2 and the final images against ref64 on the

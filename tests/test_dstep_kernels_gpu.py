@@ -560,6 +560,87 @@ def test_bn_offset_cost(margin):
         margin('dstep bn_fwd offset %5.0f x std (max-norm, observed only)' % offset, emax, float('inf'))
 
 
+# ---- eval mode: running statistics as they are (contrad_bn_relu_apply_eval) ----
+# (M, K, ld, perm_hw, what)
+BN_EVAL_SHAPES = [
+    (5, 8192, 8192, 16, 'norm_init at 32x32'),
+    (3, 2048, 2048, 4, 'norm_init at 16x16'),
+    (768, 128, 128, 1, 'the 16x16 BN of three images; also in place, as CDDLSSampler._g_forward calls it'),
+    (33, 64, 66, 1, 'ld != K'),
+    (7, 6, 7, 1, 'odd stride'),
+    (2000, 64, 64, 1, 'more than one block'),
+]
+# The bound of each case is R.bn_eval_bound: max(FAMILY_TOL['bn_fwd'], 2 x the error of plain fp32 torch on the same device
+# tensors); regime A is held to FAMILY_TOL['bn_fwd'] alone.  Observed worst on an MI355X over BN_EVAL_SHAPES, with and
+# without conv bias (profiles/bn_eval.txt):
+BN_EVAL_OBSERVED = {            # regime: kernel (max-norm, rel-L2)      fp32 torch (max-norm, rel-L2); the parent commit's form
+    'A': (1.1e-7, 5.9e-8),      # 1.4e-7, 5.9e-8; 1.1e-7, 5.9e-8
+    'B': (4.4e-7, 4.3e-7),      # 4.6e-7, 4.4e-7; 7.3e-6, 2.3e-6
+    'C': (2.9e-6, 2.8e-6),      # 2.6e-6, 2.8e-6; 9.0e-4, 2.7e-4
+    'D': (2.7e-5, 3.4e-5),      # 2.7e-5, 3.4e-5; 9.1e-2, 2.0e-2
+    'E': (3.1e-5, 4.1e-5),      # 2.9e-5, 4.1e-5; 6.7e-4, 2.4e-4
+    'F': (1.0e-5, 1.8e-5),      # 1.0e-5, 1.8e-5; 5.8e-4, 2.3e-4
+    'G': (1.3e-7, 4.9e-8),      # 2.0e-6, 2.1e-6; 1.6e-7, 6.4e-8
+}
+
+
+@pytest.mark.parametrize('regime', list(R.BN_EVAL_REGIMES))
+@pytest.mark.parametrize('shape', BN_EVAL_SHAPES, ids=lambda c: 'M%d-K%d-ld%d-p%d' % c[:4])
+def test_bn_relu_eval(margin, shape, regime):
+    """Eval-mode BatchNorm + ReLU at the statistics of a trained generator (regimes of tests/dstep_ref64.py: mean^2 / var from
+    0.1 to 3e8, var = 0, running_mean and conv bias that cancel) against float64."""
+    import types
+    M, K, ld, perm, _ = shape
+    eps = 1e-5
+    for with_bias in (True, False):
+        if not with_bias and regime in R.BN_EVAL_NEEDS_BIAS:
+            continue
+        inp = R.bn_eval_inputs(regime, M, K, M + K + ord(regime), with_bias, DEV)
+        inp['x'] = x = strided(inp['x'], ld)
+        y_ref = R.bn_relu_eval(x, inp['cb'], inp['rm'], inp['rv'], inp['gamma'], inp['beta'], eps, perm)
+        e_torch = R.errors(R.bn_relu_eval_fp32(inp, eps, perm), y_ref)
+        gm, mean = flat((K,), fill=ops.bn_eval_mean(types.SimpleNamespace(running_mean=inp['rm']), inp['cb']))
+        gv, var = flat((K,), fill=inp['rv'])
+        gg, gamma = flat((K,), fill=inp['gamma'])
+        gb, beta = flat((K,), fill=inp['beta'])
+        gy = Guard(M, K, ld=ld + 4, c0=4)
+        ops.bn_relu_apply_eval(x, gy.view, mean, var, gamma, beta, eps, perm)
+        outs = [('', gy)]
+        if perm == 1 and M == 768:
+            gx = Guard(M, K, ld=ld + 4, c0=4)
+            gx.view.copy_(x)
+            ops.bn_relu_apply_eval(gx.view, gx.view, mean, var, gamma, beta, eps, 1)
+            outs.append((' in place', gx))
+        torch.cuda.synchronize()
+        assert gm.intact() and gv.intact() and gg.intact() and gb.intact()
+        tmax, tl2 = R.bn_eval_bound(FAMILY_TOL['bn_fwd'], e_torch, regime)
+        margin('dstep bn_eval regime %s fp32 torch max-norm (observed only)' % regime, e_torch[0], float('inf'))
+        margin('dstep bn_eval regime %s fp32 torch rel-L2 (observed only)' % regime, e_torch[1], float('inf'))
+        for tag, g in outs:
+            what = 'regime %s M=%d K=%d ld=%d perm=%d bias=%d%s' % (regime, M, K, ld, perm, with_bias, tag)
+            assert g.intact(), what
+            emax, el2 = R.errors(g.view, y_ref)
+            print('bn_eval %s: kernel %.2e / %.2e, fp32 torch %.2e / %.2e' % ((what, emax, el2) + e_torch))
+            assert emax < CONTRACT, (what, emax)
+            margin('dstep bn_eval regime %s max-norm' % regime, emax, tmax)
+            margin('dstep bn_eval regime %s rel-L2' % regime, el2, tl2)
+        if len(outs) == 2:
+            assert torch.equal(outs[0][1].view, outs[1][1].view)
+
+
+def test_bn_relu_apply_eval_rejects_bad_arguments():
+    x = torch.zeros(4, 8, device=DEV)
+    k = torch.ones(8, device=DEV)
+    good = [P(x), P(x), ctypes.c_longlong(4), 8, 8, 8, P(k), P(k), P(k), P(k), 1e-5, 1, ops._stream()]
+    call('contrad_bn_relu_apply_eval', *good)
+    for i, bad in ((0, None), (1, None), (6, None), (7, None), (8, None), (9, None), (2, ctypes.c_longlong(0)), (3, 0),
+                   (4, 7), (5, 7), (10, -1.0), (11, 0), (11, 3)):
+        args = list(good)
+        args[i] = bad
+        with pytest.raises(RuntimeError, match='status -22'):
+            call('contrad_bn_relu_apply_eval', *args)
+
+
 # ======================================================================================================================
 # elementwise.hip: GAN losses
 # ======================================================================================================================

@@ -316,3 +316,42 @@ def test_generator_eval_mode_forward_matches_reference(golden):
     with torch.no_grad():
         img_t = G(torch.from_numpy(g['z']).to(DEV))
     assert rel(img_t, g['img']) > 1e-2                       # (batch statistics give a different image)
+
+
+@pytest.mark.parametrize('shift', [1.0, 3.0])
+def test_generator_eval_mode_on_a_trained_like_state(margin, shift):
+    """G.eval()(z) at N = 4, 16 x 16, on a state whose norm_init has mean^2 / var up to 3.8e3 / 3.3e4 and running variances
+    of 3e-4 .. 1e-3 (tests/cddls_ref64.py: trained_like_networks) against the float64 generator: below TOL, and below twice
+    the error of the same function in fp32 torch on the device -- with a floor, the largest family bound
+    test_conv_paths_gpu.py gives for the paths the three transposed convs plan at this batch, since the image passes
+    through them."""
+    import ctypes
+    import cddls_ref64 as C
+    from contrad_amd import ops
+    from contrad_amd._lib import lib
+    from test_conv_paths_gpu import FAMILY_TOL as CONV_TOL
+    gsd, _ = C.trained_like_networks(shift, 16)
+    G, _ = get_architecture('sndcgan', (16, 16, 3))
+    full = dict(G.state_dict())
+    full.update({k: v.float() for k, v in gsd.items()})
+    G.load_state_dict(full)
+    G = G.to(DEV).eval()
+    N = 4
+    z = (torch.rand(N, 128, generator=torch.Generator().manual_seed(int(shift))) * 2 - 1).to(DEV)
+    with torch.no_grad():
+        img = G(z)
+        sd32 = {k: v.to(DEV) for k, v in G.state_dict().items()}
+        ref = C.g_eval_forward({k: v.double() for k, v in sd32.items()}, z.double(), 16)
+        e_torch = rel(C.g_eval_forward(sd32, z, 16), ref)
+        wps, H, paths = G._weights(), 2, []
+        for j in range(3):
+            ci, co, k, s, p = G._CONVT[j]
+            H *= 2
+            paths.append(lib().raw('contrad_conv2d_path')(ctypes.byref(ops.dgrad_desc((N, H, H, co), wps[1 + j], ci, k, k, s, p)), 1))
+    floor = max(CONV_TOL[p][0] for p in paths)
+    err = rel(img, ref)
+    tag = 'sndcgan eval trained-like state +%g image max-norm ' % shift
+    margin(tag + 'against TOL', err, TOL)
+    margin(tag + 'of fp32 torch (observed only)', e_torch, float('inf'))
+    margin(tag + 'against max(2 x fp32 torch, conv paths %s)' % paths, err, max(floor, 2 * e_torch))
+    assert float(ref.std()) > 1e-3          # (an image, not a constant)
