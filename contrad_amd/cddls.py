@@ -80,7 +80,9 @@ def permute_class_row(w_row, hb, wb):
 
 class _DHalfSNDCGAN(object):
     """The D half of a Langevin step on D_SNDCGAN: seven plain convs, the logit head on the 8192 NHWC-flat features.
-    Stateless: everything it prepares lives on the sampler ``S``."""
+    Stateless: everything it prepares lives on the sampler ``S``.  ``forward`` / ``backward`` are the sampler's; latent
+    recovery (recover.py) runs the trunk alone (``prep(S, head=False)``, ``forward_trunk``, ``seed_rows``,
+    ``backward_trunk``) and never touches the logit head."""
 
     @staticmethod
     def geometry(S):
@@ -91,19 +93,24 @@ class _DHalfSNDCGAN(object):
         return permute_class_row(w_row, S.hb, S.wb)
 
     @staticmethod
-    def prep(S):
+    def prep(S, head=True):
         D, dev, N = S.D, S.dev, S.n
-        head = D._head()
-        S.d_layers = [D.main[2 * i] for i in range(7)] + [head.l1, head.l2]
+        S.d_layers = [D.main[2 * i] for i in range(7)]
         T = S.hb * S.wb
         specs = [ops.SnSpec(m.weight_orig, m.weight_u, m.weight_v) for m in S.d_layers[:7]]
-        specs.append(ops.SnSpec(head.l1.weight_orig, head.l1.weight_u, head.l1.weight_v, view_kct=(S.dh, 512, T)))
-        specs.append(ops.SnSpec(head.l2.weight_orig, head.l2.weight_u, head.l2.weight_v))
-        sizes = [s.T * s.C * s.K for s in specs[:7]] + [S.feat * S.dh, S.dh * 4]
+        sizes = [s.T * s.C * s.K for s in specs[:7]]
+        ldws = [s.K for s in specs[:7]]
+        if head:
+            h = D._head()
+            S.d_layers += [h.l1, h.l2]
+            specs.append(ops.SnSpec(h.l1.weight_orig, h.l1.weight_u, h.l1.weight_v, view_kct=(S.dh, 512, T)))
+            specs.append(ops.SnSpec(h.l2.weight_orig, h.l2.weight_u, h.l2.weight_v))
+            sizes += [S.feat * S.dh, S.dh * 4]
+            ldws += [S.dh, 4]
         S.d_wbuf, v = _flat_views(sizes, dev)
         S.d_wps = [v[i].view(s.T * s.C, s.K) for i, s in enumerate(specs[:7])]
-        S.d_wps += [v[7].view(S.feat, S.dh), v[8].view(S.dh, 4)]
-        ldws = [s.K for s in specs[:7]] + [S.dh, 4]
+        if head:
+            S.d_wps += [v[7].view(S.feat, S.dh), v[8].view(S.dh, 4)]
         offs, scr_n = ops.sn_scratch_floats(specs)
         scratch = torch.empty(scr_n, device=dev, dtype=torch.float32)
         sigma = torch.empty(len(specs), device=dev, dtype=torch.float32)
@@ -129,13 +136,18 @@ class _DHalfSNDCGAN(object):
         S.d_feats = S.d_acts[6]                     # the penultimate features, (N, hb, wb, 512) NHWC
 
     @staticmethod
-    def forward(S):
-        N, w, L = S.n, S.d_wps, S.d_layers
+    def forward_trunk(S):
+        w, L = S.d_wps, S.d_layers
         ops.rgb_conv_fwd(S.x, w[0], L[0].bias, 64, 3, 2.0, -1.0, _SLOPE, 1.0, out=S.d_acts[0])
         for i in range(1, 7):
             ci, co, k, s, p = _D_CONVS[i]
             ops.conv2d_fwd(S.d_acts[i - 1], w[i], L[i].bias, co, k, k, s, p, _SLOPE, 1.0, out=S.d_acts[i],
                            filters=S.d_filters)
+
+    @staticmethod
+    def forward(S):
+        N, w, L = S.n, S.d_wps, S.d_layers
+        _DHalfSNDCGAN.forward_trunk(S)
         ops.conv2d_fwd(S.d_acts[6].view(N, 1, 1, S.feat), w[7], L[7].bias, S.dh, 1, 1, 1, 0, _SLOPE, 1.0,
                        out=S.hidden)
         ops.conv2d_fwd(S.hidden, w[8], L[8].bias, 1, 1, 1, 1, 0, out=S.logits)
@@ -148,6 +160,16 @@ class _DHalfSNDCGAN(object):
         g = S.d_grads[6]
         ops.conv2d_dgrad(S.g_hidden, w[7], (N, 1, 1, S.feat), 1, 1, 1, 0, out=g.view(N, 1, 1, S.feat))
         ops.cddls_feature_seed(g, S.c_row, S.d_acts[6], _SLOPE, out=g)
+        _DHalfSNDCGAN.backward_trunk(S, g)
+
+    @staticmethod
+    def seed_rows(S, rows, zero_row):
+        """The trunk gradient seeded from per-sample rows at the features (N, feat): rows * lrelu'(a6)."""
+        return ops.cddls_feature_seed(rows, zero_row, S.d_acts[6], _SLOPE, out=S.d_grads[6])
+
+    @staticmethod
+    def backward_trunk(S, g):
+        w = S.d_wps
         for i in range(6, 0, -1):
             ci, co, k, s, p = _D_CONVS[i]
             a = S.d_acts[i - 1]
@@ -180,9 +202,8 @@ class _DHalfSNResNet18(object):
         return [blk for li in range(1, 5) for blk in getattr(D, 'layer%d' % li)]
 
     @staticmethod
-    def prep(S):
+    def prep(S, head=True):
         D, dev, N = S.D, S.dev, S.n
-        head = D._head()
         blocks = _DHalfSNResNet18._blocks(D)
         # (conv module, cin, cout, k, stride, pad, input map) of the trunk convs behind the stem, in execution order
         S.d_blocks, convs, hw, cin = [], [], 32, 64
@@ -197,7 +218,10 @@ class _DHalfSNResNet18(object):
                 convs.append((blk.shortcut[0], cin, p, 1, s, 0, hw))
             S.d_blocks.append(ent)
             hw, cin = ho, p
-        S.d_layers = [D.conv1] + [c[0] for c in convs] + [head.l1, head.l2]
+        S.d_layers = [D.conv1] + [c[0] for c in convs]
+        if head:
+            h = D._head()
+            S.d_layers += [h.l1, h.l2]
         specs = [ops.SnSpec(m.weight_orig, m.weight_u, m.weight_v) for m in S.d_layers]
         ldws = [ops.round_up(s.K, 4) for s in specs]
         S.d_wbuf, v = _flat_views([s.T * s.C * ld for s, ld in zip(specs, ldws)], dev)
@@ -232,8 +256,8 @@ class _DHalfSNResNet18(object):
         return flat[:math.prod(shape)].view(shape)
 
     @staticmethod
-    def forward(S):
-        N, w, L, view = S.n, S.d_wps, S.d_layers, _DHalfSNResNet18._view
+    def forward_trunk(S):
+        w, L, view = S.d_wps, S.d_layers, _DHalfSNResNet18._view
         ops.rgb_conv_fwd(S.x, w[0], L[0].bias, 64, 3, 2.0, -1.0, _SLOPE, 1.0, out=S.d_stem)
         h = S.d_stem
         for j, b in enumerate(S.d_blocks):
@@ -246,6 +270,11 @@ class _DHalfSNResNet18(object):
             ops.conv2d_fwd(S.d_c1[j], w[i2], L[i2].bias, p, 3, 3, 1, 1, 1.0, 1.0, out=pre, addend=sc, filters=S.d_filters)
             h = ops.fused_bias_act(pre, None, None, 3, 0, _SLOPE, 1.0, out=S.d_outs[j])
         torch.mean(h, (1, 2), out=S.d_feats)
+
+    @staticmethod
+    def forward(S):
+        N, w, L = S.n, S.d_wps, S.d_layers
+        _DHalfSNResNet18.forward_trunk(S)
         n = len(w)
         ops.conv2d_fwd(S.d_feats.view(N, 1, 1, 512), w[n - 2], L[n - 2].bias, S.dh, 1, 1, 1, 0, _SLOPE, 1.0, out=S.hidden)
         ops.conv2d_fwd(S.hidden, w[n - 1], L[n - 1].bias, 1, 1, 1, 1, 0, out=S.logits)
@@ -256,9 +285,20 @@ class _DHalfSNResNet18(object):
         ops.conv2d_dgrad(S.neg_one, w[n - 1], (N, 1, 1, S.dh), 1, 1, 1, 0, act_ref=S.hidden, slope=_SLOPE, gain=1.0,
                          out=S.g_hidden)
         ops.conv2d_dgrad(S.g_hidden, w[n - 2], (N, 1, 1, 512), 1, 1, 1, 0, out=S.g_feats.view(N, 1, 1, 512))
+        _DHalfSNResNet18.backward_trunk(S, _DHalfSNResNet18.seed_rows(S, S.g_feats, S.c_row))
+
+    @staticmethod
+    def seed_rows(S, rows, row):
+        """The gradient at the last join's pre-activation from per-sample rows (N, 512) at the pooled features plus one
+        broadcast row: ((rows + row) / 16) * lrelu'(a), into the first of the rotating buffers."""
+        return ops.cddls_pooled_seed(rows, row, S.d_outs[-1], _SLOPE,
+                                     out=_DHalfSNResNet18._view(S.d_gbufs[0], S.d_blocks[-1]['out']))
+
+    @staticmethod
+    def backward_trunk(S, gp):
+        w, view = S.d_wps, _DHalfSNResNet18._view
         P, Q, R = S.d_gbufs
-        # gp: the gradient at the pre-activation of the join the walk stands at
-        gp = ops.cddls_pooled_seed(S.g_feats, S.c_row, S.d_outs[-1], _SLOPE, out=view(P, S.d_blocks[-1]['out']))
+        # gp: the gradient at the pre-activation of the join the walk stands at (seed_rows wrote it into P)
         for j in range(len(S.d_blocks) - 1, -1, -1):
             b = S.d_blocks[j]
             i1, i2, isc, p, s = b['c1'], b['c2'], b['sc'], b['planes'], b['stride']
@@ -288,7 +328,67 @@ def _d_half(D):
     return None
 
 
-class CDDLSSampler(object):
+class _GHalf(object):
+    """The G half of a step on G_SNDCGAN in eval mode, on static buffers: the constant prep, the forward that keeps its
+    activations and the hand-written backward to ``g_z``.  Shared by CDDLSSampler and recover.LatentRecovery, which set
+    ``G``, ``dev``, ``n``, ``hb``, ``wb``, ``feat`` and allocate ``z``, ``g_z``, ``h0``, ``g_h0``, ``gout``, ``g_lin``,
+    ``g_acts``, ``g_grads``."""
+
+    def _prep_g(self):
+        G, dev, N = self.G, self.dev, self.n
+        self.g_wps = G._weights()
+        self.g_filters = None
+        if ops.FILTER_PREP:
+            reqs, H, W = [], self.hb, self.wb
+            for j in range(3):
+                ci, co, k, s, p = G._CONVT[j]
+                H, W = 2 * H, 2 * W
+                d = ops.dgrad_desc((N, H, W, co), self.g_wps[1 + j], ci, k, k, s, p)
+                reqs += [(1, d, self.g_wps[1 + j]), (0, d, self.g_wps[1 + j])]       # forward = dgrad, backward = fwd
+            self.g_filters = ops.filter_prep(reqs, dev)
+        # eval-mode BatchNorm through the as-is form of the apply kernel (ops.bn_relu_apply_eval): mean = running_mean -
+        # conv bias (the transposed conv runs without its bias), made once here; the variance is running_var itself, the
+        # tensor the backward kernel reads, so the step's backward is the derivative of its forward
+        self.g_bns = [G.norm_init] + [G.main[3 * j + 1] for j in range(3)]
+        self.g_means = [ops.bn_eval_mean(bn, cb).clone()
+                        for bn, cb in zip(self.g_bns, [None] + [G.main[3 * j].bias for j in range(3)])]
+
+    def _g_forward(self):
+        G, N, f, w = self.G, self.n, self.feat, self.g_wps
+        ops.conv2d_fwd(self.z.view(N, 1, 1, G.nz), w[0], G.linear.bias, f, 1, 1, 1, 0, out=self.h0.view(N, 1, 1, f))
+        bn = self.g_bns[0]
+        ops.bn_relu_apply_eval(self.h0, self.g_acts[0].view(N, f), self.g_means[0], bn.running_var, bn.weight, bn.bias,
+                               bn.eps, self.hb * self.wb)
+        for j in range(3):
+            ci, co, k, s, p = G._CONVT[j]
+            y = self.g_acts[j + 1]
+            ops.conv2d_dgrad(self.g_acts[j], w[1 + j], tuple(y.shape), k, k, s, p, out=y, filters=self.g_filters)
+            bn, y2 = self.g_bns[j + 1], ops.as_rows(y)
+            ops.bn_relu_apply_eval(y2, y2, self.g_means[j + 1], bn.running_var, bn.weight, bn.bias, bn.eps)
+        ops.rgb_conv_dgrad(self.g_acts[3], w[4], G.main[9].bias, 3, 3, act=1, out_scale=0.5, out_shift=0.5, out=self.gout)
+
+    def _g_backward(self):
+        G, N, f, w = self.G, self.n, self.feat, self.g_wps
+        # a transposed conv's backward is the conv forward kernel on the same packed weights
+        ops.rgb_conv_fwd(self.g_lin, w[4], None, 64, 3, 1.0, 0.0, 1.0, 1.0, out=self.g_grads[3])
+        for j in range(2, -1, -1):
+            ci, co, k, s, p = G._CONVT[j]
+            bn, g2 = self.g_bns[j + 1], ops.as_rows(self.g_grads[j + 1])
+            ops.bn_relu_bwd_eval(g2, ops.as_rows(self.g_acts[j + 1]), g2, bn.weight, bn.running_var, bn.eps)
+            ops.conv2d_fwd(self.g_grads[j + 1], w[1 + j], None, ci, k, k, s, p, out=self.g_grads[j], filters=self.g_filters)
+        bn = self.g_bns[0]
+        ops.bn_relu_bwd_eval(self.g_grads[0].view(N, f), self.g_acts[0].view(N, f), self.g_h0, bn.weight, bn.running_var,
+                             bn.eps, perm_hw=self.hb * self.wb)
+        ops.conv2d_dgrad(self.g_h0.view(N, 1, 1, f), w[0], (N, 1, 1, G.nz), 1, 1, 1, 0, out=self.g_z.view(N, 1, 1, G.nz))
+
+    def _g_regions(self):
+        """The ReLU regions of the last forward in the reference's layouts: after norm_init (N, f) NCHW-flat, then three
+        NCHW maps."""
+        g = [(self.g_acts[0] > 0).permute(0, 3, 1, 2).reshape(self.n, self.feat)]
+        return g + [(a > 0).permute(0, 3, 1, 2) for a in self.g_acts[1:]]
+
+
+class CDDLSSampler(_GHalf):
     """Langevin sampler for one batch size on static buffers.  ``G`` / ``D``: eval-mode modules on the device (G_SNDCGAN
     with D_SNDCGAN or D_SNResNet18); ``weight`` / ``bias``: the linear-evaluation head (n_classes, d_penul) / (n_classes,).
     The G half, the element-wise ends, the noise and the step counter are shared; the D half (prep, buffers, forward,
@@ -321,25 +421,6 @@ class CDDLSSampler(object):
     # ---- constant work ----
     def _prep_d(self):
         self.half.prep(self)
-
-    def _prep_g(self):
-        G, dev, N = self.G, self.dev, self.n
-        self.g_wps = G._weights()
-        self.g_filters = None
-        if ops.FILTER_PREP:
-            reqs, H, W = [], self.hb, self.wb
-            for j in range(3):
-                ci, co, k, s, p = G._CONVT[j]
-                H, W = 2 * H, 2 * W
-                d = ops.dgrad_desc((N, H, W, co), self.g_wps[1 + j], ci, k, k, s, p)
-                reqs += [(1, d, self.g_wps[1 + j]), (0, d, self.g_wps[1 + j])]       # forward = dgrad, backward = fwd
-            self.g_filters = ops.filter_prep(reqs, dev)
-        # eval-mode BatchNorm through the as-is form of the apply kernel (ops.bn_relu_apply_eval): mean = running_mean -
-        # conv bias (the transposed conv runs without its bias), made once here; the variance is running_var itself, the
-        # tensor the backward kernel reads, so the step's backward is the derivative of its forward
-        self.g_bns = [G.norm_init] + [G.main[3 * j + 1] for j in range(3)]
-        self.g_means = [ops.bn_eval_mean(bn, cb).clone()
-                        for bn, cb in zip(self.g_bns, [None] + [G.main[3 * j].bias for j in range(3)])]
 
     def _alloc(self):
         N, dev, hb, wb = self.n, self.dev, self.hb, self.wb
@@ -381,39 +462,11 @@ class CDDLSSampler(object):
                 ops.cddls_normal_fill(self.z2.numel(), self.seed, STREAM_INIT, step_dev=self.state, out=self.z2.view(-1))
 
     # ---- one Langevin step ----
-    def _g_forward(self):
-        G, N, f, w = self.G, self.n, self.feat, self.g_wps
-        ops.conv2d_fwd(self.z.view(N, 1, 1, G.nz), w[0], G.linear.bias, f, 1, 1, 1, 0, out=self.h0.view(N, 1, 1, f))
-        bn = self.g_bns[0]
-        ops.bn_relu_apply_eval(self.h0, self.g_acts[0].view(N, f), self.g_means[0], bn.running_var, bn.weight, bn.bias,
-                               bn.eps, self.hb * self.wb)
-        for j in range(3):
-            ci, co, k, s, p = G._CONVT[j]
-            y = self.g_acts[j + 1]
-            ops.conv2d_dgrad(self.g_acts[j], w[1 + j], tuple(y.shape), k, k, s, p, out=y, filters=self.g_filters)
-            bn, y2 = self.g_bns[j + 1], ops.as_rows(y)
-            ops.bn_relu_apply_eval(y2, y2, self.g_means[j + 1], bn.running_var, bn.weight, bn.bias, bn.eps)
-        ops.rgb_conv_dgrad(self.g_acts[3], w[4], G.main[9].bias, 3, 3, act=1, out_scale=0.5, out_shift=0.5, out=self.gout)
-
     def _d_forward(self):
         self.half.forward(self)
 
     def _d_backward(self):
         self.half.backward(self)
-
-    def _g_backward(self):
-        G, N, f, w = self.G, self.n, self.feat, self.g_wps
-        # a transposed conv's backward is the conv forward kernel on the same packed weights
-        ops.rgb_conv_fwd(self.g_lin, w[4], None, 64, 3, 1.0, 0.0, 1.0, 1.0, out=self.g_grads[3])
-        for j in range(2, -1, -1):
-            ci, co, k, s, p = G._CONVT[j]
-            bn, g2 = self.g_bns[j + 1], ops.as_rows(self.g_grads[j + 1])
-            ops.bn_relu_bwd_eval(g2, ops.as_rows(self.g_acts[j + 1]), g2, bn.weight, bn.running_var, bn.eps)
-            ops.conv2d_fwd(self.g_grads[j + 1], w[1 + j], None, ci, k, k, s, p, out=self.g_grads[j], filters=self.g_filters)
-        bn = self.g_bns[0]
-        ops.bn_relu_bwd_eval(self.g_grads[0].view(N, f), self.g_acts[0].view(N, f), self.g_h0, bn.weight, bn.running_var,
-                             bn.eps, perm_hw=self.hb * self.wb)
-        ops.conv2d_dgrad(self.g_h0.view(N, 1, 1, f), w[0], (N, 1, 1, G.nz), 1, 1, 1, 0, out=self.g_z.view(N, 1, 1, G.nz))
 
     def _body(self, noise=None, noise2=None):
         with torch.no_grad():
@@ -466,10 +519,7 @@ class CDDLSSampler(object):
         """Test hook: the ReLU / LeakyReLU regions the last step ran on, as bool masks in the reference's layouts (G:
         after norm_init (N, f) NCHW-flat, then three NCHW maps; D: NCHW maps in execution order -- seven for sndcgan, 17
         for snresnet18 (stem, then conv1 and join of every block); the logit head's hidden (N, dh))."""
-        N = self.n
-        g = [(self.g_acts[0] > 0).permute(0, 3, 1, 2).reshape(N, self.feat)]
-        g += [(a > 0).permute(0, 3, 1, 2) for a in self.g_acts[1:]]
-        return {'g': g, 'd': self.half.regions(self), 'hidden': (self.hidden > 0).view(N, self.dh)}
+        return {'g': self._g_regions(), 'd': self.half.regions(self), 'hidden': (self.hidden > 0).view(self.n, self.dh)}
 
 
 def load_networks(logdir, linear_path, architecture, n_classes, dev):

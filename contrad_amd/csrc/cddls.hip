@@ -13,6 +13,14 @@
 //   cddls_energy_kernel            per-sample energy (diagnostic), one block per sample, fixed summation order
 //   cddls_normal_fill_kernel       the generator alone (tests, the initial z2)
 //
+// Latent recovery (contrad_amd/recover.py) runs on the same chain with one more form of three of these kernels, each a
+// loop of its own behind a wave-uniform launch argument (a null pointer selects the Langevin form, so those launches run
+// the code they ran before):
+//   cddls_energy_kernel, recovery form          pix[n] = |gout - x*|^2 / P, feat[n] = |phi - phi*|^2 / F, their weighted
+//                                               sum, and the residual rows (2 lambda / F)(phi - phi*) the D backward seeds from
+//   cddls_image_end_kernel, recovery form       g = (2 / P)(gout - x*) [+ g_x] through the tanh; no z2, no noise
+//   cddls_latent_update_kernel, Adam form       m, v, z in place with the clamp; the same last-ticket step counter
+//
 // Noise: Philox4x32-10, key = the 64-bit seed, counter = (quad index of the element, step, stream id, 0); one counter gives
 // the four normals of elements 4q .. 4q + 3 by Box-Muller (words 0, 1 -> elements 0, 1; words 2, 3 -> elements 2, 3).  A
 // draw depends on (seed, stream, step, element) only, never on the launch shape.  The step is read from device memory
@@ -260,51 +268,115 @@ __global__ __launch_bounds__(CD_THREADS) void cddls_compose_kernel(const float* 
   }
 }
 
+// recovery form of the image end: the loss's own pixel gradient (scale = 2 / P) plus the D half's (gx, may be null),
+// through the tanh.  No z2, no noise, no Philox work.
+__device__ __forceinline__ void image_end_recover_form(const float* __restrict__ gx, const float* __restrict__ gout,
+                                                       const float* __restrict__ target, float* __restrict__ g_lin,
+                                                       long long n, float scale, bool vec, long long q0,
+                                                       long long stride) {
+  const long long nq = (n + 3) / 4;
+  for (long long q = q0; q < nq; q += stride) {
+    float g[4] = {0.f, 0.f, 0.f, 0.f}, o[4], x[4], gl[4];
+    if (gx) load4(gx, 4 * q, n, vec, g);
+    load4(gout, 4 * q, n, vec, o);
+    load4(target, 4 * q, n, vec, x);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float t = 2.f * o[k] - 1.f;
+      gl[k] = fmaf(scale, o[k] - x[k], g[k]) * (0.5f * (1.f - t * t));
+    }
+    store4(g_lin, 4 * q, n, vec, gl);
+  }
+}
+
 __global__ __launch_bounds__(CD_THREADS) void cddls_image_end_kernel(const float* __restrict__ gx,
                                                                      const float* __restrict__ gout, float* z2,
                                                                      float* __restrict__ g_lin, long long n, float eps,
                                                                      float noise_scale, const float* __restrict__ noise,
                                                                      long long seed, const int* __restrict__ state,
-                                                                     int vec) {
-  const int step = state ? state[0] : 0;
-  const float he = 0.5f * eps;
+                                                                     int vec, const float* __restrict__ target,
+                                                                     float target_scale) {
+  // the launch geometry is read once, ahead of the branch; the Langevin loop stays right behind the entry block and the
+  // recovery form (target != null: a launch argument, wave-uniform) behind it
+  const long long q0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+  if (__builtin_expect(target == nullptr, 1)) {
+    const int step = state ? state[0] : 0;
+    const float he = 0.5f * eps;
+    const long long nq = (n + 3) / 4;
+    for (long long q = q0; q < nq; q += stride) {
+      float g[4], o[4], b[4], nz[4], gl[4];
+      load4(gx, 4 * q, n, vec != 0, g);
+      load4(gout, 4 * q, n, vec != 0, o);
+      load4(z2, 4 * q, n, vec != 0, b);
+      noise4(noise, q, n, vec != 0, step, CD_STREAM_Z2, seed, nz);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float t = 2.f * o[k] - 1.f;                     // tanh of the generator's last pre-activation
+        gl[k] = g[k] * (0.5f * (1.f - t * t));
+        const float gz2 = fmaf(eps, g[k], b[k]);              // d e / d z2 = eps * g_x + z2
+        b[k] = fmaf(noise_scale, nz[k], fmaf(-he, gz2, b[k]));
+      }
+      store4(g_lin, 4 * q, n, vec != 0, gl);
+      store4(z2, 4 * q, n, vec != 0, b);
+    }
+  } else {
+    image_end_recover_form(gx, gout, target, g_lin, n, target_scale, vec != 0, q0, stride);
+  }
+}
+
+// Adam form of the latent update, t = step + 1:  m <- b1 m + (1 - b1) g,  v <- b2 v + (1 - b2) g^2,
+// z <- clamp(z - lr (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + adam_eps), -1, 1).  The two bias corrections are made once
+// per thread in float64 and rounded once to fp32.  g = 0 on m = v = 0 leaves z bitwise as it was.
+__device__ __forceinline__ void latent_adam_form(float* z, const float* __restrict__ gz, float* m, float* v, long long n,
+                                                 float lr, float b1, float b2, float adam_eps, int step, bool vec,
+                                                 long long q0, long long stride) {
+  const double t = (double)step + 1.0;
+  const float c1 = (float)(1.0 - pow((double)b1, t)), c2 = (float)(1.0 - pow((double)b2, t));
+  const float ob1 = 1.f - b1, ob2 = 1.f - b2;
   const long long nq = (n + 3) / 4;
-  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
-    float g[4], o[4], b[4], nz[4], gl[4];
-    load4(gx, 4 * q, n, vec != 0, g);
-    load4(gout, 4 * q, n, vec != 0, o);
-    load4(z2, 4 * q, n, vec != 0, b);
-    noise4(noise, q, n, vec != 0, step, CD_STREAM_Z2, seed, nz);
+  for (long long q = q0; q < nq; q += stride) {
+    float a[4], g[4], mm[4], vv[4];
+    load4(z, 4 * q, n, vec, a);
+    load4(gz, 4 * q, n, vec, g);
+    load4(m, 4 * q, n, vec, mm);
+    load4(v, 4 * q, n, vec, vv);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float t = 2.f * o[k] - 1.f;                       // tanh of the generator's last pre-activation
-      gl[k] = g[k] * (0.5f * (1.f - t * t));
-      const float gz2 = fmaf(eps, g[k], b[k]);                // d e / d z2 = eps * g_x + z2
-      b[k] = fmaf(noise_scale, nz[k], fmaf(-he, gz2, b[k]));
+      mm[k] = fmaf(b1, mm[k], ob1 * g[k]);
+      vv[k] = fmaf(b2, vv[k], ob2 * (g[k] * g[k]));
+      const float u = (mm[k] / c1) / (sqrtf(vv[k] / c2) + adam_eps);
+      a[k] = fminf(fmaxf(fmaf(-lr, u, a[k]), -1.f), 1.f);
     }
-    store4(g_lin, 4 * q, n, vec != 0, gl);
-    store4(z2, 4 * q, n, vec != 0, b);
+    store4(m, 4 * q, n, vec, mm);
+    store4(v, 4 * q, n, vec, vv);
+    store4(z, 4 * q, n, vec, a);
   }
 }
 
 __global__ __launch_bounds__(CD_THREADS) void cddls_latent_update_kernel(float* z, const float* __restrict__ gz,
                                                                          long long n, float eps, float noise_scale,
                                                                          const float* __restrict__ noise,
-                                                                         long long seed, int* state, int vec) {
+                                                                         long long seed, int* state, int vec, float* m,
+                                                                         float* v, float b1, float b2, float adam_eps) {
   const int step = state ? state[0] : 0;
-  const float he = 0.5f * eps;
-  const long long nq = (n + 3) / 4;
-  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
-    float a[4], g[4], nz[4];
-    load4(z, 4 * q, n, vec != 0, a);
-    load4(gz, 4 * q, n, vec != 0, g);
-    noise4(noise, q, n, vec != 0, step, CD_STREAM_Z, seed, nz);
+  if (__builtin_expect(m != nullptr, 0)) {        // wave-uniform: a launch argument (eps carries the learning rate)
+    latent_adam_form(z, gz, m, v, n, eps, b1, b2, adam_eps, step, vec != 0,
+                     (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
+  } else {
+    const float he = 0.5f * eps;
+    const long long nq = (n + 3) / 4;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
+      float a[4], g[4], nz[4];
+      load4(z, 4 * q, n, vec != 0, a);
+      load4(gz, 4 * q, n, vec != 0, g);
+      noise4(noise, q, n, vec != 0, step, CD_STREAM_Z, seed, nz);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float v = fmaf(noise_scale, nz[k], fmaf(-he, g[k], a[k]));
-      a[k] = fminf(fmaxf(v, -1.f), 1.f);
+      for (int k = 0; k < 4; ++k) {
+        const float u = fmaf(noise_scale, nz[k], fmaf(-he, g[k], a[k]));
+        a[k] = fminf(fmaxf(u, -1.f), 1.f);
+      }
+      store4(z, 4 * q, n, vec != 0, a);
     }
-    store4(z, 4 * q, n, vec != 0, a);
   }
   if (state == nullptr) return;
   // every thread of this block has read state[0] (the value is in a register before the barrier); the block that draws
@@ -319,23 +391,67 @@ __global__ __launch_bounds__(CD_THREADS) void cddls_latent_update_kernel(float* 
   }
 }
 
+// recovery form of the energy kernel: pix[n] = |gout[n] - x*[n]|^2 / P, feat[n] = |phi[n] - phi*[n]|^2 / F (0 without phi), loss[n] = pix[n] +
+// lam feat[n], and the residual row r[n][f] = (2 lam / F)(phi - phi*).  One block per sample, the sums in the order of the
+// Langevin form (a strided partial per lane, the wave tree, the waves in index order): no atomics, two calls bitwise equal.
+__device__ __forceinline__ void energy_recover_form(const float* __restrict__ gout, const float* __restrict__ target,
+                                                    const float* __restrict__ phi, const float* __restrict__ phi_target,
+                                                    float* __restrict__ resid, float* __restrict__ pix,
+                                                    float* __restrict__ featl, float* __restrict__ loss, int F,
+                                                    long long P, float lam, float* red) {
+  const long long n = blockIdx.x;
+  const float* o = gout + n * P;
+  const float* x = target + n * P;
+  float q = 0.f, s = 0.f;
+  for (long long i = threadIdx.x; i < P; i += blockDim.x) {
+    const float d = o[i] - x[i];
+    q = fmaf(d, d, q);
+  }
+  q = block_sum(q, red);
+  if (phi) {                        // block-uniform
+    const float* f = phi + n * F;
+    const float* t = phi_target + n * F;
+    float* r = resid + n * F;
+    const float rs = (2.f * lam) / (float)F;
+    for (int i = threadIdx.x; i < F; i += blockDim.x) {
+      const float d = f[i] - t[i];
+      s = fmaf(d, d, s);
+      r[i] = rs * d;
+    }
+    s = block_sum(s, red);
+  }
+  if (threadIdx.x == 0) {
+    const float pv = q / (float)P, fv = phi ? s / (float)F : 0.f;
+    pix[n] = pv;
+    featl[n] = fv;
+    loss[n] = fmaf(lam, fv, pv);
+  }
+}
+
 // e[n] = -d[n] + <feat[n], c_row> + bias_term[0] + 0.5 |z2[n]|^2 with c_row = -lbd * w_y (trunk order), bias_term = -lbd * b_y
 __global__ __launch_bounds__(CD_THREADS) void cddls_energy_kernel(const float* __restrict__ d, int ldd,
                                                                   const float* __restrict__ feat,
                                                                   const float* __restrict__ c_row,
                                                                   const float* __restrict__ bias_term,
                                                                   const float* __restrict__ z2, float* __restrict__ e,
-                                                                  int F, long long P) {
+                                                                  int F, long long P,
+                                                                  const float* __restrict__ target,
+                                                                  float* __restrict__ resid, float* __restrict__ pix,
+                                                                  float* __restrict__ featl, float lam) {
   __shared__ float red[16];
-  const long long n = blockIdx.x;
-  const float* f = feat + n * F;
-  const float* b = z2 + n * P;
-  float s = 0.f, q = 0.f;
-  for (int i = threadIdx.x; i < F; i += blockDim.x) s = fmaf(f[i], c_row[i], s);
-  for (long long i = threadIdx.x; i < P; i += blockDim.x) q = fmaf(b[i], b[i], q);
-  s = block_sum(s, red);
-  q = block_sum(q, red);
-  if (threadIdx.x == 0) e[n] = (s + bias_term[0] - d[n * ldd]) + 0.5f * q;
+  if (__builtin_expect(target == nullptr, 1)) {       // the Langevin form stays right behind the entry block
+    const long long n = blockIdx.x;
+    const float* f = feat + n * F;
+    const float* b = z2 + n * P;
+    float s = 0.f, q = 0.f;
+    for (int i = threadIdx.x; i < F; i += blockDim.x) s = fmaf(f[i], c_row[i], s);
+    for (long long i = threadIdx.x; i < P; i += blockDim.x) q = fmaf(b[i], b[i], q);
+    s = block_sum(s, red);
+    q = block_sum(q, red);
+    if (threadIdx.x == 0) e[n] = (s + bias_term[0] - d[n * ldd]) + 0.5f * q;
+  } else {            // wave-uniform: a launch argument (z2 = gout, feat = phi, c_row = phi*, e = loss)
+    energy_recover_form(z2, target, feat, c_row, resid, pix, featl, e, F, P, lam, red);
+  }
 }
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -420,7 +536,8 @@ extern "C" int contrad_cddls_image_end(const float* gx, const float* gout, float
   CONTRAD_ARG(gx && gout && z2 && g_lin && n >= 1 && eps >= 0.f);
   const int vec = al16(gx) && al16(gout) && al16(z2) && al16(g_lin) && (noise == nullptr || al16(noise));
   hipLaunchKernelGGL(cddls_image_end_kernel, dim3(quad_grid((n + 3) / 4)), dim3(CD_THREADS), 0, (hipStream_t)stream, gx,
-                     gout, z2, g_lin, n, eps, noise_scale_of(eps, sigma_n), noise, seed, static_cast<const int*>(state), vec);
+                     gout, z2, g_lin, n, eps, noise_scale_of(eps, sigma_n), noise, seed, static_cast<const int*>(state), vec,
+                     (const float*)nullptr, 0.f);
   CONTRAD_CHECK_LAUNCH();
   return 0;
 }
@@ -430,7 +547,8 @@ extern "C" int contrad_cddls_latent_update(float* z, const float* gz, long long 
   CONTRAD_ARG(z && gz && n >= 1 && eps >= 0.f);
   const int vec = al16(z) && al16(gz) && (noise == nullptr || al16(noise));
   hipLaunchKernelGGL(cddls_latent_update_kernel, dim3(quad_grid((n + 3) / 4)), dim3(CD_THREADS), 0, (hipStream_t)stream,
-                     z, gz, n, eps, noise_scale_of(eps, sigma_n), noise, seed, static_cast<int*>(state), vec);
+                     z, gz, n, eps, noise_scale_of(eps, sigma_n), noise, seed, static_cast<int*>(state), vec, (float*)nullptr,
+                     (float*)nullptr, 0.f, 0.f, 0.f);
   CONTRAD_CHECK_LAUNCH();
   return 0;
 }
@@ -440,7 +558,43 @@ extern "C" int contrad_cddls_energy(const float* d, int ldd, const float* feat, 
                                     contrad_stream_t stream) {
   CONTRAD_ARG(d && feat && c_row && bias_term && z2 && e && N >= 1 && F >= 1 && P >= 1 && ldd >= 1);
   hipLaunchKernelGGL(cddls_energy_kernel, dim3(N), dim3(CD_THREADS), 0, (hipStream_t)stream, d, ldd, feat, c_row,
-                     bias_term, z2, e, F, P);
+                     bias_term, z2, e, F, P, (const float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0.f);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- latent recovery (contrad_amd/recover.py): the recovery / Adam forms of the three kernels above ----
+extern "C" int contrad_cddls_recover_loss(const float* gout, const float* target, const float* phi,
+                                          const float* phi_target, float* resid, float* pix, float* feat, float* loss,
+                                          int N, int F, long long P, float lambda_feat, contrad_stream_t stream) {
+  CONTRAD_ARG(gout && target && pix && feat && loss && N >= 1 && P >= 1);
+  CONTRAD_ARG(phi ? (phi_target && resid && F >= 1) : (!phi_target && !resid));
+  hipLaunchKernelGGL(cddls_energy_kernel, dim3(N), dim3(CD_THREADS), 0, (hipStream_t)stream, (const float*)nullptr, 1, phi,
+                     phi_target, (const float*)nullptr, gout, loss, F, P, target, resid, pix, feat, lambda_feat);
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int contrad_cddls_recover_image_end(const float* gx, const float* gout, const float* target, float* g_lin,
+                                               long long n, long long P, contrad_stream_t stream) {
+  CONTRAD_ARG(gout && target && g_lin && n >= 1 && P >= 1);
+  const int vec = (gx == nullptr || al16(gx)) && al16(gout) && al16(target) && al16(g_lin);
+  hipLaunchKernelGGL(cddls_image_end_kernel, dim3(quad_grid((n + 3) / 4)), dim3(CD_THREADS), 0, (hipStream_t)stream, gx,
+                     gout, (float*)nullptr, g_lin, n, 0.f, 0.f, (const float*)nullptr, 0ll, (const int*)nullptr, vec, target,
+                     (float)(2.0 / (double)P));
+  CONTRAD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int contrad_cddls_recover_update(float* z, const float* gz, float* m, float* v, long long n, float lr,
+                                            float beta1, float beta2, float adam_eps, void* state,
+                                            contrad_stream_t stream) {
+  CONTRAD_ARG(z && gz && m && v && state && n >= 1 && lr >= 0.f);
+  CONTRAD_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && adam_eps >= 0.f);
+  const int vec = al16(z) && al16(gz) && al16(m) && al16(v);
+  hipLaunchKernelGGL(cddls_latent_update_kernel, dim3(quad_grid((n + 3) / 4)), dim3(CD_THREADS), 0, (hipStream_t)stream,
+                     z, gz, n, lr, 0.f, (const float*)nullptr, 0ll, static_cast<int*>(state), vec, m, v, beta1, beta2,
+                     adam_eps);
   CONTRAD_CHECK_LAUNCH();
   return 0;
 }

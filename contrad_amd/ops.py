@@ -1491,6 +1491,60 @@ def cddls_energy(d, feat, c_row, bias_term, z2, out=None):
     return out
 
 
+def cddls_recover_loss(gout, target, lambda_feat=0.0, phi=None, phi_target=None, resid=None, out=None):
+    """The recovery loss of ``gout`` (N, ...) against ``target`` -> (pix, feat, loss), the rows of ``out`` (3, N).  With
+    ``phi`` / ``phi_target`` (N, F) the feature term and its residual rows ``resid`` (N, F) are written too."""
+    _flat_f32(gout, 'gout'); _flat_f32(target, 'target')
+    N = gout.shape[0]
+    if target.numel() != gout.numel() or gout.numel() % N:
+        raise RuntimeError('contrad_hip: gout and target must hold the same N samples')
+    F = 1
+    if phi is not None:
+        for t, nm in ((phi, 'phi'), (phi_target, 'phi_target'), (resid, 'resid')):
+            if t is None:
+                raise RuntimeError('contrad_hip: the feature term needs phi, phi_target and resid')
+            _flat_f32(t, nm)
+            if t.numel() != phi.numel() or t.numel() % N:
+                raise RuntimeError('contrad_hip: %s must hold N feature rows' % nm)
+        F = phi.numel() // N
+    elif phi_target is not None or resid is not None:
+        raise RuntimeError('contrad_hip: phi_target and resid without phi')
+    if out is None:
+        out = torch.empty(3, N, device=gout.device, dtype=torch.float32)
+    _flat_f32(out, 'out')
+    if tuple(out.shape) != (3, N):
+        raise RuntimeError('contrad_hip: out must be (3, N)')
+    lib().call('contrad_cddls_recover_loss', _p(gout), _p(target), _p(phi), _p(phi_target), _p(resid), _p(out[0]),
+               _p(out[1]), _p(out[2]), N, F, ctypes.c_longlong(gout.numel() // N), float(lambda_feat), _stream())
+    return out[0], out[1], out[2]
+
+
+def cddls_recover_image_end(gout, target, g_lin, P, gx=None):
+    """Writes ``g_lin``: ((2 / P)(gout - target) [+ gx]) through the generator's tanh."""
+    for t, nm in ((gout, 'gout'), (target, 'target'), (g_lin, 'g_lin'), (gx, 'gx')):
+        _flat_f32(t, nm)
+        if t is not None and t.numel() != gout.numel():
+            raise RuntimeError('contrad_hip: %s must have the size of gout' % nm)
+    lib().call('contrad_cddls_recover_image_end', _p(gx), _p(gout), _p(target), _p(g_lin), ctypes.c_longlong(gout.numel()),
+               ctypes.c_longlong(int(P)), _stream())
+    return g_lin
+
+
+def cddls_recover_update(z, gz, m, v, lr, betas, adam_eps, state):
+    """One Adam step on ``z`` with the clamp to [-1, 1], ``m`` / ``v`` in place; t = state[0] + 1; advances ``state[0]``."""
+    for t, nm in ((z, 'z'), (gz, 'gz'), (m, 'm'), (v, 'v')):
+        _flat_f32(t, nm)
+        if t.numel() != z.numel():
+            raise RuntimeError('contrad_hip: %s must have the size of z' % nm)
+    _chk_state(state)
+    if state is None:
+        raise RuntimeError('contrad_hip: the Adam form needs the step state')
+    lib().call('contrad_cddls_recover_update', _p(z), _p(gz), _p(m), _p(v), ctypes.c_longlong(z.numel()), float(lr),
+               float(betas[0]), float(betas[1]), float(adam_eps), _p(state), _stream())
+    for t in (z, m, v):
+        torch.autograd.graph.increment_version(t)
+
+
 # --------------------------------------------------------------------------------------------------
 # baseline training modes (csrc/baseline_aug.hip): hfrt / hflip, DiffAugment, consistency, (2N,1) GAN loss
 # --------------------------------------------------------------------------------------------------

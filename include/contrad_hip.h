@@ -695,6 +695,24 @@ int contrad_cddls_latent_update(float* z, const float* gz, long long n, float ep
  * c_row = -lbd * w_y (in feat's order) and bias_term = -lbd * b_y. */
 int contrad_cddls_energy(const float* d, int ldd, const float* feat, const float* c_row, const float* bias_term,
                          const float* z2, float* e, int N, int F, long long P, contrad_stream_t stream);
+/* Latent recovery (contrad_amd/recover.py): one more form of the energy, image-end and latent-update kernels, for
+ * projecting given images x* onto G by Adam on z.  gout = G(z) and x* are (N, P) rows, phi / phi* (N, F) feature rows.
+ * Every call returns -EINVAL before any GPU call on a null required pointer, N / n / P < 1, a feature pointer without its
+ * target or residual pointer (or those without it), lr < 0, a beta outside [0, 1) or adam_eps < 0.
+ * loss     pix[i] = |gout[i] - x*[i]|^2 / P, feat[i] = |phi[i] - phi*[i]|^2 / F, loss[i] = pix[i] + lambda_feat * feat[i],
+ *          resid[i][f] = (2 lambda_feat / F) (phi[i][f] - phi*[i][f]).  phi == NULL (then phi_target and resid too): the
+ *          pixel part only, feat[i] = 0.  One block per sample, fixed summation order, no atomics.
+ * image end g_lin = ((2 / P) (gout - x*) [+ gx]) * 0.5 (1 - t^2), t = 2 gout - 1; gx may be NULL.  n floats, any n.
+ * update   t = state[0] + 1:  m <- beta1 m + (1 - beta1) gz,  v <- beta2 v + (1 - beta2) gz^2,
+ *          z <- clamp(z - lr (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + adam_eps), -1, 1) in place (the two
+ *          corrections in float64, rounded once to fp32), then state[0] += 1 as contrad_cddls_latent_update does. */
+int contrad_cddls_recover_loss(const float* gout, const float* target, const float* phi, const float* phi_target,
+                               float* resid, float* pix, float* feat, float* loss, int N, int F, long long P,
+                               float lambda_feat, contrad_stream_t stream);
+int contrad_cddls_recover_image_end(const float* gx, const float* gout, const float* target, float* g_lin, long long n,
+                                    long long P, contrad_stream_t stream);
+int contrad_cddls_recover_update(float* z, const float* gz, float* m, float* v, long long n, float lr, float beta1,
+                                 float beta2, float adam_eps, void* state, contrad_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Gradient penalty (csrc/gp.hip): the two device-side pieces of --penalty=gp (the reference's penalty.py:16-42).
