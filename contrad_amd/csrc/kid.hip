@@ -11,6 +11,9 @@
 //               kind 2 (contrad_dot_sums only) takes a second operand T of the same shape, with a leading dimension and a
 //               vec_ok of its own, walked by the same load_tile behind the wave-uniform branch on `kind`: the term is
 //               (double)s * (double)t, exact in float64, and nothing is left out.  Kinds 0 and 1 load no T tile.
+//               kind 3 (contrad_gauss_sums only; contrad_amd/contrast.py's uniformity) is the Gaussian potential of two
+//               unit vectors, exp(-t u) at u = max(2 - 2 s, 0), t in the `gamma` argument: one float64 multiply and one
+//               float64 exp per term, in a loop of its own behind the same kind of wave-uniform branch.
 //   kid_final   one workgroup adds the partials in a fixed order (thread t the partials t, t + 256, ...; then a tree
 //               in LDS) and one thread adds the old value last when `accumulate` is set.
 // No atomics: out[0] depends on no order of arrival, two calls are bitwise equal.
@@ -27,6 +30,7 @@ constexpr int KID_RPW_MAX = 32;                     // rows per wave of a tile
 constexpr int KID_RPW_MIN = 4;
 constexpr long long KID_ENOUGH_BLOCKS = 1024;
 constexpr int KID_KIND_DOT = 2;                     // internal: the product of two operands (contrad_dot_sums)
+constexpr int KID_KIND_GAUSS = 3;                   // internal: exp(-t u) (contrad_gauss_sums)
 
 struct KidPlan {
   long long ctiles, blocks;
@@ -75,6 +79,41 @@ __device__ __forceinline__ double dot_rows(const float* __restrict__ S, long lon
   return acc;
 }
 
+// Kind 3, a wave's rows of a tile: the walk and the leave-out of kinds 0 and 1, the term exp(-t u) in float64.  A NaN stays a
+// NaN through the comparison, an s slightly above 1 gives u = 0 and the term exp(-0) = 1.  exp in float64 needs more
+// registers than the terms of kinds 0 and 1: with the 16 floats of a tile held beside it the kernel would pass from 70 to
+// 78 VGPRs and from 7 to 6 waves per SIMD for every kind.  So a lane parks its tile in LDS (its own 16 words, column
+// `tid`: no bank conflict, no barrier) and takes the cells back one at a time in a rolled loop, in the order u, j of the
+// other kinds' loop.
+__device__ __forceinline__ double gauss_rows(const float* __restrict__ S, long long ldS, long long r0, int rows, long long c0, int n,
+                                             long long self0, double t, int vec_ok) {
+  __shared__ float park[16][KID_THREADS];
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  for (int t0 = 0; t0 < rows; t0 += 4) {
+    {
+      float v[4][4];
+      simrow::load_tile(v, S, ldS, r0, t0, rows, c0, n, vec_ok, 0.f, [](int, long long) {});
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) park[4 * u + j][tid] = v[u][j];
+    }
+#pragma unroll 1
+    for (int q = 0; q < 16; ++q) {
+      const int u = q >> 2, j = q & 3;
+      const bool live = t0 + u < rows;                 // (uniform)
+      const long long excl = self0 >= 0 ? self0 + r0 + 4 * (t0 + u) : -1;
+      double d = 2.0 - 2.0 * (double)park[q][tid];     // exact: a float doubled and taken from 2 fits 53 bits
+      d = d < 0.0 ? 0.0 : d;
+      const double k = exp(-(t * d));
+      const bool in = live && c0 + j < n && c0 + j != excl;       // left out by index: a select, so a NaN there is not seen
+      acc += in ? k : 0.0;
+    }
+  }
+  return acc;
+}
+
 // T may alias S (contrad_dot_sums with B = A): neither is written, so __restrict__ holds for both.
 __global__ __launch_bounds__(KID_THREADS) void kid_sums_kernel(const float* __restrict__ S, long long ldS,
                                                                const float* __restrict__ T, long long ldT,
@@ -91,6 +130,9 @@ __global__ __launch_bounds__(KID_THREADS) void kid_sums_kernel(const float* __re
   double acc = 0.0;
   if (kind == KID_KIND_DOT) {                          // (uniform) the T tile stays out of the loop of kinds 0 and 1
     acc = dot_rows(S, ldS, T, ldT, r0, rows, c0, n, vec_ok, vec_ok_t);
+    rows = 0;
+  } else if (kind == KID_KIND_GAUSS) {                 // (uniform) and so does exp
+    acc = gauss_rows(S, ldS, r0, rows, c0, n, self0, gamma, vec_ok);
     rows = 0;
   }
   for (int t0 = 0; t0 < rows; t0 += 4) {
@@ -146,7 +188,7 @@ int mmd_sums(const float* S, long long ldS, const float* T, long long ldT, int M
              double coef0, int accumulate, double* out, void* workspace, long long workspace_bytes, contrad_stream_t stream) {
   CONTRAD_ARG(S && out);
   CONTRAD_ARG(M >= 1 && n >= 1 && ldS >= n);
-  CONTRAD_ARG(kind == 0 || kind == 1 || (kind == KID_KIND_DOT && T && ldT >= n));
+  CONTRAD_ARG(kind == 0 || kind == 1 || kind == KID_KIND_GAUSS || (kind == KID_KIND_DOT && T && ldT >= n));
   CONTRAD_ARG(isfinite(gamma) && isfinite(coef0));
   const KidPlan p = kid_plan(M, n);
   CONTRAD_ARG(p.blocks <= 0x7fffffffll);
@@ -183,4 +225,10 @@ extern "C" int contrad_dot_sums(const float* A, long long ldA, const float* B, l
                                 double* out, void* workspace, long long workspace_bytes, contrad_stream_t stream) {
   CONTRAD_ARG(A && B);
   return mmd_sums(A, ldA, B, ldB, M, n, -1, KID_KIND_DOT, 1.0, 0.0, accumulate, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int contrad_gauss_sums(const float* S, long long ldS, int M, int n, long long self0, double t, int accumulate,
+                                  double* out, void* workspace, long long workspace_bytes, contrad_stream_t stream) {
+  CONTRAD_ARG(isfinite(t) && t >= 0.0);                // (a NaN compares false)
+  return mmd_sums(S, ldS, nullptr, 0, M, n, self0, KID_KIND_GAUSS, t, 0.0, accumulate, out, workspace, workspace_bytes, stream);
 }

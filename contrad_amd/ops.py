@@ -1280,9 +1280,10 @@ MMD_KINDS = {'poly3': 0, 'rq': 1}                                           # co
 
 
 def _sums(who, S, n, kind, self0, gamma, coef0, out, accumulate, T=None):
-    """The one body of ``kid_sums``, ``mmd_sums`` and ``dot_sums``; ``who`` names the caller in the messages and its entry
-    point, contrad_<who> (contrad_kid_sums is the kind = 0 entry point and takes no ``kind``; contrad_dot_sums takes the
-    second operand ``T`` and neither ``self0``, ``kind``, gamma nor coef0)."""
+    """The one body of ``kid_sums``, ``mmd_sums``, ``dot_sums`` and ``gauss_sums``; ``who`` names the caller in the messages
+    and its entry point, contrad_<who> (contrad_kid_sums is the kind = 0 entry point and takes no ``kind``; contrad_dot_sums
+    takes the second operand ``T`` and neither ``self0``, ``kind``, gamma nor coef0; contrad_gauss_sums takes its ``t`` where
+    gamma stands and neither ``kind`` nor coef0)."""
     M, ldS, n = _chk_S(S, n)
     if T is not None:
         _chk(T, 'B')
@@ -1309,6 +1310,9 @@ def _sums(who, S, n, kind, self0, gamma, coef0, out, accumulate, T=None):
     tail = (1 if accumulate else 0, _p(out), _p(ws), ctypes.c_longlong(nbytes), _stream())
     if T is not None:
         lib().call('contrad_' + who, _p(S), ctypes.c_longlong(ldS), _p(T), ctypes.c_longlong(_ld(T)), M, n, *tail)
+        return out
+    if who == 'gauss_sums':                                                 # t travels in gamma; there is no coef0
+        lib().call('contrad_' + who, _p(S), ctypes.c_longlong(ldS), M, n, ctypes.c_longlong(int(self0)), gamma, *tail)
         return out
     kargs = (int(kind),) if who == 'mmd_sums' else ()
     lib().call('contrad_' + who, _p(S), ctypes.c_longlong(ldS), M, n, ctypes.c_longlong(int(self0)), *kargs, gamma, coef0, *tail)
@@ -1339,6 +1343,18 @@ def dot_sums(A, B, n, out=None, accumulate=False):
     if B is None:
         raise RuntimeError('contrad_hip: dot_sums needs two operands (pass A twice for the sum of squares)')
     return _sums('dot_sums', A, n, 0, -1, 1.0, 0.0, out, accumulate, T=B)
+
+
+def gauss_sums(S, n, t=2.0, self0=-1, out=None, accumulate=False):
+    """out (1,) float64: the sum over rows i and columns j < n of ``S`` (M, ldS >= n), column ``self0 + i`` left out of row
+    i by index, of exp(-t * u) at u = max(2 - 2 S[i][j], 0) -- S holds similarities of UNIT vectors, u is their squared
+    distance; every term in float64, added in ``kid_sums``'s fixed order (no atomics: two calls are bitwise equal).
+    ``t``: finite and not negative.  ``out`` / ``accumulate``: as in ``kid_sums``.  contrad_gauss_sums's contract
+    (include/contrad_hip.h)."""
+    t = float(t)
+    if not (math.isfinite(t) and t >= 0.0):
+        raise RuntimeError('contrad_hip: gauss_sums needs a finite t >= 0, got %r' % (t,))
+    return _sums('gauss_sums', S, n, 0, self0, t, 0.0, out, accumulate)
 
 
 # ---- cDDLS sampling (csrc/cddls.hip) ----

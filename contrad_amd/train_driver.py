@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import config, prdc
+from . import config, contrast, prdc
 from .augment import get_augment
 from .data import loader_for
 from .engine import GradAllReducer, setup_grad_exchange
@@ -74,13 +74,14 @@ def monitor_help(shows):
 def make_parser(description, layout):
     """``layout``: the script's flags in ``--help`` order -- the name of a common flag, or ``(name, kwargs)`` for a flag of
     the script's own or for what it sets differently on a common one.  The monitoring hooks' flags
-    (knn.add_hook_arguments, then prdc.add_hook_arguments) come last."""
+    (knn.add_hook_arguments, then prdc.add_hook_arguments, then contrast.add_hook_arguments) come last."""
     parser = ArgumentParser(description=description)
     for item in layout:
         name, own = (item, {}) if isinstance(item, str) else item
         parser.add_argument(name, **dict(COMMON_FLAGS.get(name, {}), **own))
     add_hook_arguments(parser)
     prdc.add_hook_arguments(parser)
+    contrast.add_hook_arguments(parser)
     return parser
 
 
@@ -185,6 +186,7 @@ def build_run(P, script):
     """Everything between the parsed command line and the first iteration -> the run: P, options, G, D, g_ema (or None),
     opt_G, opt_D, reducers, loader, graphed, and what ``run_loop`` needs around them."""
     H = prdc.check_hook_arguments(P)                                # (refusals that need no device come first)
+    C = contrast.check_hook_arguments(P)
     if P.comment:
         P.comment = '_' + P.comment
     P.gin_stem = Path(P.gin_config).stem
@@ -241,12 +243,15 @@ def build_run(P, script):
     for line in (script.start_up_lines(P) if script.start_up_lines is not None else ()):
         log(line)
 
-    monitor = knn_monitor = prdc_monitor = None
+    monitor = knn_monitor = prdc_monitor = contrast_monitor = None
     if P.monitor and rank == 0:
         monitor = Monitor(logdir, P.architecture, image_size, dev, P.seed, no_gif=P.no_gif, P=P)
         loader = LastBatch(loader)                                  # the preview shows the batch the step drew
     if P.knn_data and rank == 0:
         knn_monitor = KNNMonitor(logdir, P.architecture, image_size, dev, P.seed, P.knn_data, k=P.knn_k, temp=P.knn_temp, P=P)
+    if C.contrast_data and rank == 0:                               # blocks of the training batch (all ranks' images)
+        contrast_monitor = contrast.ContrastMonitor(logdir, P.architecture, image_size, dev, P.seed, C.contrast_data,
+                                                    n=C.contrast_n, t=C.contrast_t, P=P, batch=options['batch_size'] * world)
     if H.prdc_data and rank == 0:
         prdc_monitor = prdc.PRDCMonitor(logdir, P.architecture, image_size, dev, P.seed, H.prdc_data, H.prdc_encoder,
                                         encoder_arch=H.prdc_encoder_arch, k=H.prdc_k, n_fake=H.prdc_n, best=H.prdc_best,
@@ -259,7 +264,7 @@ def build_run(P, script):
     return SimpleNamespace(P=P, options=options, G=G, D=D, g_ema=g_ema, opt_G=opt_G, opt_D=opt_D, reducers=reducers,
                            loader=loader, graphed=graphed, nets=nets, rank=rank, world=world, logdir=logdir, log=log,
                            starting_step=starting_step, monitor=monitor, knn_monitor=knn_monitor,
-                           prdc_monitor=prdc_monitor)
+                           prdc_monitor=prdc_monitor, contrast_monitor=contrast_monitor)
 
 
 def run_loop(run, iteration):
@@ -285,6 +290,8 @@ def run_loop(run, iteration):
                 run.monitor.update(step, run.g_ema if run.g_ema is not None else run.G, run.loader.last, P.augment_fn)
             if run.knn_monitor is not None:
                 log('[Steps %7d] [kNN Acc@1 %.3f]' % (step, run.knn_monitor.update(step, run.D)['acc@1']))
+            if run.contrast_monitor is not None:
+                log(contrast.log_line(step, run.contrast_monitor.update(step, run.D)))
             tags = ('', f'_{step}') if step % P.save_every == 0 else ('',)
             if run.prdc_monitor is not None:
                 m = run.prdc_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)

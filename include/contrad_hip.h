@@ -855,6 +855,16 @@ int contrad_mmd_sums(const float* S, long long ldS, int M, int n, long long self
  * is the only way to the two-operand kind: contrad_mmd_sums refuses every kind outside {0, 1}. */
 int contrad_dot_sums(const float* A, long long ldA, const float* B, long long ldB, int M, int n, int accumulate, double* out,
                      void* workspace, long long workspace_bytes, contrad_stream_t stream);
+/* The sum kernel with the Gaussian potential of two unit vectors (contrad_amd/contrast.py: the uniformity of Wang &
+ * Isola 2020): out[0] = (accumulate ? out[0] : 0) + sum over i < M, j < n, j != self0 + i of exp(-t * u) at
+ * u = max(2 - 2 (double)S[i][j], 0), the squared distance (a NaN stays a NaN; an s slightly above 1 gives u = 0 and a
+ * term of exactly 1; t = 0 gives the number of cells that count).  u is exact in float64; one float64 multiply and one
+ * float64 exp per term.  Layout, exclusion by index, the workspace (contrad_kid_sums_workspace_bytes(M, n)), the fixed
+ * summation order and the second launch are contrad_kid_sums's: no atomics, two calls are bitwise equal.  -EINVAL
+ * (before any GPU call) on everything contrad_kid_sums refuses (gamma and coef0 apart: there are none) and on a t that
+ * is negative, NaN or infinite.  This is the only way to this term: contrad_mmd_sums refuses every kind outside {0, 1}. */
+int contrad_gauss_sums(const float* S, long long ldS, int M, int n, long long self0, double t, int accumulate, double* out,
+                       void* workspace, long long workspace_bytes, contrad_stream_t stream);
 
 #ifdef __cplusplus
 }
