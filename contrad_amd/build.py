@@ -1,4 +1,4 @@
-"""Build csrc/*.hip into csrc/libcontrad_hip.so for gfx950 with hipcc (in-tree, no torch headers)."""
+"""Build csrc/*.hip and csrc/eval/*.hip into csrc/libcontrad_hip.so for gfx950 with hipcc (in-tree, no torch headers)."""
 import glob
 import os
 import subprocess
@@ -15,6 +15,12 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC'] + os.environ.get('CONTRAD_EXTRA_HIPCC_FLAGS', '').split()
 
 
+def eval_sources():
+    """csrc/eval/*.hip: the kernels of the evaluators that read no network (swd.hip), linked into the same two libraries.
+    They have a ledger of their own (tests/eval_ledger.py); tests/kernel_ledger.py pins csrc/*.hip alone."""
+    return sorted(glob.glob(os.path.join(CSRC, 'eval', '*.hip')))
+
+
 def _stale(target, deps):
     if not os.path.exists(target):
         return True
@@ -23,7 +29,7 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=True):
-    srcs = sorted(glob.glob(os.path.join(CSRC, '*.hip')))
+    srcs = sorted(glob.glob(os.path.join(CSRC, '*.hip'))) + eval_sources()
     hdrs = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + \
         sorted(glob.glob(os.path.join(CSRC, '..', '..', 'include', '*.h')))
     objs, dev_objs = [], []

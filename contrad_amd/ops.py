@@ -1778,3 +1778,134 @@ def images_u8(images):
     out = torch.empty((n, H, W, 3), device=images.device, dtype=torch.uint8)
     lib().call('contrad_image_grid_u8', _p(images), _p(out), n, H, W, 1, 0, 0.0, _stream())
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# sliced Wasserstein distance (csrc/eval/swd.hip): pyramid, patch gather, row sort, absolute-difference sum
+# --------------------------------------------------------------------------------------------------
+def swd_sort_tile():
+    """The floats of the row sort's LDS tile (contrad_swd_sort_tile)."""
+    return int(lib().raw('contrad_swd_sort_tile')())
+
+
+def _chk_planes(t, name, who):
+    _chk(t, name)
+    if t.dim() != 3 or t.shape[1] != t.shape[2] or t.shape[0] < 1 or t.shape[0] % 3 or not t.is_contiguous():
+        raise RuntimeError('contrad_hip: %s: %s must be a contiguous (n * 3, R, R) tensor, got %s' % (who, name, tuple(t.shape)))
+
+
+def swd_u8_planes(x_u8, out=None):
+    """uint8 NHWC (n, R, R, 3) -> fp32 planes (n * 3, R, R), plane = image * 3 + channel, the values 0 ... 255 as they are."""
+    if not torch.is_tensor(x_u8) or not x_u8.is_cuda or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3] != 3 \
+            or x_u8.shape[1] != x_u8.shape[2] or x_u8.shape[0] < 1 or not x_u8.is_contiguous():
+        raise RuntimeError('contrad_hip: swd_u8_planes: a contiguous non-empty CUDA uint8 (n, R, R, 3) tensor expected')
+    n, R = x_u8.shape[0], x_u8.shape[1]
+    if out is None:
+        out = torch.empty((n * 3, R, R), device=x_u8.device, dtype=torch.float32)
+    _chk_planes(out, 'out', 'swd_u8_planes')
+    if tuple(out.shape) != (n * 3, R, R) or out.device != x_u8.device:
+        raise RuntimeError('contrad_hip: swd_u8_planes: out must be (%d, %d, %d) on %s' % (n * 3, R, R, x_u8.device))
+    lib().call('contrad_swd_u8_planes', _p(x_u8), _p(out), ctypes.c_longlong(n), R, _stream())
+    return out
+
+
+def swd_pyr_down(fine, out=None):
+    """One Gaussian pyramid step on planes (P, R, R) -> (P, R / 2, R / 2): the 5 x 5 binomial stencil at the even coordinates,
+    mirror boundary.  contrad_swd_pyr_down's contract (include/contrad_hip.h)."""
+    _chk_planes(fine, 'fine', 'swd_pyr_down')
+    P, R = fine.shape[0], fine.shape[1]
+    if R < 4 or R % 2:
+        raise RuntimeError('contrad_hip: swd_pyr_down: an even R >= 4 expected, got %d' % R)
+    if out is None:
+        out = torch.empty((P, R // 2, R // 2), device=fine.device, dtype=torch.float32)
+    _chk_planes(out, 'out', 'swd_pyr_down')
+    if tuple(out.shape) != (P, R // 2, R // 2) or out.device != fine.device:
+        raise RuntimeError('contrad_hip: swd_pyr_down: out must be (%d, %d, %d) on %s' % (P, R // 2, R // 2, fine.device))
+    lib().call('contrad_swd_pyr_down', _p(fine), _p(out), ctypes.c_longlong(P), R, _stream())
+    return out
+
+
+def swd_pyr_up_sub(fine, coarse):
+    """fine -= up(coarse) in place (planes (P, R, R) and (P, R / 2, R / 2)): the Laplacian step.  Returns ``fine``.
+    contrad_swd_pyr_up_sub's contract (include/contrad_hip.h)."""
+    _chk_planes(fine, 'fine', 'swd_pyr_up_sub'); _chk_planes(coarse, 'coarse', 'swd_pyr_up_sub')
+    P, R = fine.shape[0], fine.shape[1]
+    if R < 4 or R % 2 or tuple(coarse.shape) != (P, R // 2, R // 2) or coarse.device != fine.device:
+        raise RuntimeError('contrad_hip: swd_pyr_up_sub: fine %s needs an even R >= 4 and coarse (%d, %d, %d) on its device, got %s'
+                           % (tuple(fine.shape), P, R // 2, R // 2, tuple(coarse.shape)))
+    lib().call('contrad_swd_pyr_up_sub', _p(fine), _p(coarse), ctypes.c_longlong(P), R, _stream())
+    return fine
+
+
+SWD_DESC = 147                                                             # 7 x 7 x 3 values of a descriptor
+SWD_BANK_ROWS = 148
+
+
+def swd_gather(level, cx, cy, nhoods, bank=None, stats=None):
+    """The 7 x 7 x 3 patches of ``level`` (planes (n * 3, R, R)) around the centres ``cx``, ``cy`` (int32 CUDA vectors of
+    n * nhoods elements, descriptor d in image d // nhoods) as the transposed bank (148, round_up(n * nhoods, 4)) -- row
+    c * 49 + dy * 7 + dx, row 147 and the padding columns zero -- and ``stats`` (6,) float64: per channel the sum and the sum
+    of squares over all descriptors and positions.  Returns (bank, stats).  contrad_swd_gather's contract."""
+    _chk_planes(level, 'level', 'swd_gather')
+    n, R, nhoods = level.shape[0] // 3, level.shape[1], int(nhoods)
+    if R < 7 or nhoods < 1:
+        raise RuntimeError('contrad_hip: swd_gather: R >= 7 and nhoods >= 1 expected, got %d, %d' % (R, nhoods))
+    n_desc = n * nhoods
+    n_pad = round_up(n_desc, 4)
+    _chk_vec(cx, 'cx', n_desc, torch.int32); _chk_vec(cy, 'cy', n_desc, torch.int32)
+    if cx is None or cy is None or cx.device != level.device or cy.device != level.device:
+        raise RuntimeError('contrad_hip: swd_gather: cx and cy must be int32 vectors on %s' % level.device)
+    if bank is None:
+        bank = torch.empty((SWD_BANK_ROWS, n_pad), device=level.device, dtype=torch.float32)
+    _chk(bank, 'bank')
+    if tuple(bank.shape) != (SWD_BANK_ROWS, n_pad) or not bank.is_contiguous() or bank.device != level.device:
+        raise RuntimeError('contrad_hip: swd_gather: bank must be a contiguous (%d, %d) tensor on %s' % (SWD_BANK_ROWS, n_pad, level.device))
+    if stats is None:
+        stats = torch.empty((6,), device=level.device, dtype=torch.float64)
+    _chk_vec(stats, 'stats', 6, torch.float64)
+    if stats.device != level.device:
+        raise RuntimeError('contrad_hip: swd_gather: stats is on %s, the level on %s' % (stats.device, level.device))
+    nbytes = lib().raw('contrad_swd_gather_workspace_bytes')(ctypes.c_longlong(n_desc))
+    if nbytes < 0:
+        raise RuntimeError('contrad_hip: bad swd_gather shape (%d)' % nbytes)
+    ws = _workspace(nbytes, level.device)
+    lib().call('contrad_swd_gather', _p(level), ctypes.c_longlong(n), R, _as_int(cx), _as_int(cy), nhoods, _p(bank),
+               ctypes.c_longlong(n_pad), _p(stats), _p(ws), ctypes.c_longlong(nbytes), _stream())
+    return bank, stats
+
+
+def swd_sort_rows(X, n):
+    """Sorts the first ``n`` columns of every row of ``X`` (R, ld >= n) ascending, in place; finite values.  Columns at or
+    behind ``n`` are neither read nor written.  Returns ``X``.  contrad_swd_sort_rows's contract (include/contrad_hip.h)."""
+    R, ld, n = _chk_S(X, n)
+    lib().call('contrad_swd_sort_rows', _p(X), ctypes.c_longlong(ld), R, n, _stream())
+    return X
+
+
+def swd_absdiff_sums(A, B, n, row_offset=None, out=None, accumulate=False):
+    """out (1,) float64: the sum over rows r and columns i < n of |A[r][i] - B[r][i] + row_offset[r]| on ``A`` (R, ldA >= n)
+    and ``B`` (R, ldB >= n), every term in float64, added in a fixed order (no atomics: two calls are bitwise equal).
+    ``row_offset``: a float64 CUDA vector of R elements (None: zero).  ``out`` / ``accumulate``: as in ``kid_sums``.
+    contrad_swd_absdiff_sums's contract (include/contrad_hip.h)."""
+    R, ldA, n = _chk_S(A, n)
+    _chk(B, 'B')
+    if B.dim() != 2 or B.shape[0] != R or B.shape[1] < n or B.device != A.device:
+        raise RuntimeError('contrad_hip: swd_absdiff_sums operands of %s and %s for n = %d (the same rows, at least n columns, '
+                           'one device)' % (tuple(A.shape), tuple(B.shape), n))
+    _chk_vec(row_offset, 'row_offset', R, torch.float64)
+    if row_offset is not None and row_offset.device != A.device:
+        raise RuntimeError('contrad_hip: row_offset is on %s, A on %s' % (row_offset.device, A.device))
+    if out is None:
+        if accumulate:
+            raise RuntimeError('contrad_hip: swd_absdiff_sums with accumulate adds to `out`')
+        out = torch.empty((1,), device=A.device, dtype=torch.float64)
+    _chk_vec(out, 'out', 1, torch.float64)
+    if out.device != A.device:
+        raise RuntimeError('contrad_hip: out is on %s, A on %s' % (out.device, A.device))
+    nbytes = lib().raw('contrad_swd_absdiff_workspace_bytes')(R, n)
+    if nbytes < 0:
+        raise RuntimeError('contrad_hip: bad swd_absdiff_sums shape (%d)' % nbytes)
+    ws = _workspace(nbytes, A.device)
+    lib().call('contrad_swd_absdiff_sums', _p(A), ctypes.c_longlong(ldA), _p(B), ctypes.c_longlong(_ld(B)), _p(row_offset), R, n,
+               1 if accumulate else 0, _p(out), _p(ws), ctypes.c_longlong(nbytes), _stream())
+    return out

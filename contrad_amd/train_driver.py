@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import config, contrast, prdc
+from . import config, contrast, prdc, swd
 from .augment import get_augment
 from .data import loader_for
 from .engine import GradAllReducer, setup_grad_exchange
@@ -74,7 +74,7 @@ def monitor_help(shows):
 def make_parser(description, layout):
     """``layout``: the script's flags in ``--help`` order -- the name of a common flag, or ``(name, kwargs)`` for a flag of
     the script's own or for what it sets differently on a common one.  The monitoring hooks' flags
-    (knn.add_hook_arguments, then prdc.add_hook_arguments, then contrast.add_hook_arguments) come last."""
+    (knn.add_hook_arguments, then prdc.add_hook_arguments, contrast.add_hook_arguments, swd.add_hook_arguments) come last."""
     parser = ArgumentParser(description=description)
     for item in layout:
         name, own = (item, {}) if isinstance(item, str) else item
@@ -82,6 +82,7 @@ def make_parser(description, layout):
     add_hook_arguments(parser)
     prdc.add_hook_arguments(parser)
     contrast.add_hook_arguments(parser)
+    swd.add_hook_arguments(parser)
     return parser
 
 
@@ -187,6 +188,7 @@ def build_run(P, script):
     opt_G, opt_D, reducers, loader, graphed, and what ``run_loop`` needs around them."""
     H = prdc.check_hook_arguments(P)                                # (refusals that need no device come first)
     C = contrast.check_hook_arguments(P)
+    W = swd.check_hook_arguments(P)
     if P.comment:
         P.comment = '_' + P.comment
     P.gin_stem = Path(P.gin_config).stem
@@ -258,13 +260,16 @@ def build_run(P, script):
                                         resumed_step=starting_step - 1, P=P, kid=H.prdc_kid,
                                         kid_kernel=H.prdc_kid_kernel, auth=H.prdc_auth, fd=H.prdc_fd,
                                         fd_iter=H.prdc_fd_iter)
+    swd_monitor = None
+    if W.swd_data and rank == 0:                                    # (no encoder: none of the --prdc_* flags is needed)
+        swd_monitor = swd.SWDMonitor(logdir, P.architecture, image_size, dev, P.seed, W.swd_data, n=W.swd_n, P=P)
     graphed, why_not = graph_gate(P, script)
     if why_not:
         log(why_not)
     return SimpleNamespace(P=P, options=options, G=G, D=D, g_ema=g_ema, opt_G=opt_G, opt_D=opt_D, reducers=reducers,
                            loader=loader, graphed=graphed, nets=nets, rank=rank, world=world, logdir=logdir, log=log,
                            starting_step=starting_step, monitor=monitor, knn_monitor=knn_monitor,
-                           prdc_monitor=prdc_monitor, contrast_monitor=contrast_monitor)
+                           prdc_monitor=prdc_monitor, contrast_monitor=contrast_monitor, swd_monitor=swd_monitor)
 
 
 def run_loop(run, iteration):
@@ -292,6 +297,8 @@ def run_loop(run, iteration):
                 log('[Steps %7d] [kNN Acc@1 %.3f]' % (step, run.knn_monitor.update(step, run.D)['acc@1']))
             if run.contrast_monitor is not None:
                 log(contrast.log_line(step, run.contrast_monitor.update(step, run.D)))
+            if run.swd_monitor is not None:
+                log(swd.log_line(step, run.swd_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)))
             tags = ('', f'_{step}') if step % P.save_every == 0 else ('',)
             if run.prdc_monitor is not None:
                 m = run.prdc_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)

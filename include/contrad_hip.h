@@ -866,6 +866,53 @@ int contrad_dot_sums(const float* A, long long ldA, const float* B, long long ld
 int contrad_gauss_sums(const float* S, long long ldS, int M, int n, long long self0, double t, int accumulate, double* out,
                        void* workspace, long long workspace_bytes, contrad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sliced Wasserstein distance on Laplacian-pyramid patches (Karras et al. 2018; csrc/eval/swd.hip, contrad_amd/swd.py,
+ * DESIGN.md section 22).  An addition of this project: the one sample-quality number here that needs no network.  Image
+ * levels are fp32 planes [n * 3][R][R] (plane = image * 3 + channel), values 0 ... 255 as the uint8 set holds them.
+ * No entry point uses an atomic: two calls are bitwise equal.
+ * ---------------------------------------------------------------------------------------------- */
+/* dst[(i * 3 + c)][y][x] = (float)src[i][y][x][c] for the uint8 NHWC set src[n][R][R][3] (exact).  -EINVAL on a null
+ * pointer, n < 1, R < 1 or R > 32768. */
+int contrad_swd_u8_planes(const void* src_u8, float* dst, long long n, int R, contrad_stream_t stream);
+/* One Gaussian pyramid step: coarse[p][y][x] = sum over dy, dx in [-2, 2] of g[dy] g[dx] fine[p][m(2y + dy)][m(2x + dx)]
+ * on `planes` planes of R x R (coarse: R/2 x R/2), g = [1 4 6 4 1] / 16 and m the mirror rule d c b | a b c d | c b a
+ * (-1 -> 1, -2 -> 2, R -> R - 2, R + 1 -> R - 3).  25 products in fp32 with exact weights, added in the order dy, dx.
+ * -EINVAL on a null pointer, fine == coarse, planes < 1, an odd R, R < 4 or R > 32768. */
+int contrad_swd_pyr_down(const float* fine, float* coarse, long long planes, int R, contrad_stream_t stream);
+/* The Laplacian step in place: fine[p][y][x] -= sum over dy, dx in [-2, 2] of 4 g[dy] g[dx] Z[m(y + dy)][m(x + dx)] with Z
+ * the zero-inserted coarse level (Z[2i][2j] = coarse[p][i][j], zero elsewhere), which is never made: the taps on odd
+ * coordinates are skipped.  -EINVAL as contrad_swd_pyr_down. */
+int contrad_swd_pyr_up_sub(float* fine, const float* coarse, long long planes, int R, contrad_stream_t stream);
+/* Bytes of workspace contrad_swd_gather needs for n_desc descriptors; -EINVAL on n_desc < 1. */
+long long contrad_swd_gather_workspace_bytes(long long n_desc);
+/* Descriptor d < n_desc = n_images * nhoods is the 7 x 7 x 3 patch of image d / nhoods around (cx[d], cy[d]) (a centre
+ * outside [3, R - 4] is clamped into it: nothing outside the level is read):
+ *   bank[c * 49 + dy * 7 + dx][d] = level[(d / nhoods) * 3 + c][cy[d] + dy - 3][cx[d] + dx - 3]
+ * on the transposed bank[148][n_pad], n_pad = n_desc rounded up to a multiple of 4; row 147 and the columns
+ * [n_desc, n_pad) are written as zero.  stats[c] / stats[3 + c] (float64): the sum / sum of squares of channel c over
+ * every descriptor and position, each value widened (the squares exact) and added in float64 in a fixed order.
+ * -EINVAL on a null pointer, n_images < 1, nhoods < 1, R < 7, an n_pad other than the rounded n_desc, a workspace that is
+ * null, smaller than the query says or not 8-byte aligned, stats not 8-byte aligned. */
+int contrad_swd_gather(const float* level, long long n_images, int R, const int* cx, const int* cy, int nhoods, float* bank,
+                       long long n_pad, double* stats, void* workspace, long long workspace_bytes, contrad_stream_t stream);
+/* The floats of the sort's LDS tile (a power of two): the row lengths around it are where contrad_swd_sort_rows changes
+ * its launch sequence. */
+int contrad_swd_sort_tile(void);
+/* Sorts each of `rows` rows X[r][0 .. n) (row stride ld >= n) ascending, in place; the values must be finite (zeros of
+ * both signs keep some order among themselves).  Nothing at or behind column n is read or written.  -EINVAL on a null X,
+ * rows < 1, n < 1, n > 2^30 or ld < n. */
+int contrad_swd_sort_rows(float* X, long long ld, int rows, int n, contrad_stream_t stream);
+/* Bytes of workspace contrad_swd_absdiff_sums needs; -EINVAL on rows < 1, n < 1 or n > 2^30. */
+long long contrad_swd_absdiff_workspace_bytes(int rows, int n);
+/* out[0] = (accumulate ? out[0] : 0) + sum over r < rows, i < n of |(double)A[r][i] - (double)B[r][i] + row_offset[r]|
+ * (row_offset null: 0), every term formed and added in float64 in a fixed order, the old value last.  Columns >= n are
+ * never read.  -EINVAL on a null A, B or out, rows < 1, n < 1, ldA < n, ldB < n, a workspace that is null, smaller than the
+ * query says or not 8-byte aligned, an out or row_offset that is not 8-byte aligned. */
+int contrad_swd_absdiff_sums(const float* A, long long ldA, const float* B, long long ldB, const double* row_offset, int rows,
+                             int n, int accumulate, double* out, void* workspace, long long workspace_bytes,
+                             contrad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

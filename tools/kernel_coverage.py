@@ -13,6 +13,7 @@ The databases run to tens of megabytes per module.  --counts-out writes, where t
 TRACE_DIR may hold such files in place of (or beside) databases, and the record is then made from them where the object files are.
 
 --ledger prints the LEDGER literal of the record (tests/kernel_ledger.py).
+--eval does all of the above for the ledger of csrc/eval/*.hip instead (tests/eval_ledger.py, profiles/eval_ledger.txt).
 
 Recording (on the GPU box, one step per parity module, kernel trace only, each under its own time limit):
     rocprofv3 --kernel-trace -f rocpd -d TRACE_DIR -o <module>_%pid% -- python -m pytest tests/<module>.py -q -m gpu
@@ -70,13 +71,20 @@ def collect(trace_dir, modules, normalise=L.normalise):
 
 
 def main(argv=None):
+    global L
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('trace_dir')
-    ap.add_argument('--out', default=L.RECORD)
+    ap.add_argument('--out', default=None, help='default: the ledger\'s own record')
     ap.add_argument('--ledger', action='store_true')
     ap.add_argument('--counts-out', metavar='DIR')
     ap.add_argument('--only', action='append', default=[], metavar='MODULE')
+    ap.add_argument('--eval', action='store_true',
+                    help='the ledger of csrc/eval/*.hip (tests/eval_ledger.py, profiles/eval_ledger.txt) in place of csrc/*.hip\'s')
     a = ap.parse_args(argv)
+    if a.eval:
+        import eval_ledger
+        L = eval_ledger
+    a.out = a.out or L.RECORD
     if a.counts_out:
         per, procs = collect(a.trace_dir, set(a.only or L.PARITY_MODULES), normalise=str)
         for m, counts in sorted(per.items()):
