@@ -10,6 +10,9 @@
  *     no host synchronisation, re-entrant; every launcher enqueues on the caller's `stream`
  *     (a hipStream_t passed as void*);
  *   - outputs and workspaces are caller-allocated;
+ *   - a workspace holds exactly what its `contrad_*_workspace_bytes` query answers (more is allowed), 16-byte aligned; its
+ *     contents on entry are undefined and mean nothing after the call returns, and nothing outside
+ *     [workspace, workspace + workspace_bytes) is written (tests/test_workspace_contract_gpu.py);
  *   - return value 0 = ok, >0 = hipError_t of the launch, <0 = -EINVAL style argument error
  *     (the Python host raises RuntimeError, mirroring TORCH_CHECK in the reference's .cpp shims).
  *

@@ -194,13 +194,18 @@ def test_diffaug_shapes_reach_both_forms():
     assert ops.lib().raw('contrad_diffaug_workspace_bytes')(5, 32, 32) == 16
 
 
-@pytest.mark.parametrize('H,W', DIFFAUG_SHAPES)
-@pytest.mark.parametrize('B', [1, 5])
-def test_diffaug_forward_and_backward_match_float64(H, W, B, margin):
+def diffaug_inputs(H, W, B):
+    """(x, gy, P) on the host: images, an upstream gradient and diffaug_rows.  (Shared with tests/test_workspace_contract_gpu.py.)"""
     gen = torch.Generator().manual_seed(H * 100 + W + B)
     x = torch.rand(B, 3, H, W, generator=gen)
     gy = torch.randn(B, 3, H, W, generator=gen)
-    P = diffaug_rows(B, H, W, seed=H + W + B)
+    return x, gy, diffaug_rows(B, H, W, seed=H + W + B)
+
+
+@pytest.mark.parametrize('H,W', DIFFAUG_SHAPES)
+@pytest.mark.parametrize('B', [1, 5])
+def test_diffaug_forward_and_backward_match_float64(H, W, B, margin):
+    x, gy, P = diffaug_inputs(H, W, B)
     for policy in POLICIES:
         bits = ops.diffaug_policy_bits(policy)
         what = '%dx%d B=%d %s' % (H, W, B, policy)

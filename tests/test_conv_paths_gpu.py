@@ -177,6 +177,28 @@ def _forced(P, mode, inp, wp, C, K, bias, ref, slope, gain, out):
                            f44=P in (9, 11), k4s2=P == 8, k3s2=P == 10)
 
 
+def case_tensors(case, dev):
+    """The operands of a PATH_CASES entry, drawn from the case's own generator: w, wp and, by mode, x / bias / add (forward),
+    gy / act (data gradient), x / gy (weight gradient).  (Shared with tests/test_workspace_contract_gpu.py.)"""
+    P, mode, split, N, H, W, C, K, k, s, p = case[:11]
+    ldx, ldy, ldw = case_lds(case)
+    d = case_desc(case)
+    g = torch.Generator().manual_seed(1000 + PATH_CASES.index(case))
+    t = {}
+    t['w'], t['wp'] = _weights(case, g, dev)
+    if mode == 0:
+        t['x'] = _input(N, H, W, C, ldx, g, dev)
+        t['bias'] = _rand((K,), g, dev, 0.3)
+        t['add'] = _input(N, d.Ho, d.Wo, K, ldy, g, dev)
+    elif mode == 1:
+        t['gy'] = _input(N, d.Ho, d.Wo, K, ldy, g, dev)
+        t['act'] = _input(N, H, W, C, ldx, g, dev)
+    else:
+        t['x'] = _input(N, H, W, C, ldx, g, dev)
+        t['gy'] = _input(N, d.Ho, d.Wo, K, ldy, g, dev)
+    return t
+
+
 @pytest.mark.parametrize('case', PATH_CASES, ids=case_id)
 def test_conv_path_matches_float64(case, margin):
     P, mode, split, N, H, W, C, K, k, s, p = case[:11]
@@ -185,12 +207,10 @@ def test_conv_path_matches_float64(case, margin):
     d = case_desc(case)
     assert lib().raw('contrad_conv2d_path')(ctypes.byref(d), mode) == P
     Ho, Wo = d.Ho, d.Wo
-    g = torch.Generator().manual_seed(1000 + PATH_CASES.index(case))
-    w, wp = _weights(case, g, dev)
+    t = case_tensors(case, dev)
+    w, wp = t['w'], t['wp']
     if mode == 0:
-        x = _input(N, H, W, C, ldx, g, dev)
-        bias = _rand((K,), g, dev, 0.3)
-        add = _input(N, Ho, Wo, K, ldy, g, dev)
+        x, bias, add = t['x'], t['bias'], t['add']
         for epi in (True, False):
             y = Guarded(N, Ho, Wo, K, ldy, float('nan'), dev)
             kw = dict(slope=SLOPE, gain=GAIN, addend=add) if epi else {}
@@ -205,8 +225,7 @@ def test_conv_path_matches_float64(case, margin):
                         GAIN if epi else 1.0, y2.t)
                 assert torch.equal(y.t, y2.t), 'the planned forward is not the kernel path %d names' % P
     elif mode == 1:
-        gy = _input(N, Ho, Wo, K, ldy, g, dev)
-        act = _input(N, H, W, C, ldx, g, dev)
+        gy, act = t['gy'], t['act']
         for epi in (True, False):
             dx = Guarded(N, H, W, C, ldx, float('nan'), dev)
             kw = dict(act_ref=act, slope=SLOPE, gain=GAIN) if epi else {}
@@ -220,8 +239,7 @@ def test_conv_path_matches_float64(case, margin):
                 _forced(P, 1, gy, wp, C, K, None, act if epi else None, SLOPE if epi else 1.0, GAIN if epi else 1.0, dx2.t)
                 assert torch.equal(dx.t, dx2.t), 'the planned data gradient is not the kernel path %d names' % P
     else:
-        x = _input(N, H, W, C, ldx, g, dev)
-        gy = _input(N, Ho, Wo, K, ldy, g, dev)
+        x, gy = t['x'], t['gy']
         refw, refb = R.wgrad(x, gy, k, k, s, p)
         refw = refw.permute(2, 3, 1, 0).reshape(k * k * C, K)         # packed layout
         # (the fused bias gradient needs C, K and the leading dimensions in multiples of 4: an argument error otherwise)

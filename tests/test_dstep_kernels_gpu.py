@@ -135,6 +135,12 @@ CONTRAST_CASES = [
 ]
 
 
+def contrast_z(N, D, mode):
+    """The normalised rows of a contrastive problem: 2N (NT-Xent) or 3N (SupCon) of them.  (Shared with
+    tests/test_workspace_contract_gpu.py.)"""
+    return F.normalize(torch.randn((2 if mode == 0 else 3) * N, D, device=DEV, generator=gen(N * 7 + D + mode)))
+
+
 @pytest.mark.parametrize('case', CONTRAST_CASES, ids=lambda c: 'N%d-D%d-m%d' % c[:3])
 def test_contrast(margin, case):
     N, D, mode, _ = case
@@ -144,7 +150,7 @@ def test_contrast(margin, case):
         assert S == 1
     temp = 0.1
     inv_temp = f32(1.0 / temp)
-    z = F.normalize(torch.randn(R_, D, device=DEV, generator=gen(N * 7 + D + mode)))
+    z = contrast_z(N, D, mode)
     loss_ref, lse_ref, dz_ref = R.contrast(z, N, mode, 1.0 / inv_temp)
     nbytes = lib().raw('contrad_contrast_workspace_bytes')(R_, D)
     ws = torch.empty((nbytes + 3) // 4, device=DEV)
@@ -365,13 +371,23 @@ RGB_FWD_CASES = [
 ]
 
 
-@pytest.mark.parametrize('case', RGB_FWD_CASES, ids=lambda c: 'N%d-%dx%d-K%d-k%d' % c[:5])
-def test_rgb_conv_fwd_wgrad(margin, case):
+def rgb_inputs(case):
+    """(img, w, bias guard, bias, gy) of an RGB_FWD_CASES entry: gy NHWC with ldy > K where the case says so and NaN in the
+    spare channels.  (Shared with tests/test_workspace_contract_gpu.py.)"""
     N, H, W, K, k, has_bias, ye, _ = case
     g = gen(N + K + k)
     img = torch.rand(N, 3, H, W, device=DEV, generator=g)
     w = torch.randn(K, 3, k, k, device=DEV, generator=g) * 0.2
     gb, bias = flat((K,), fill=torch.randn(K, device=DEV, generator=g) * 0.1) if has_bias else (None, None)
+    gyv = torch.full((N, H, W, K + ye), NAN, device=DEV)
+    gyv[..., :K] = torch.randn(N, H, W, K, device=DEV, generator=g)
+    return img, w, gb, bias, gyv[..., :K]
+
+
+@pytest.mark.parametrize('case', RGB_FWD_CASES, ids=lambda c: 'N%d-%dx%d-K%d-k%d' % c[:5])
+def test_rgb_conv_fwd_wgrad(margin, case):
+    N, H, W, K, k, has_bias, ye, _ = case
+    img, w, gb, bias, gyv = rgb_inputs(case)
     wp = packed_weight(w, 4)
     ldy = K + ye
     gy_out = Guard(N * H * W, K, ld=ldy, pr=H * W)                   # (a spare image either side)
@@ -379,9 +395,6 @@ def test_rgb_conv_fwd_wgrad(margin, case):
     ops.rgb_conv_fwd(img, wp, bias, K, k, 2.0, -1.0, SLOPE, GAIN, out=y)
     ref = R.rgb_fwd(img, w, bias, 2.0, -1.0, SLOPE, GAIN)
     # wgrad: gy NHWC with ldy > K and NaN in the spare channels; dwp rows x ldw with NaN spare rows / columns
-    gyv = torch.full((N, H, W, ldy), NAN, device=DEV)
-    gyv[..., :K] = torch.randn(N, H, W, K, device=DEV, generator=g)
-    gyv = gyv[..., :K]
     ldw = K + 8
     gdw = Guard(k * k * 3, K, ld=ldw)
     gdb, db = flat((K,))
@@ -455,14 +468,22 @@ COLSTATS_CASES = [
 ]
 
 
+def colstats_inputs(case, with_sq):
+    """(x, base) of a COLSTATS_CASES entry: the strided, possibly misaligned operand and what an accumulating case adds to
+    (None otherwise).  (Shared with tests/test_workspace_contract_gpu.py.)"""
+    M, K, ld, mis, acc, _ = case
+    x = strided(torch.randn(M, K, device=DEV, generator=gen(M + K)) + 0.25, ld, mis)
+    assert (x.data_ptr() % 16 != 0) == bool(mis)
+    base = torch.randn(2 if with_sq else 1, K, device=DEV, generator=gen(1)) * 10 if acc else None
+    return x, base
+
+
 @pytest.mark.parametrize('case', COLSTATS_CASES, ids=lambda c: 'M%d-K%d-ld%d-m%d-a%d' % c[:5])
 @pytest.mark.parametrize('with_sq', [True, False])
 def test_colstats(margin, case, with_sq):
     M, K, ld, mis, acc, _ = case
-    x = strided(torch.randn(M, K, device=DEV, generator=gen(M + K)) + 0.25, ld, mis)
-    assert (x.data_ptr() % 16 != 0) == bool(mis)
+    x, base = colstats_inputs(case, with_sq)
     nstat = 2 if with_sq else 1
-    base = torch.randn(nstat, K, device=DEV, generator=gen(1)) * 10 if acc else None
     gout, out = flat((nstat, K), fill=base)
     ops.colstats(x, with_sq=with_sq, out=out, accumulate=acc)
     ref = R.colstats(x)[:nstat]

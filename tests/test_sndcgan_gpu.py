@@ -249,11 +249,10 @@ def test_overlapped_gradient_exchange_single_rank_rccl():
             dist.destroy_process_group()
 
 
-def test_full_size_step_is_bitwise_deterministic():
-    """BASELINE size (global batch 512 -> 1536 images through D): every reduction on the path (split-K slabs, bias /
-    BatchNorm column sums, spectral-norm partials, contrastive column splits) has a fixed order, so two runs from the
-    same state and the same samples give bit-identical losses, gradients, power-iteration vectors and Adam updates --
-    and the step has the properties the loss promises (finite, GAN loss of an untrained D = 2 log 2)."""
+def _full_size_step():
+    """The set-up of the BASELINE-size eager D-step (global batch 512 -> 1536 images through D): returns ``run()``, which takes
+    one ``d_step`` from the same state on the same samples and returns (loss, penalty, gradients, parameters after Adam,
+    buffers)."""
     import argparse
     import copy
     from contrad_amd.augment import get_augment
@@ -272,8 +271,8 @@ def test_full_size_step_is_bitwise_deterministic():
     images = torch.rand(N, 3, 32, 32, device=DEV)
     z = torch.empty(N, 128).uniform_(-1, 1)
     params = aug.sample(3 * N, 32, 32)
-    outs = []
-    for _ in range(2):
+
+    def run():
         G, D = copy.deepcopy(G0), copy.deepcopy(D0)
         G.sample_latent = lambda n: z.to(DEV)
         a = copy.deepcopy(aug)
@@ -284,16 +283,49 @@ def test_full_size_step_is_bitwise_deterministic():
         set_grad(G, False); set_grad(D, True)
         d_loss, aux = d_step(P, G, D, opt, {'loss': 'nonsat', 'batch_size': N}, images, None)
         torch.cuda.synchronize()
-        outs.append((d_loss.detach().clone(), aux['penalty'].detach().clone(),
-                     [p.grad.detach().clone() for p in D.parameters()],
-                     [p.detach().clone() for p in D.parameters()],
-                     [b.detach().clone() for b in D.buffers()]))
-    a, b = outs
+        return (d_loss.detach().clone(), aux['penalty'].detach().clone(),
+                [p.grad.detach().clone() for p in D.parameters()],
+                [p.detach().clone() for p in D.parameters()],
+                [b.detach().clone() for b in D.buffers()])
+    return run
+
+
+def _same_step(a, b):
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
     for k in (2, 3, 4):
         assert len(a[k]) == len(b[k]) and all(torch.equal(x, y) for x, y in zip(a[k], b[k]))
+
+
+def test_full_size_step_is_bitwise_deterministic():
+    """BASELINE size (global batch 512 -> 1536 images through D): every reduction on the path (split-K slabs, bias /
+    BatchNorm column sums, spectral-norm partials, contrastive column splits) has a fixed order, so two runs from the
+    same state and the same samples give bit-identical losses, gradients, power-iteration vectors and Adam updates --
+    and the step has the properties the loss promises (finite, GAN loss of an untrained D = 2 log 2)."""
+    run = _full_size_step()
+    a, b = run(), run()
+    _same_step(a, b)
     assert torch.isfinite(a[0]).item() and all(torch.isfinite(g).all().item() for g in a[2])
     assert abs(a[1].item() - 2 * np.log(2)) < 0.05        # sigmoid(0) on both sides: softplus(0) * 2
+
+
+def test_full_size_step_on_exact_size_poisoned_workspaces():
+    """The same eager step with every ``ops._workspace`` request served by tests/ws_guard.py: storage of its own of exactly the
+    size asked for, 16-byte aligned, filled with quiet NaNs, between guard bands.  Loss, penalty, every gradient, every
+    parameter after Adam and every buffer equal the plain run bit for bit (the test above shows the plain run repeatable), and
+    every guard band is intact: no launch of the step writes past its workspace, reads a workspace element it did not write,
+    or relies on what an earlier call left in the shared scratch (forward for backward, one launch of a pair for the other)."""
+    from ws_guard import POISONS, WorkspaceGuard
+    run = _full_size_step()
+    plain = run()
+    with WorkspaceGuard(POISONS['qnan']) as g:
+        guarded = run()
+        g.check()
+    callers = {r.caller.split(' <- ')[-1] for r in g.log}
+    print('whole step: %d workspace requests, %.1f MB in all, from %s' % (
+        len(g.log), sum(r.nbytes for r in g.log) / 1e6, ', '.join(sorted(callers))))
+    assert {'conv2d_fwd', 'conv2d_dgrad', 'conv2d_wgrad'} <= callers
+    _same_step(plain, guarded)
+    assert torch.isfinite(guarded[0]).item() and all(torch.isfinite(x).all().item() for x in guarded[2])
 
 
 def test_generator_eval_mode_forward_matches_reference(golden):

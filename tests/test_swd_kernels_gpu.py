@@ -105,19 +105,26 @@ def test_u8_level_is_exact():
 
 
 # ---- gather ----
-@pytest.mark.parametrize('n,size,nhoods', [(3, 16, 5), (24, 32, 16), (2, 64, 300)])
-def test_gather_bitwise_and_channel_sums(margin, n, size, nhoods):
-    from contrad_amd import ops
+def _gather_inputs(n, size, nhoods):
+    """(level, pos) on the host and (planes, cx, cy) on the device.  (Shared with tests/test_workspace_contract_gpu.py.)"""
     r = np.random.RandomState(n)
     level = (r.randn(n, size, size, 3) * 40 + 7).astype(np.float32)
     n_desc = n * nhoods
-    n_pad = (n_desc + 3) // 4 * 4
     pos = r.randint(3, size - 3, (n_desc, 2)).astype(np.int32)
     pos[:4] = [(3, 3), (3, size - 4), (size - 4, 3), (size - 4, size - 4)]           # all four extreme centres
     pos[-1] = (size - 4, size - 4)
-    want = R.descriptors(level, pos, nhoods)                                           # float32 indexing: exact
     dev_level = torch.from_numpy(_planes(level)).cuda()
     cx, cy = torch.from_numpy(pos[:, 0].copy()).cuda(), torch.from_numpy(pos[:, 1].copy()).cuda()
+    return level, pos, dev_level, cx, cy
+
+
+@pytest.mark.parametrize('n,size,nhoods', [(3, 16, 5), (24, 32, 16), (2, 64, 300)])
+def test_gather_bitwise_and_channel_sums(margin, n, size, nhoods):
+    from contrad_amd import ops
+    level, pos, dev_level, cx, cy = _gather_inputs(n, size, nhoods)
+    n_desc = n * nhoods
+    n_pad = (n_desc + 3) // 4 * 4
+    want = R.descriptors(level, pos, nhoods)                                           # float32 indexing: exact
     runs = []
     for _ in range(2):
         bank, cb = _guarded((148, n_pad))
@@ -219,9 +226,8 @@ def test_pyramid_and_gather_refusals():
 
 
 # ---- abs-diff ----
-@pytest.mark.parametrize('rows,n', [(1, 1), (5, 4096), (5, 4097), (3, 10007), (128, 999)])
-def test_absdiff_against_fsum(margin, rows, n):
-    from contrad_amd import ops
+def _absdiff_inputs(rows, n):
+    """(A, B, off) on the host and the two device operands.  (Shared with tests/test_workspace_contract_gpu.py.)"""
     r = np.random.RandomState(rows + n)
     A, B = r.randn(rows, n).astype(np.float32), r.randn(rows, n).astype(np.float32)
     off = r.randn(rows) * 0.1
@@ -230,6 +236,13 @@ def test_absdiff_against_fsum(margin, rows, n):
         t = torch.full((rows, n + pad), NAN, device='cuda')
         t[:, :n] = torch.from_numpy(M).cuda()
         dev.append(t)
+    return A, B, off, dev
+
+
+@pytest.mark.parametrize('rows,n', [(1, 1), (5, 4096), (5, 4097), (3, 10007), (128, 999)])
+def test_absdiff_against_fsum(margin, rows, n):
+    from contrad_amd import ops
+    A, B, off, dev = _absdiff_inputs(rows, n)
     for o in (None, off):
         terms = R.absdiff_terms(A, B, o)
         ref, bound = R.fsum(terms), R.fsum_bound(rows * n + 1, R.fsum(terms))
