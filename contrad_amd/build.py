@@ -1,4 +1,4 @@
-"""Build csrc/*.hip and csrc/eval/*.hip into csrc/libcontrad_hip.so for gfx950 with hipcc (in-tree, no torch headers)."""
+"""Build csrc/*.hip, csrc/eval/*.hip and csrc/spectral/*.hip into csrc/libcontrad_hip.so for gfx950 with hipcc (in-tree, no torch headers)."""
 import glob
 import os
 import subprocess
@@ -21,6 +21,12 @@ def eval_sources():
     return sorted(glob.glob(os.path.join(CSRC, 'eval', '*.hip')))
 
 
+def spectral_sources():
+    """csrc/spectral/*.hip: the frequency-domain kernels (spectrum.hip), linked into the same two libraries, with a ledger of
+    their own (tests/spectral_ledger.py)."""
+    return sorted(glob.glob(os.path.join(CSRC, 'spectral', '*.hip')))
+
+
 def _stale(target, deps):
     if not os.path.exists(target):
         return True
@@ -29,7 +35,7 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=True):
-    srcs = sorted(glob.glob(os.path.join(CSRC, '*.hip'))) + eval_sources()
+    srcs = sorted(glob.glob(os.path.join(CSRC, '*.hip'))) + eval_sources() + spectral_sources()
     hdrs = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + \
         sorted(glob.glob(os.path.join(CSRC, '..', '..', 'include', '*.h')))
     objs, dev_objs = [], []

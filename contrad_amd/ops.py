@@ -1909,3 +1909,75 @@ def swd_absdiff_sums(A, B, n, row_offset=None, out=None, accumulate=False):
     lib().call('contrad_swd_absdiff_sums', _p(A), ctypes.c_longlong(ldA), _p(B), ctypes.c_longlong(_ld(B)), _p(row_offset), R, n,
                1 if accumulate else 0, _p(out), _p(ws), ctypes.c_longlong(nbytes), _stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# radial power spectrum (csrc/spectral/spectrum.hip): half-spectrum FFT of the luma, radial bin means, mean 2-D map.  None of
+# the three takes scratch: every buffer is an output.
+
+SPEC_SIDES = (16, 32, 64, 128, 256, 512)
+
+
+def _chk_spec(spec, who):
+    """A half spectrum (n, S, S / 2 + 1, 2) -> (n, S)."""
+    _chk(spec, 'spec')
+    if spec.dim() != 4 or spec.shape[0] < 1 or spec.shape[1] not in SPEC_SIDES or spec.shape[2] != spec.shape[1] // 2 + 1 \
+            or spec.shape[3] != 2 or not spec.is_contiguous():
+        raise RuntimeError('contrad_hip: %s: spec must be a contiguous (n, S, S / 2 + 1, 2) tensor with S a power of two in '
+                           '[16, 512], got %s' % (who, tuple(spec.shape)))
+    return int(spec.shape[0]), int(spec.shape[1])
+
+
+def _chk_dense(t, name, shape, dtype, device, who):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() \
+            or t.device != device:
+        raise RuntimeError('contrad_hip: %s: %s must be a contiguous %s %s tensor on %s' % (who, name, tuple(shape), dtype, device))
+
+
+def spec_rfft2(x_u8, twiddles, out=None):
+    """The half spectrum (n, S, S / 2 + 1, 2) fp32 of the exact luma (77 R + 150 G + 29 B) / 256 of a uint8 NHWC set
+    (n, S, S, 3): numpy.fft.rfft2's layout, real then imaginary part.  ``twiddles``: (S / 2, 2) fp32 on the device,
+    (cos, -sin)(2 pi j / S) (``spectrum.twiddles``).  contrad_spec_rfft2's contract (include/contrad_hip.h)."""
+    if not torch.is_tensor(x_u8) or not x_u8.is_cuda or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3] != 3 \
+            or x_u8.shape[1] != x_u8.shape[2] or x_u8.shape[0] < 1 or x_u8.shape[1] not in SPEC_SIDES or not x_u8.is_contiguous():
+        raise RuntimeError('contrad_hip: spec_rfft2: a contiguous non-empty CUDA uint8 (n, S, S, 3) tensor with S a power of two in '
+                           '[16, 512] expected')
+    n, S = int(x_u8.shape[0]), int(x_u8.shape[1])
+    _chk_dense(twiddles, 'twiddles', (S // 2, 2), torch.float32, x_u8.device, 'spec_rfft2')
+    if out is None:
+        out = torch.empty((n, S, S // 2 + 1, 2), device=x_u8.device, dtype=torch.float32)
+    _chk_dense(out, 'out', (n, S, S // 2 + 1, 2), torch.float32, x_u8.device, 'spec_rfft2')
+    lib().call('contrad_spec_rfft2', _p(x_u8), _p(twiddles), _p(out), ctypes.c_longlong(n), S, _stream())
+    return out
+
+
+def spec_radial(spec, bin_of, rcount, out=None):
+    """(n, K) float64: the mean of |spec|^2 / S^4 over the full grid's members of every radial bin, from the half spectrum
+    with weight 1 in the columns v = 0 and v = S / 2 and 2 elsewhere.  ``bin_of``: (S, S / 2 + 1) int32, ``rcount``: (K,)
+    float64 reciprocal member counts (``spectrum.bin_table``), both on the device.  contrad_spec_radial's contract."""
+    n, S = _chk_spec(spec, 'spec_radial')
+    _chk_dense(bin_of, 'bin_of', (S, S // 2 + 1), torch.int32, spec.device, 'spec_radial')
+    if not torch.is_tensor(rcount) or rcount.dim() != 1:
+        raise RuntimeError('contrad_hip: spec_radial: rcount must be a (K,) float64 vector')
+    K = int(rcount.shape[0])
+    _chk_dense(rcount, 'rcount', (K,), torch.float64, spec.device, 'spec_radial')
+    if not S // 2 + 1 <= K <= S:
+        raise RuntimeError('contrad_hip: spec_radial: %d bins for S = %d (between S / 2 + 1 and S expected)' % (K, S))
+    if out is None:
+        out = torch.empty((n, K), device=spec.device, dtype=torch.float64)
+    _chk_dense(out, 'out', (n, K), torch.float64, spec.device, 'spec_radial')
+    lib().call('contrad_spec_radial', _p(spec), _as_int(bin_of), _p(rcount), _p(out), ctypes.c_longlong(n), S, K, _stream())
+    return out
+
+
+def spec_mean_map(spec, out=None, accumulate=False):
+    """(S, S / 2 + 1) float64: the sum over the images of |spec|^2 / S^4 (a sum: the caller divides by the number of images
+    after the last chunk).  ``accumulate`` adds to ``out``.  contrad_spec_mean_map's contract (include/contrad_hip.h)."""
+    n, S = _chk_spec(spec, 'spec_mean_map')
+    if out is None:
+        if accumulate:
+            raise RuntimeError('contrad_hip: spec_mean_map with accumulate adds to `out`')
+        out = torch.empty((S, S // 2 + 1), device=spec.device, dtype=torch.float64)
+    _chk_dense(out, 'out', (S, S // 2 + 1), torch.float64, spec.device, 'spec_mean_map')
+    lib().call('contrad_spec_mean_map', _p(spec), _p(out), ctypes.c_longlong(n), S, 1 if accumulate else 0, _stream())
+    return out

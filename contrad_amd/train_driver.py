@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import config, contrast, prdc, swd
+from . import config, contrast, prdc, spectrum, swd
 from .augment import get_augment
 from .data import loader_for
 from .engine import GradAllReducer, setup_grad_exchange
@@ -74,7 +74,8 @@ def monitor_help(shows):
 def make_parser(description, layout):
     """``layout``: the script's flags in ``--help`` order -- the name of a common flag, or ``(name, kwargs)`` for a flag of
     the script's own or for what it sets differently on a common one.  The monitoring hooks' flags
-    (knn.add_hook_arguments, then prdc.add_hook_arguments, contrast.add_hook_arguments, swd.add_hook_arguments) come last."""
+    (knn.add_hook_arguments, then prdc.add_hook_arguments, contrast.add_hook_arguments, swd.add_hook_arguments,
+    spectrum.add_hook_arguments) come last."""
     parser = ArgumentParser(description=description)
     for item in layout:
         name, own = (item, {}) if isinstance(item, str) else item
@@ -83,6 +84,7 @@ def make_parser(description, layout):
     prdc.add_hook_arguments(parser)
     contrast.add_hook_arguments(parser)
     swd.add_hook_arguments(parser)
+    spectrum.add_hook_arguments(parser)
     return parser
 
 
@@ -189,6 +191,7 @@ def build_run(P, script):
     H = prdc.check_hook_arguments(P)                                # (refusals that need no device come first)
     C = contrast.check_hook_arguments(P)
     W = swd.check_hook_arguments(P)
+    F = spectrum.check_hook_arguments(P)
     if P.comment:
         P.comment = '_' + P.comment
     P.gin_stem = Path(P.gin_config).stem
@@ -263,13 +266,18 @@ def build_run(P, script):
     swd_monitor = None
     if W.swd_data and rank == 0:                                    # (no encoder: none of the --prdc_* flags is needed)
         swd_monitor = swd.SWDMonitor(logdir, P.architecture, image_size, dev, P.seed, W.swd_data, n=W.swd_n, P=P)
+    spectrum_monitor = None
+    if F.spectrum_data and rank == 0:                               # (no encoder either; the real set is transformed once, here)
+        spectrum_monitor = spectrum.SpectrumMonitor(logdir, P.architecture, image_size, dev, P.seed, F.spectrum_data,
+                                                    n=F.spectrum_n, P=P)
     graphed, why_not = graph_gate(P, script)
     if why_not:
         log(why_not)
     return SimpleNamespace(P=P, options=options, G=G, D=D, g_ema=g_ema, opt_G=opt_G, opt_D=opt_D, reducers=reducers,
                            loader=loader, graphed=graphed, nets=nets, rank=rank, world=world, logdir=logdir, log=log,
                            starting_step=starting_step, monitor=monitor, knn_monitor=knn_monitor,
-                           prdc_monitor=prdc_monitor, contrast_monitor=contrast_monitor, swd_monitor=swd_monitor)
+                           prdc_monitor=prdc_monitor, contrast_monitor=contrast_monitor, swd_monitor=swd_monitor,
+                           spectrum_monitor=spectrum_monitor)
 
 
 def run_loop(run, iteration):
@@ -299,6 +307,8 @@ def run_loop(run, iteration):
                 log(contrast.log_line(step, run.contrast_monitor.update(step, run.D)))
             if run.swd_monitor is not None:
                 log(swd.log_line(step, run.swd_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)))
+            if run.spectrum_monitor is not None:
+                log(spectrum.log_line(step, run.spectrum_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)))
             tags = ('', f'_{step}') if step % P.save_every == 0 else ('',)
             if run.prdc_monitor is not None:
                 m = run.prdc_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)

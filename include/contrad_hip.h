@@ -916,6 +916,32 @@ int contrad_swd_absdiff_sums(const float* A, long long ldA, const float* B, long
                              int n, int accumulate, double* out, void* workspace, long long workspace_bytes,
                              contrad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Radial power spectrum of uint8 images (csrc/spectral/spectrum.hip, contrad_amd/spectrum.py).  An
+ * addition of this project: the azimuthally averaged power of the luma, which shows up-sampling artefacts directly.  S is
+ * the image side, a power of two in [16, 512]; the half spectrum spec[n][S][S / 2 + 1][2] is numpy.fft.rfft2's layout
+ * (u along H, v along W, real then imaginary part).  No entry point takes scratch or uses an atomic: two calls are
+ * bitwise equal.
+ * ---------------------------------------------------------------------------------------------- */
+/* spec[i][u][v] = sum over y, x of Y_i[y][x] exp(-2 pi i (u y + v x) / S), v <= S / 2, of the exact luma
+ * Y = (77 R + 150 G + 29 B) / 256 of the uint8 NHWC set src[n][S][S][3], in fp32.  twiddles[j][2] = (cos, -sin)(2 pi j / S),
+ * j < S / 2, rounded from float64 by the caller: the device calls no sine.  |spec - exact| <= gamma_m sum |Y| with
+ * m = 15 log2 S - 22.  -EINVAL on a null pointer, an S that is no power of two in [16, 512], n < 1 or
+ * n > 2^24, src_u8 not 4-byte aligned, twiddles or spec not 8-byte aligned. */
+int contrad_spec_rfft2(const void* src_u8, const float* twiddles, float* spec, long long n, int S, contrad_stream_t stream);
+/* prof[i][k] = rcount[k] / S^4 * sum over u < S, v <= S / 2 with bin_of[u][v] == k of w(v) |spec[i][u][v]|^2, w = 1 at
+ * v = 0 and v = S / 2 and 2 elsewhere (the mean of |F|^2 / S^4 over the full grid's members of bin k when rcount[k] is the
+ * reciprocal of their number), squares and sums in float64 in a fixed order.  bin_of[S][S / 2 + 1] (int32) must not
+ * decrease along v nor along |fu| and must equal its mirror u -> S - u, as the rounded radius does; only its rows
+ * u <= S / 2 are read.  K is the number of bins.  -EINVAL on a null pointer, an S as above, n < 1 or n > 2^24, K outside
+ * [S / 2 + 1, S], spec, rcount or prof not 8-byte aligned, bin_of not 4-byte aligned. */
+int contrad_spec_radial(const float* spec, const int* bin_of, const double* rcount, double* prof, long long n, int S, int K,
+                        contrad_stream_t stream);
+/* map[u][v] = (accumulate ? map[u][v] : 0) + sum over i < n of |spec[i][u][v]|^2 / S^4 on the half spectrum, in float64,
+ * the images in a fixed order, the old value last: the caller feeds chunks of images and divides by their total number.
+ * -EINVAL on a null pointer, an S as above, n < 1 or n > 2^24, accumulate outside {0, 1}, spec or map not 8-byte aligned. */
+int contrad_spec_mean_map(const float* spec, double* map, long long n, int S, int accumulate, contrad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
