@@ -1,4 +1,4 @@
-"""Build csrc/*.hip, csrc/eval/*.hip and csrc/spectral/*.hip into csrc/libcontrad_hip.so for gfx950 with hipcc (in-tree, no torch headers)."""
+"""Build csrc/*.hip, csrc/eval/*.hip, csrc/spectral/*.hip and csrc/latent/*.hip into csrc/libcontrad_hip.so for gfx950 with hipcc (in-tree, no torch headers)."""
 import glob
 import os
 import subprocess
@@ -27,6 +27,12 @@ def spectral_sources():
     return sorted(glob.glob(os.path.join(CSRC, 'spectral', '*.hip')))
 
 
+def latent_sources():
+    """csrc/latent/*.hip: the latent-space kernels (latent.hip), linked into the same two libraries, with a ledger of their
+    own (tests/latent_ledger.py)."""
+    return sorted(glob.glob(os.path.join(CSRC, 'latent', '*.hip')))
+
+
 def _stale(target, deps):
     if not os.path.exists(target):
         return True
@@ -35,7 +41,7 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=True):
-    srcs = sorted(glob.glob(os.path.join(CSRC, '*.hip'))) + eval_sources() + spectral_sources()
+    srcs = sorted(glob.glob(os.path.join(CSRC, '*.hip'))) + eval_sources() + spectral_sources() + latent_sources()
     hdrs = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + \
         sorted(glob.glob(os.path.join(CSRC, '..', '..', 'include', '*.h')))
     objs, dev_objs = [], []

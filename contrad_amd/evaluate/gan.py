@@ -48,9 +48,10 @@ def preserved_rng(device=None):
             torch.cuda.set_rng_state(cuda, device)
 
 
-def fixed_latent(G, n, seed):
-    """``n`` latents of ``G``'s prior (G.sample_latent's distribution) from a torch.Generator of their own, on G's device."""
-    g = torch.Generator(device='cpu').manual_seed(int(seed))
+def fixed_latent(G, n, seed, generator=None):
+    """``n`` latents of ``G``'s prior (G.sample_latent's distribution) from a torch.Generator of their own, on G's device.
+    ``generator``: the caller's CPU generator, already seeded, to go on drawing from behind the latents."""
+    g = torch.Generator(device='cpu').manual_seed(int(seed)) if generator is None else generator
     dev = next(G.parameters()).device
     if hasattr(G, 'style_dim'):                                    # StyleGAN2: N(0, 1)
         return torch.randn(n, G.style_dim, generator=g).to(dev)

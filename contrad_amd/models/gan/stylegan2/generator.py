@@ -161,6 +161,25 @@ class Generator(nn.Module):
     def sample_latent(self, num_samples):
         return torch.randn(num_samples, self.style_dim, device=self.device)
 
+    def make_noise(self):
+        """One noise map (1, 1, 2^res, 2^res) per layer, res = (layer_idx + 5) // 2, to be shared by every row of a batch
+        (generator.py:214-220)."""
+        return [torch.randn(1, 1, 2 ** ((i + 5) // 2), 2 ** ((i + 5) // 2), device=self.device) for i in range(self.num_layers)]
+
+    def get_latent(self, input):
+        """The mapping network alone: z (B, style_dim) -> w (B, style_dim) (generator.py:230-231)."""
+        if not input.is_cuda:
+            raise RuntimeError('contrad_amd StyleGAN2 generator runs on the MI355X HIP path only (no CPU fallback)')
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        return self._mapping(input, self._prepared(differentiable=grad))
+
+    def mean_latent(self, n_latent):
+        """The (1, style_dim) mean of w over ``n_latent`` draws of the prior (generator.py:222-228): the centre that
+        truncation pulls towards.  The column sums are taken in float64 and rounded once (once per checkpoint: plumbing)."""
+        latent_in = torch.randn(n_latent, self.style_dim, device=self.device)
+        with torch.no_grad():
+            return self.get_latent(latent_in).double().mean(0, keepdim=True).float()
+
     def input_sizes(self, N):
         """Element counts of everything a training-mode forward draws on the device: z, the mixing latent, per-layer noise."""
         return [N * self.style_dim, N * self.style_dim] + [N * 4 ** ((i + 5) // 2) for i in range(self.num_layers)]

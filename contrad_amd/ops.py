@@ -1981,3 +1981,76 @@ def spec_mean_map(spec, out=None, accumulate=False):
     _chk_dense(out, 'out', (S, S // 2 + 1), torch.float64, spec.device, 'spec_mean_map')
     lib().call('contrad_spec_mean_map', _p(spec), _p(out), ctypes.c_longlong(n), S, 1 if accumulate else 0, _stream())
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# latent-space tools (csrc/latent/latent.hip): pairs an eps apart, per-layer styles, the float64 pair distance
+# --------------------------------------------------------------------------------------------------
+def latent_pair(a, b, t, dt, mode, out0=None, out1=None):
+    """The points of the path from row ``a[i]`` to row ``b[i]`` at ``t[i]`` and at ``t[i] + dt`` (the sum in float64), as two
+    fp32 (n, d) tensors.  ``mode``: 0 lerp, 1 the slerp of Karras et al.  contrad_latent_pair's contract
+    (include/contrad_hip.h)."""
+    if not torch.is_tensor(a) or a.dim() != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise RuntimeError('contrad_hip: latent_pair: a must be a non-empty (n, d) tensor')
+    n, d = int(a.shape[0]), int(a.shape[1])
+    _chk_dense(a, 'a', (n, d), torch.float32, a.device, 'latent_pair')
+    _chk_dense(b, 'b', (n, d), torch.float32, a.device, 'latent_pair')
+    _chk_dense(t, 't', (n,), torch.float32, a.device, 'latent_pair')
+    if mode not in (0, 1):
+        raise ValueError('latent_pair: mode 0 (lerp) or 1 (slerp) expected, got %r' % (mode,))
+    if out0 is None:
+        out0 = torch.empty((n, d), device=a.device, dtype=torch.float32)
+    if out1 is None:
+        out1 = torch.empty((n, d), device=a.device, dtype=torch.float32)
+    _chk_dense(out0, 'out0', (n, d), torch.float32, a.device, 'latent_pair')
+    _chk_dense(out1, 'out1', (n, d), torch.float32, a.device, 'latent_pair')
+    lib().call('contrad_latent_pair', _p(a), _p(b), _p(t), float(dt), int(mode), _p(out0), _p(out1), ctypes.c_longlong(n), d,
+               _stream())
+    return out0, out1
+
+
+def latent_styles(w, L, w2=None, cross=None, w_avg=None, psi=None, out=None):
+    """Per-layer latents (B, L, d): ``w_avg + psi[l] * (src - w_avg)`` with ``src = w[b]`` for the layers ``l < cross[b]`` and
+    ``w2[b]`` behind them.  ``cross``: (B,) fp32 on the device; ``w_avg``: (d,) or (1, d); ``psi``: (L,).  Without ``psi`` (and
+    in every layer whose psi is 1) the rows are the source's bits.  contrad_latent_styles's contract."""
+    if not torch.is_tensor(w) or w.dim() != 2 or w.shape[0] < 1 or w.shape[1] < 1 or int(L) < 1:
+        raise RuntimeError('contrad_hip: latent_styles: w must be a non-empty (B, d) tensor and L at least 1')
+    B, d, L = int(w.shape[0]), int(w.shape[1]), int(L)
+    _chk_dense(w, 'w', (B, d), torch.float32, w.device, 'latent_styles')
+    if (w2 is None) != (cross is None) or (w_avg is None) != (psi is None):
+        raise RuntimeError('contrad_hip: latent_styles: w2 goes with cross, w_avg with psi')
+    if w2 is not None:
+        _chk_dense(w2, 'w2', (B, d), torch.float32, w.device, 'latent_styles')
+        _chk_dense(cross, 'cross', (B,), torch.float32, w.device, 'latent_styles')
+    if psi is not None:
+        w_avg = w_avg.view(-1) if torch.is_tensor(w_avg) else w_avg
+        _chk_dense(w_avg, 'w_avg', (d,), torch.float32, w.device, 'latent_styles')
+        _chk_dense(psi, 'psi', (L,), torch.float32, w.device, 'latent_styles')
+    if out is None:
+        out = torch.empty((B, L, d), device=w.device, dtype=torch.float32)
+    _chk_dense(out, 'out', (B, L, d), torch.float32, w.device, 'latent_styles')
+    lib().call('contrad_latent_styles', _p(w), _p(w2), _p(w_avg), _p(psi), _p(cross), _p(out), B, L, d, _stream())
+    return out
+
+
+def pair_dist_resident_d():
+    """The largest row length at which ``pair_dist`` keeps both rows in LDS (contrad_pair_dist_resident_d)."""
+    return int(lib().raw('contrad_pair_dist_resident_d')())
+
+
+def pair_dist(A, B, scale=1.0, out=None):
+    """(n,) float64: ``scale * |A^_i - B^_i|^2`` of the normalised rows of two fp32 (n, d) matrices (row stride free, last
+    stride 1), the difference taken first and everything in float64.  contrad_pair_dist's contract."""
+    for name, m in (('A', A), ('B', B)):
+        if not torch.is_tensor(m) or not m.is_cuda or m.dtype != torch.float32 or m.dim() != 2 or m.shape[0] < 1 or m.shape[1] < 1 \
+                or m.stride(1) != 1 or m.stride(0) < m.shape[1]:
+            raise RuntimeError('contrad_hip: pair_dist: %s must be a non-empty CUDA float32 (n, d) matrix with unit column stride' % name)
+    if tuple(A.shape) != tuple(B.shape) or A.device != B.device:
+        raise RuntimeError('contrad_hip: pair_dist: A %s and B %s must have one shape and device' % (tuple(A.shape), tuple(B.shape)))
+    n, d = int(A.shape[0]), int(A.shape[1])
+    if out is None:
+        out = torch.empty((n,), device=A.device, dtype=torch.float64)
+    _chk_dense(out, 'out', (n,), torch.float64, A.device, 'pair_dist')
+    lib().call('contrad_pair_dist', _p(A), ctypes.c_longlong(A.stride(0)), _p(B), ctypes.c_longlong(B.stride(0)),
+               ctypes.c_longlong(n), d, float(scale), _p(out), _stream())
+    return out

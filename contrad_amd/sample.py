@@ -10,6 +10,10 @@ Additions: ``--seed`` (the tag, and ``torch.manual_seed(tag)`` before the first 
 
 The image side is one launch per batch (``ops.images_u8``, csrc/imagegrid.hip: quantisation and NCHW -> NHWC) and a D2H copy
 of the uint8 batch, a quarter of the float one; the PNG deflate runs on a small host thread pool (zlib releases the GIL).
+``--truncation PSI`` (StyleGAN2 only; with ``--truncation_n`` draws behind ``G.mean_latent`` and ``--truncation_cutoff L``)
+samples at ``w_avg + PSI (w - w_avg)`` through ``latent.truncated`` and adds ``_psi<PSI>`` to the folder tag; w_avg is drawn
+after the seed and before the first batch.  Without the flag nothing else is drawn and the output is what it was.
+
 Any state dict the generator accepts works (gen.pt, gen_best.pt, gen_ema.pt) for all four names of ``get_architecture``.
 """
 import math
@@ -21,7 +25,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import ops
+from . import latent, ops
 from .features import load_frozen
 from .hostio import write_png
 
@@ -37,6 +41,7 @@ def parse_args(argv=None):
     # additions
     parser.add_argument('--seed', default=None, type=int, help='RNG seed and directory tag (default: drawn)')
     parser.add_argument('--grid', default=0, type=int, metavar='K', help='also write grid.png of the first K samples')
+    latent.add_truncation_arguments(parser)
     return parser.parse_args(argv)
 
 
@@ -61,6 +66,7 @@ def main(argv=None):
     P = parse_args(argv)
     if P.n_samples <= 0 or P.batch_size <= 0 or P.grid < 0:
         raise ValueError('--n_samples and --batch_size must be positive, --grid non-negative')
+    latent.check_truncation_arguments(P)                           # (refused before the GPU is opened)
     if not torch.cuda.is_available():
         raise RuntimeError('sampling runs on the MI355X HIP path only (no CPU fallback)')
     dev = torch.device('cuda', 0)
@@ -70,6 +76,10 @@ def main(argv=None):
     tag = int(np.random.randint(10000)) if P.seed is None else P.seed
     torch.manual_seed(tag)
     subdir = os.path.join(str(Path(P.model_path).parent), 'samples_%d_n%d' % (tag, P.n_samples))
+    w_avg = None
+    if P.truncation is not None:
+        subdir += '_psi%g' % P.truncation
+        w_avg = G.mean_latent(P.truncation_n)
     os.makedirs(subdir, exist_ok=True)
     print('Sampling in %s' % subdir, flush=True)
 
@@ -81,7 +91,11 @@ def main(argv=None):
             offset = i * P.batch_size
             keep = min(P.batch_size, P.n_samples - offset)
             with torch.no_grad():
-                samples = G(G.sample_latent(P.batch_size)).contiguous()
+                if w_avg is None:
+                    samples = G(G.sample_latent(P.batch_size)).contiguous()
+                else:
+                    styles = latent.truncated(G, G.sample_latent(P.batch_size), P.truncation, w_avg, P.truncation_cutoff)
+                    samples = G(styles, input_is_latent=True).contiguous()
                 u8 = ops.images_u8(samples).cpu().numpy()[:keep]
                 if sum(h.shape[0] for h in head) < n_grid:         # the float images of the grid stay on the device
                     head.append(samples[:n_grid - sum(h.shape[0] for h in head)].clone())

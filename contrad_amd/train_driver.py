@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import config, contrast, prdc, spectrum, swd
+from . import config, contrast, latent, prdc, spectrum, swd
 from .augment import get_augment
 from .data import loader_for
 from .engine import GradAllReducer, setup_grad_exchange
@@ -75,7 +75,7 @@ def make_parser(description, layout):
     """``layout``: the script's flags in ``--help`` order -- the name of a common flag, or ``(name, kwargs)`` for a flag of
     the script's own or for what it sets differently on a common one.  The monitoring hooks' flags
     (knn.add_hook_arguments, then prdc.add_hook_arguments, contrast.add_hook_arguments, swd.add_hook_arguments,
-    spectrum.add_hook_arguments) come last."""
+    spectrum.add_hook_arguments, latent.add_hook_arguments) come last."""
     parser = ArgumentParser(description=description)
     for item in layout:
         name, own = (item, {}) if isinstance(item, str) else item
@@ -85,6 +85,7 @@ def make_parser(description, layout):
     contrast.add_hook_arguments(parser)
     swd.add_hook_arguments(parser)
     spectrum.add_hook_arguments(parser)
+    latent.add_hook_arguments(parser)
     return parser
 
 
@@ -192,6 +193,7 @@ def build_run(P, script):
     C = contrast.check_hook_arguments(P)
     W = swd.check_hook_arguments(P)
     F = spectrum.check_hook_arguments(P)
+    L = latent.check_hook_arguments(P)
     if P.comment:
         P.comment = '_' + P.comment
     P.gin_stem = Path(P.gin_config).stem
@@ -270,6 +272,10 @@ def build_run(P, script):
     if F.spectrum_data and rank == 0:                               # (no encoder either; the real set is transformed once, here)
         spectrum_monitor = spectrum.SpectrumMonitor(logdir, P.architecture, image_size, dev, P.seed, F.spectrum_data,
                                                     n=F.spectrum_n, P=P)
+    ppl_monitor = None
+    if L.ppl_encoder and rank == 0:                                 # (no real data: an encoder file alone)
+        ppl_monitor = latent.PPLMonitor(logdir, P.architecture, image_size, dev, P.seed, L.ppl_encoder,
+                                        encoder_arch=L.ppl_encoder_arch, n=L.ppl_n, space=L.ppl_space, P=P)
     graphed, why_not = graph_gate(P, script)
     if why_not:
         log(why_not)
@@ -277,7 +283,7 @@ def build_run(P, script):
                            loader=loader, graphed=graphed, nets=nets, rank=rank, world=world, logdir=logdir, log=log,
                            starting_step=starting_step, monitor=monitor, knn_monitor=knn_monitor,
                            prdc_monitor=prdc_monitor, contrast_monitor=contrast_monitor, swd_monitor=swd_monitor,
-                           spectrum_monitor=spectrum_monitor)
+                           spectrum_monitor=spectrum_monitor, ppl_monitor=ppl_monitor)
 
 
 def run_loop(run, iteration):
@@ -309,6 +315,8 @@ def run_loop(run, iteration):
                 log(swd.log_line(step, run.swd_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)))
             if run.spectrum_monitor is not None:
                 log(spectrum.log_line(step, run.spectrum_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)))
+            if run.ppl_monitor is not None:
+                log(latent.log_line(step, run.ppl_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)))
             tags = ('', f'_{step}') if step % P.save_every == 0 else ('',)
             if run.prdc_monitor is not None:
                 m = run.prdc_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)

@@ -942,6 +942,35 @@ int contrad_spec_radial(const float* spec, const int* bin_of, const double* rcou
  * -EINVAL on a null pointer, an S as above, n < 1 or n > 2^24, accumulate outside {0, 1}, spec or map not 8-byte aligned. */
 int contrad_spec_mean_map(const float* spec, double* map, long long n, int S, int accumulate, contrad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Latent-space tools (csrc/latent/latent.hip, contrad_amd/latent.py).  An addition of this project:
+ * pairs of latents an exact eps apart, per-layer styles with truncation and mixing, and a pair distance that takes the
+ * difference first.  No entry point takes scratch or uses an atomic: two calls are bitwise equal.
+ * ---------------------------------------------------------------------------------------------- */
+/* out0[i] = the point at t[i] and out1[i] = the point at (double)t[i] + dt of the path from row a[i] to row b[i], all fp32
+ * [n][d] dense; every intermediate is float64 and shared by both points, one rounding to fp32 at the store; dt == 0 makes
+ * out1 bitwise out0.  mode 0: a + t (b - a).  mode 1 (slerp of Karras et al.): with x^ = x / max(|x|, 1e-300),
+ * r = b^ - (a^.b^) a^, theta = atan2(|r|, a^.b^) (never acos), the point is normalize(a^ cos(t theta) + (r / |r|) sin(t theta));
+ * where |r| <= (d + 16) 2^-52 (zero to the rounding of the dot product: b = a, b = -a) the point is a^ for every t.
+ * -EINVAL on a null pointer, a mode outside {0, 1}, n < 1, n >= 2^31, d < 1, a dt that is not finite, out0 == out1. */
+int contrad_latent_pair(const float* a, const float* b, const float* t, double dt, int mode, float* out0, float* out1,
+                        long long n, int d, contrad_stream_t stream);
+/* out[b][l][:] = w_avg + psi[l] (src - w_avg) in fp32, src = w[b] if l < cross[b] else w2[b]; w, w2 [B][d], w_avg [d], psi [L],
+ * cross [B] fp32 (layer counts as floats, the way the generator takes its mixing layers), out [B][L][d].  w2 and cross may
+ * both be null (no mixing), w_avg and psi may both be null (no truncation).  A layer with psi[l] == 1, and every layer
+ * without psi, holds the bits of the source row.  -EINVAL on a null w or out, B, L or d < 1, w2 without cross or cross
+ * without w2, w_avg without psi or psi without w_avg. */
+int contrad_latent_styles(const float* w, const float* w2, const float* w_avg, const float* psi, const float* cross, float* out,
+                          int B, int L, int d, contrad_stream_t stream);
+/* The largest d at which contrad_pair_dist keeps both rows in LDS between its two passes; above it the rows are read twice. */
+int contrad_pair_dist_resident_d(void);
+/* out[i] = scale * |A^_i - B^_i|^2 in float64, x^ = x / max(|x|, 1e-12), rows A[i] at A + i ldA and B[i] at B + i ldB, d
+ * fp32 values each: norms, quotients, differences, squares and sums in float64 in a fixed order, so equal rows give exactly
+ * 0.  Columns >= d are never read.  -EINVAL on a null pointer, n < 1, n >= 2^31, d < 1, ldA < d, ldB < d, a scale that is
+ * not finite, an out that is not 8-byte aligned. */
+int contrad_pair_dist(const float* A, long long ldA, const float* B, long long ldB, long long n, int d, double scale, double* out,
+                      contrad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

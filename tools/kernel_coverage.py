@@ -15,6 +15,7 @@ TRACE_DIR may hold such files in place of (or beside) databases, and the record 
 --ledger prints the LEDGER literal of the record (tests/kernel_ledger.py).
 --eval does all of the above for the ledger of csrc/eval/*.hip instead (tests/eval_ledger.py, profiles/eval_ledger.txt).
 --spectral does it for the ledger of csrc/spectral/*.hip (tests/spectral_ledger.py, profiles/spectral_ledger.txt).
+--latent does it for the ledger of csrc/latent/*.hip (tests/latent_ledger.py, profiles/latent_ledger.txt).
 
 Recording (on the GPU box, one step per parity module, kernel trace only, each under its own time limit):
     rocprofv3 --kernel-trace -f rocpd -d TRACE_DIR -o <module>_%pid% -- python -m pytest tests/<module>.py -q -m gpu
@@ -83,15 +84,20 @@ def main(argv=None):
                     help='the ledger of csrc/eval/*.hip (tests/eval_ledger.py, profiles/eval_ledger.txt) in place of csrc/*.hip\'s')
     ap.add_argument('--spectral', action='store_true',
                     help='the ledger of csrc/spectral/*.hip (tests/spectral_ledger.py, profiles/spectral_ledger.txt)')
+    ap.add_argument('--latent', action='store_true',
+                    help='the ledger of csrc/latent/*.hip (tests/latent_ledger.py, profiles/latent_ledger.txt)')
     a = ap.parse_args(argv)
-    if a.eval and a.spectral:
-        ap.error('--eval and --spectral name two ledgers: one run writes one record')
+    if a.eval + a.spectral + a.latent > 1:
+        ap.error('--eval, --spectral and --latent name three ledgers: one run writes one record')
     if a.eval:
         import eval_ledger
         L = eval_ledger
     if a.spectral:
         import spectral_ledger
         L = spectral_ledger
+    if a.latent:
+        import latent_ledger
+        L = latent_ledger
     a.out = a.out or L.RECORD
     if a.counts_out:
         per, procs = collect(a.trace_dir, set(a.only or L.PARITY_MODULES), normalise=str)
