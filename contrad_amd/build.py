@@ -1,4 +1,4 @@
-"""Build csrc/*.hip, csrc/eval/*.hip, csrc/spectral/*.hip and csrc/latent/*.hip into csrc/libcontrad_hip.so for gfx950 with hipcc (in-tree, no torch headers)."""
+"""Build csrc/*.hip, csrc/eval/*.hip, csrc/spectral/*.hip, csrc/latent/*.hip and csrc/project/*.hip into csrc/libcontrad_hip.so for gfx950 with hipcc (in-tree, no torch headers)."""
 import glob
 import os
 import subprocess
@@ -33,6 +33,12 @@ def latent_sources():
     return sorted(glob.glob(os.path.join(CSRC, 'latent', '*.hip')))
 
 
+def project_sources():
+    """csrc/project/*.hip: the loss ends of the StyleGAN2 projector (project.hip), linked into the same two libraries, with a
+    ledger of their own (tests/project_ledger.py)."""
+    return sorted(glob.glob(os.path.join(CSRC, 'project', '*.hip')))
+
+
 def _stale(target, deps):
     if not os.path.exists(target):
         return True
@@ -41,7 +47,8 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=True):
-    srcs = sorted(glob.glob(os.path.join(CSRC, '*.hip'))) + eval_sources() + spectral_sources() + latent_sources()
+    srcs = sorted(glob.glob(os.path.join(CSRC, '*.hip'))) + eval_sources() + spectral_sources() + latent_sources() + \
+        project_sources()
     hdrs = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + \
         sorted(glob.glob(os.path.join(CSRC, '..', '..', 'include', '*.h')))
     objs, dev_objs = [], []

@@ -447,7 +447,50 @@ def walk_parse_args(argv=None):
                         help='with --mix: the layers below L come from the row source (default: half of them)')
     add_truncation_arguments(parser, cutoff=False)
     parser.add_argument('--seed', default=None, type=int, help="the tag of the output files and the latents' seed (default: drawn)")
+    parser.add_argument('--latents', default=None, type=str, metavar='NPZ',
+                        help='StyleGAN2 only: walk between projected codes instead of draws -- the w (n, n_latent, D) of a '
+                             'project_<seed>.npz (test_gan_project.py); row r of the sheet is the lerp in W+ from chosen code r to '
+                             'chosen code r + 1 (--pairs, --space and --truncation do not apply)')
+    parser.add_argument('--latent_rows', default=None, type=int, nargs='+', metavar='I',
+                        help='with --latents: the codes to walk through, in order (default: all of them)')
     return parser.parse_args(argv)
+
+
+def load_projected(path, rows=None):
+    """The chosen codes of a ``project_<seed>.npz`` as float32 numpy [k, n_latent, D], k >= 2 (no device needed)."""
+    with np.load(path) as f:
+        if 'w' not in f.files:
+            raise ValueError('%s holds no w (a project_<seed>.npz of test_gan_project.py expected)' % path)
+        w = np.asarray(f['w'])
+    if w.ndim != 3 or w.dtype != np.float32:
+        raise ValueError('%s: w must be float32 (n, n_latent, D), got %s %s' % (path, w.dtype, w.shape))
+    rows = list(range(len(w))) if rows is None else [int(r) for r in rows]
+    if len(rows) < 2:
+        raise ValueError('--latents walks between consecutive codes: at least two rows expected, got %r' % (rows,))
+    for r in rows:
+        if not 0 <= r < len(w):
+            raise ValueError('--latent_rows %d: %s holds %d codes' % (r, path, len(w)))
+    return np.ascontiguousarray(w[rows])
+
+
+def walk_sheet_between(G, codes, steps=9, seed=0, padding=2):
+    """The sheet of the lerps in W+ between consecutive ``codes`` [k, n_latent, D] (on the device): k - 1 rows, columns at equal
+    steps of t, all cells at the one ``shared_noise`` list of ``seed``.  The first and last cell of a row are the codes' own
+    bits (``ops.latent_pair``'s lerp at t = 0 and 1)."""
+    need_w(G, 'walk_sheet_between')
+    if G.training:
+        raise RuntimeError('latent.walk_sheet_between: G must be in eval mode')
+    if codes.dim() != 3 or codes.shape[0] < 2 or tuple(codes.shape[1:]) != (G.n_latent, G.style_dim) or steps < 2:
+        raise ValueError('latent.walk_sheet_between: at least two codes of (%d, %d) and two steps expected' % (G.n_latent, G.style_dim))
+    dev = next(G.parameters()).device
+    k = codes.shape[0]
+    flat = codes.to(dev).float().reshape(k, -1)
+    with torch.no_grad(), preserved_rng(dev):
+        noise = shared_noise(G, seed, dev)
+        t = upload(torch.linspace(0.0, 1.0, steps, dtype=torch.float64).float().repeat(k - 1).view(-1, 1), dev).view(-1)
+        x0, _x1 = ops.latent_pair(flat[:-1].repeat_interleave(steps, 0).contiguous(), flat[1:].repeat_interleave(steps, 0).contiguous(),
+                                  t, 0.0, 0)
+        return ops.image_grid_u8(images_of(G, x0.view(-1, G.n_latent, G.style_dim), 'w', noise), nrow=steps, padding=padding)
 
 
 def walk_main(argv=None):
@@ -465,9 +508,21 @@ def walk_main(argv=None):
         raise ValueError('--cross does nothing without --mix')
     if P.cross is not None and P.cross < 0:
         raise ValueError('--cross must not be negative, got %r' % (P.cross,))
+    codes = None
+    if P.latent_rows is not None and P.latents is None:
+        raise ValueError('--latent_rows does nothing without --latents FILE.npz')
+    if P.latents is not None:
+        if P.architecture not in STYLE_ARCHITECTURES:
+            raise ValueError('--latents holds W+ codes: %s has no W (StyleGAN2 only)' % P.architecture)
+        codes = load_projected(P.latents, P.latent_rows)
     dev = _open_device('Latent walks run')
     seed = int(np.random.randint(10000)) if P.seed is None else P.seed
     G = load_generator(P.model_path, P.architecture, dev)
+    if codes is not None:
+        path = os.path.join(Path(P.model_path).parent, 'walk_%d.png' % seed)
+        write_png(path, walk_sheet_between(G, torch.from_numpy(codes), P.steps, seed).cpu().numpy())
+        print('Wrote %s' % path, flush=True)
+        return [path]
     w_avg = None
     if P.truncation is not None:
         with preserved_rng(dev):

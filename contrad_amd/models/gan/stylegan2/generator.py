@@ -535,6 +535,56 @@ class Generator(nn.Module):
                                   out_scale=0.5 if final else 1.0, out_shift=0.5 if final else 0.0,
                                   mod=s, residual=res)
 
+    def synthesize(self, latents, noise, noise_grad=False):
+        """The synthesis network alone on the differentiable path, for given per-layer latents (B, n_latent, D) and a given
+        noise list (one (B or 1, 1, R, R) map per layer): the image 0.5 * skip + 0.5, not clamped -- the
+        ``_styled_conv_grad`` / ``_to_rgb_grad`` chain of ``forward``, run whether or not any parameter requires a gradient
+        (the nodes honour ``needs_input_grad``: a frozen G pays for no weight gradient, and its prepared tables are cached
+        on the parameters' version counters).  ``noise_grad``: the maps receive gradients too
+        (``project_nodes.styled_conv_noise``).  The projector's forward (contrad_amd/project.py)."""
+        if not latents.is_cuda:
+            raise RuntimeError('contrad_amd StyleGAN2 generator runs on the MI355X HIP path only (no CPU fallback)')
+        if latents.dim() != 3 or latents.shape[1] != self.n_latent or latents.shape[2] != self.style_dim:
+            raise ValueError('synthesize: latents of (B, %d, %d) expected, got %s' % (self.n_latent, self.style_dim, tuple(latents.shape)))
+        if noise is None or len(noise) != self.num_layers:
+            raise ValueError('synthesize: a list of %d noise maps expected' % self.num_layers)
+        params = list(self.parameters())
+        if any(p.requires_grad for p in params) and torch.is_grad_enabled():
+            c = self._prepared(differentiable=True)
+        else:
+            key = tuple((p.data_ptr(), p._version) for p in params)
+            if getattr(self, '_synth_key', None) != key:
+                with torch.no_grad():
+                    self._synth_cache, self._synth_key = self._prepared(differentiable=True), key
+            c = self._synth_cache
+        rec = getattr(self, '_record_regions', None)       # test hook: a list that receives every styled layer's output (NHWC),
+        #                                                    whose signs are the leaky-relu regions this forward ran on
+        if noise_grad:
+            from ....project_nodes import styled_conv_noise
+
+            def conv(layer, x, w_lat, nz):
+                return styled_conv_noise(self, layer, x, w_lat, nz, c)
+        else:
+            def conv(layer, x, w_lat, nz):
+                return self._styled_conv_grad(layer, x, w_lat, nz, c)
+
+        def styled(layer, x, w_lat, nz):
+            y = conv(layer, x, w_lat, nz)
+            if rec is not None:
+                rec.append(y.detach())
+            return y
+        B = latents.shape[0]
+        x = self.input.const.permute(0, 2, 3, 1).expand(B, -1, -1, -1).contiguous()        # NHWC const input
+        x = styled(self.conv1, x, latents[:, 0], noise[0])
+        skip = self._to_rgb_grad(self.to_rgb1, x, latents[:, 1], None, c)
+        idx = 1
+        for j in range(len(self.to_rgbs)):
+            x = styled(self.layers[2 * j], x, latents[:, idx], noise[1 + 2 * j])
+            x = styled(self.layers[2 * j + 1], x, latents[:, idx + 1], noise[2 + 2 * j])
+            skip = self._to_rgb_grad(self.to_rgbs[j], x, latents[:, idx + 2], skip, c)
+            idx += 2
+        return 0.5 * skip + 0.5
+
     def forward(self, input, return_latents=False, style_mix=0.9, input_is_latent=False, noise=None, _mix=None):
         if not input.is_cuda:
             raise RuntimeError('contrad_amd StyleGAN2 generator runs on the MI355X HIP path only (no CPU fallback)')

@@ -2054,3 +2054,116 @@ def pair_dist(A, B, scale=1.0, out=None):
     lib().call('contrad_pair_dist', _p(A), ctypes.c_longlong(A.stride(0)), _p(B), ctypes.c_longlong(B.stride(0)),
                ctypes.c_longlong(n), d, float(scale), _p(out), _stream())
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# StyleGAN2 projector (csrc/project/project.hip): the image end of the pixel-pyramid loss, the noise maps' gradient, the noise
+# regulariser and the noise normalisation.  Scratch is a plain tensor sized by the formulas of include/contrad_hip.h.
+# --------------------------------------------------------------------------------------------------
+PROJ_MAX_LEVELS = 4
+
+
+def proj_image_end_partial_floats(L, N, H, W):
+    """Floats of ``proj_image_end``'s scratch: L * N * 3 * (H / rows), rows = 2^(L-1) doubled while 2 rows W <= 4096 and
+    2 rows divides H (contrad_proj_image_end's contract)."""
+    rows = 1 << (L - 1)
+    while rows * 2 * W <= 4096 and H % (rows * 2) == 0:
+        rows *= 2
+    return L * N * 3 * (H // rows)
+
+
+def proj_image_end(x, target, level_weights, pix=None, gx=None, partial=None):
+    """(pix, gx): the rows ``pix[l][n] = mean(pool_l(x[n] - target[n]) ** 2)`` as an (L, N) tensor and
+    ``gx = d sum_n sum_l level_weights[l] pix[l][n] / d x`` for NCHW fp32 ``x`` and ``target`` (N, 3, H, W); ``level_weights``:
+    1 to 4 host floats.  contrad_proj_image_end's contract (include/contrad_hip.h)."""
+    lam = [float(v) for v in level_weights]
+    L = len(lam)
+    if not 1 <= L <= PROJ_MAX_LEVELS:
+        raise ValueError('proj_image_end: 1 to %d level weights expected, got %d' % (PROJ_MAX_LEVELS, L))
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
+        raise RuntimeError('contrad_hip: proj_image_end: x must be a non-empty (N, 3, H, W) tensor')
+    N, _, H, W = (int(v) for v in x.shape)
+    _chk_dense(x, 'x', (N, 3, H, W), torch.float32, x.device, 'proj_image_end')
+    _chk_dense(target, 'target', (N, 3, H, W), torch.float32, x.device, 'proj_image_end')
+    T = 1 << (L - 1)
+    if H % T or W % T:
+        raise RuntimeError('contrad_hip: proj_image_end: %d levels need H and W divisible by %d, got %d x %d' % (L, T, H, W))
+    if pix is None:
+        pix = torch.empty((L, N), device=x.device, dtype=torch.float32)
+    if gx is None:
+        gx = torch.empty_like(x)
+    nfl = proj_image_end_partial_floats(L, N, H, W)
+    if partial is None:
+        partial = torch.empty((nfl,), device=x.device, dtype=torch.float32)
+    _chk_dense(pix, 'pix', (L, N), torch.float32, x.device, 'proj_image_end')
+    _chk_dense(gx, 'gx', (N, 3, H, W), torch.float32, x.device, 'proj_image_end')
+    _chk_dense(partial, 'partial', (nfl,), torch.float32, x.device, 'proj_image_end')
+    lib().call('contrad_proj_image_end', _p(x), _p(target), (ctypes.c_float * L)(*lam), L, _p(pix), _p(gx), _p(partial),
+               ctypes.c_longlong(nfl), N, H, W, _stream())
+    return pix, gx
+
+
+def proj_noise_grad(g_pre, noise_w, out=None):
+    """(B, 1, H, W): ``noise_w * sum_k g_pre[b, h, w, k]`` of an NHWC gradient (B, H, W, K); ``noise_w``: the (1,) noise
+    strength on the device.  contrad_proj_noise_grad's contract."""
+    if not torch.is_tensor(g_pre) or g_pre.dim() != 4 or g_pre.numel() < 1:
+        raise RuntimeError('contrad_hip: proj_noise_grad: g_pre must be a non-empty NHWC (B, H, W, K) tensor')
+    B, H, W, K = (int(v) for v in g_pre.shape)
+    _chk_dense(g_pre, 'g_pre', (B, H, W, K), torch.float32, g_pre.device, 'proj_noise_grad')
+    _chk_dense(noise_w, 'noise_w', (1,), torch.float32, g_pre.device, 'proj_noise_grad')
+    if out is None:
+        out = torch.empty((B, 1, H, W), device=g_pre.device, dtype=torch.float32)
+    _chk_dense(out, 'out', (B, 1, H, W), torch.float32, g_pre.device, 'proj_noise_grad')
+    lib().call('contrad_proj_noise_grad', _p(g_pre), _p(noise_w), _p(out), ctypes.c_longlong(B * H * W), K, _stream())
+    return out
+
+
+def proj_noise_levels(R):
+    """Levels of the noise regulariser on an R x R map: pooled while the side is above 8, the first level of side <= 8 counted."""
+    J = 1
+    while R > 8:
+        R //= 2
+        J += 1
+    return J
+
+
+def proj_noise_reg_scratch_floats(N, R):
+    """Floats of ``proj_noise_reg``'s scratch: N * (sum_{j=1}^{J-1} (R / 2^j)^2 + 2 J ceil(R^2 / 4096) + 2 J)
+    (contrad_proj_noise_reg's contract)."""
+    J = proj_noise_levels(R)
+    return N * (sum((R >> j) ** 2 for j in range(1, J)) + 2 * J * (-(-R * R // 4096)) + 2 * J)
+
+
+def _chk_noise_map(m, who):
+    if not torch.is_tensor(m) or m.dim() != 4 or m.shape[0] < 1 or m.shape[1] != 1 or m.shape[2] != m.shape[3]:
+        raise RuntimeError('contrad_hip: %s: a non-empty (N, 1, R, R) map set expected' % who)
+    N, R = int(m.shape[0]), int(m.shape[2])
+    if R < 4 or R > 1024 or R & (R - 1):
+        raise RuntimeError('contrad_hip: %s: R must be a power of two in [4, 1024], got %d' % (who, R))
+    _chk_dense(m, 'map', (N, 1, R, R), torch.float32, m.device, who)
+    return N, R
+
+
+def proj_noise_reg(noise, g_acc, scale=1.0, reg=None, scratch=None):
+    """reg (N,): the StyleGAN2 noise regulariser of every map of ``noise`` (N, 1, R, R); ``g_acc`` (same shape) receives
+    ``+= scale * d reg[n] / d noise`` in place.  contrad_proj_noise_reg's contract."""
+    N, R = _chk_noise_map(noise, 'proj_noise_reg')
+    _chk_dense(g_acc, 'g_acc', (N, 1, R, R), torch.float32, noise.device, 'proj_noise_reg')
+    if reg is None:
+        reg = torch.empty((N,), device=noise.device, dtype=torch.float32)
+    nfl = proj_noise_reg_scratch_floats(N, R)
+    if scratch is None:
+        scratch = torch.empty((nfl,), device=noise.device, dtype=torch.float32)
+    _chk_dense(reg, 'reg', (N,), torch.float32, noise.device, 'proj_noise_reg')
+    _chk_dense(scratch, 'scratch', (nfl,), torch.float32, noise.device, 'proj_noise_reg')
+    lib().call('contrad_proj_noise_reg', _p(noise), _p(reg), _p(g_acc), float(scale), _p(scratch), ctypes.c_longlong(nfl), N, R,
+               _stream())
+    return reg
+
+
+def proj_noise_normalize_(noise):
+    """In place per map of ``noise`` (N, 1, R, R): subtract the mean, divide by the root of the mean square; a map of zero
+    variance becomes zeros.  contrad_proj_noise_normalize's contract."""
+    N, R = _chk_noise_map(noise, 'proj_noise_normalize_')
+    lib().call('contrad_proj_noise_normalize', _p(noise), N, R, _stream())
+    return noise

@@ -971,6 +971,40 @@ int contrad_pair_dist_resident_d(void);
 int contrad_pair_dist(const float* A, long long ldA, const float* B, long long ldB, long long n, int d, double scale, double* out,
                       contrad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * StyleGAN2 projector (csrc/project/project.hip, contrad_amd/project.py).  An addition of this project:
+ * the loss ends of projecting an image onto the generator (Karras et al. 2020, appendix D) under a pixel-pyramid loss.  fp32
+ * storage and accumulation, every sum in a fixed order, no atomics: two calls are bitwise equal.  Scratch is a caller-owned
+ * array passed with its length in floats (no size query): contents undefined on entry, nothing outside it is written.
+ * ---------------------------------------------------------------------------------------------- */
+/* pix[l][n] = mean over the 3 (H / 2^l) (W / 2^l) values of pool_l(x[n] - target[n])^2, l < L, pool_l the 2^l x 2^l mean
+ * (each level from the one below: ((a + b) + (c + d)) / 4), and gx = d sum_n sum_l lam[l] pix[l][n] / d x
+ * = (2 / 3HW) sum_l lam[l] pool_l(x - target)[the tile of the pixel].  x, target, gx fp32 [N][3][H][W] dense; lam: L floats in
+ * HOST memory; pix [L][N].  partial: scratch of at least L * N * 3 * (H / rows) floats, rows = T = 2^(L-1) doubled while
+ * 2 rows W <= 4096 and 2 rows divides H (L * N * 3 * H / T always suffices).  x == target gives exact zeros everywhere.
+ * -EINVAL on a null pointer, L outside [1, 4], N < 1 or N > 65535, H or W not divisible by 2^(L-1), 2^(L-1) W > 8192, a lam
+ * that is not finite, gx aliasing an input, a partial that is too short. */
+int contrad_proj_image_end(const float* x, const float* target, const float* lam, int L, float* pix, float* gx, float* partial,
+                           long long partial_floats, int N, int H, int W, contrad_stream_t stream);
+/* g_noise[p] = noise_w[0] * sum_k g_pre[p][k] over the P rows of K channels of an NHWC gradient (the noise map's gradient
+ * behind the modulated-conv epilogue); noise_w is read from device memory.  -EINVAL on a null pointer, P < 1 or P > 2^40,
+ * K < 1 or K > 65536. */
+int contrad_proj_noise_grad(const float* g_pre, const float* noise_w, float* g_noise, long long P, int K, contrad_stream_t stream);
+/* The StyleGAN2 noise regulariser of one map set map[N][1][R][R], R a power of two in [4, 1024]: m_0 = map,
+ * m_{j+1} = avgpool2(m_j) while the side is above 8 (the first level of side <= 8 is the last: J = 1 for R <= 8, else
+ * log2 R - 2), a_j = mean(m_j roll(m_j, 1, W)), b_j = mean(m_j roll(m_j, 1, H)) with circular rolls,
+ * reg[n] = sum_j a_j^2 + b_j^2, and g_acc[n][h][w] += scale * d reg[n] / d map[n][h][w] (g_acc is read, then written).
+ * scratch: at least N * (sum_{j=1}^{J-1} (R / 2^j)^2 + 2 J ceil(R^2 / 4096) + 2 J) floats, 16-byte aligned: the pooled
+ * levels, the partial sums per level, a_j and b_j.  -EINVAL on a null pointer, N < 1 or N > 65535, such an R, a map or scratch
+ * off 16 bytes, a scale that is not finite, g_acc == map, a scratch that is too short. */
+int contrad_proj_noise_reg(const float* map, float* reg, float* g_acc, float scale, float* scratch, long long scratch_floats, int N,
+                           int R, contrad_stream_t stream);
+/* In place on map[N][1][R][R], per image: m -= mean(m), then m *= 1 / sqrt(mean(m^2)); a map whose centred square mean is 0
+ * becomes all zeros (the paper's code would divide by zero).  The mean is formed about the first element,
+ * m[0] + mean(m - m[0]), so a constant map centres to exact zeros.  -EINVAL on a null pointer, N < 1, R no power of two in
+ * [4, 1024], a map off 16 bytes. */
+int contrad_proj_noise_normalize(float* map, int N, int R, contrad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ TRACE_DIR may hold such files in place of (or beside) databases, and the record 
 --eval does all of the above for the ledger of csrc/eval/*.hip instead (tests/eval_ledger.py, profiles/eval_ledger.txt).
 --spectral does it for the ledger of csrc/spectral/*.hip (tests/spectral_ledger.py, profiles/spectral_ledger.txt).
 --latent does it for the ledger of csrc/latent/*.hip (tests/latent_ledger.py, profiles/latent_ledger.txt).
+--project does it for the ledger of csrc/project/*.hip (tests/project_ledger.py, profiles/project_ledger.txt).
 
 Recording (on the GPU box, one step per parity module, kernel trace only, each under its own time limit):
     rocprofv3 --kernel-trace -f rocpd -d TRACE_DIR -o <module>_%pid% -- python -m pytest tests/<module>.py -q -m gpu
@@ -86,9 +87,11 @@ def main(argv=None):
                     help='the ledger of csrc/spectral/*.hip (tests/spectral_ledger.py, profiles/spectral_ledger.txt)')
     ap.add_argument('--latent', action='store_true',
                     help='the ledger of csrc/latent/*.hip (tests/latent_ledger.py, profiles/latent_ledger.txt)')
+    ap.add_argument('--project', action='store_true',
+                    help='the ledger of csrc/project/*.hip (tests/project_ledger.py, profiles/project_ledger.txt)')
     a = ap.parse_args(argv)
-    if a.eval + a.spectral + a.latent > 1:
-        ap.error('--eval, --spectral and --latent name three ledgers: one run writes one record')
+    if a.eval + a.spectral + a.latent + a.project > 1:
+        ap.error('--eval, --spectral, --latent and --project name four ledgers: one run writes one record')
     if a.eval:
         import eval_ledger
         L = eval_ledger
@@ -98,6 +101,9 @@ def main(argv=None):
     if a.latent:
         import latent_ledger
         L = latent_ledger
+    if a.project:
+        import project_ledger
+        L = project_ledger
     a.out = a.out or L.RECORD
     if a.counts_out:
         per, procs = collect(a.trace_dir, set(a.only or L.PARITY_MODULES), normalise=str)
