@@ -31,22 +31,22 @@ penultimate space (keys ``align_pen``, ``uniform_pen``).
     ``ops.prdc_count`` pass counts exactly in integers, and the positive's own hit is subtracted.
 
 The device is read once, at the end.  ``--contrast_data`` of the training scripts runs this at every ``--evaluate_every``
-through ``ContrastMonitor``, which follows ``KNNMonitor``: a discriminator of its own, so that the training trajectory does
-not move by a bit.
+through ``ContrastMonitor`` (evaluate/gan.py's ``WeightsMonitor``: a discriminator of its own, so that the training
+trajectory does not move by a bit).
 """
 import inspect
 import json
 import math
 import os
-from argparse import SUPPRESS, ArgumentParser
+from argparse import ArgumentParser
 from pathlib import Path
-from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import config, features, ops
-from .evaluate.gan import eval_seed_of, own_network, preserved_rng
+from .evaluate.gan import WeightsMonitor, load_x_train, own_network, preserved_rng
+from .hooks import Hook
 
 KEYS = ('nt_xent', 'acc@1', 'acc@5', 'rank_mean', 'align', 'uniform', 'align_pen', 'uniform_pen')
 CSV_HEADER = 'step,' + ','.join(KEYS)
@@ -209,13 +209,11 @@ def log_line(step, out):
             % (step, out['nt_xent'], out['acc@1'], out['acc@5'], out['chance'], out['rank_mean'], out['align'], out['uniform']))
 
 
-class ContrastMonitor(object):
+class ContrastMonitor(WeightsMonitor):
     """``--contrast_data`` on rank 0: the diagnostics of the training discriminator's weights at every evaluation, appended
-    as ``step,nt_xent,acc@1,acc@5,rank_mean,align,uniform,align_pen,uniform_pen`` to ``contrast_<eval_seed>.csv``.  Like
-    ``KNNMonitor`` it owns its module (built inside ``preserved_rng``, always in eval mode, never requiring grad) and loads
-    the training D's state dict at each evaluation: D's mode, u / v, packed-weight caches and captured graphs are not
-    touched; the views are drawn from host generators seeded with the evaluation seed and restored afterwards.  ``aug`` /
-    ``temp`` default to the run's (``P.augment_fn``, ``P.temp``); ``batch`` is the run's training batch."""
+    as ``step,nt_xent,acc@1,acc@5,rank_mean,align,uniform,align_pen,uniform_pen`` to ``contrast_<eval_seed>.csv``
+    (evaluate/gan.py's ``WeightsMonitor``).  The views are drawn from host generators seeded with the evaluation seed.
+    ``aug`` / ``temp`` default to the run's (``P.augment_fn``, ``P.temp``); ``batch`` is the run's training batch."""
 
     def __init__(self, logdir, architecture, image_size, device, seed, data_path, n=2000, t=2.0, P=None, aug=None, batch=None,
                  temp=None, fwd_batch=500):
@@ -223,60 +221,38 @@ class ContrastMonitor(object):
         self.temp = float(P.temp if temp is None else temp)
         if batch is None:
             raise ValueError('contrast: the monitor needs the block size (the training batch)')
-        x = features.load_images(data_path, 'x_train')
-        if tuple(x.shape[1:]) != tuple(image_size):
-            raise ValueError('%s: x_train holds %s images, the discriminator takes %s' % (data_path, tuple(x.shape[1:]), tuple(image_size)))
+        x = load_x_train(data_path, image_size, 'discriminator takes')
         self.n, self.t, self.fwd_batch = min(int(n), len(x)), float(t), fwd_batch
         self.batch = check_sizes(self.n, batch, self.temp, self.t)
         self.x = torch.from_numpy(x[:self.n]).to(device)                   # the uint8 set goes to the device once
-        self.device, self.eval_seed = device, eval_seed_of(seed)
-        self.path = os.path.join(logdir, 'contrast_%d.csv' % self.eval_seed)
-        self.D = own_network('D', architecture, image_size, device, P)
-        if not os.path.exists(self.path):                                  # (a resumed run appends to its file)
-            with open(self.path, 'w') as f:
-                f.write(CSV_HEADER + '\n')
+        super().__init__(logdir, device, seed, own_network('D', architecture, image_size, device, P),
+                         [('contrast_%d.csv', CSV_HEADER, csv_row)], which='D')
 
-    def update(self, step, discriminator):
-        with torch.no_grad(), preserved_rng(self.device):
-            self.D.load_state_dict(discriminator.state_dict())
-            self.D.eval()
-            out = contrast_of(self.D, self.x, self.aug, self.n, self.batch, self.temp, self.t, self.eval_seed, self.fwd_batch)
-        with open(self.path, 'a') as f:
-            f.write(csv_row(step, out) + '\n')
-        return out
+    def evaluate(self):
+        return contrast_of(self.D, self.x, self.aug, self.n, self.batch, self.temp, self.t, self.eval_seed, self.fwd_batch)
 
 
-HOOK_DEFAULTS = {'contrast_data': None, 'contrast_n': 2000, 'contrast_t': 2.0}
-
-
-def add_hook_arguments(parser):
-    """The three flags of the training scripts.  A flag that is not given leaves no attribute on the parsed namespace (its
-    default lives in ``HOOK_DEFAULTS``; read the flags through ``check_hook_arguments``): a run without the hook parses to
-    what it parsed to before the hook existed."""
-    off = dict(default=SUPPRESS)
-    parser.add_argument('--contrast_data', type=str, **off,
-                        help='npz with x_train uint8 [n, H, W, 3] (no labels needed): rank 0 appends the NT-Xent value, the rank '
-                             'of the positive (Acc@1, Acc@5, mean rank), alignment and uniformity of D on two held-out views '
-                             'under the run\'s --aug and --temp to contrast_<seed>.csv at every evaluate_every; the training '
-                             'trajectory is unchanged')
-    parser.add_argument('--contrast_n', type=int, **off,
-                        help='with --contrast_data: the first N images of x_train (default: 2000)')
-    parser.add_argument('--contrast_t', type=float, **off,
-                        help='with --contrast_data: t of the uniformity potential exp(-t |a - b|^2) (default: 2)')
-
-
-def check_hook_arguments(P):
-    """Refusals that need no device (called before the first CUDA call) -> the hook's flags, defaults filled in."""
-    H = SimpleNamespace(**{name: getattr(P, name, default) for name, default in HOOK_DEFAULTS.items()})
-    given = [name for name in HOOK_DEFAULTS if name != 'contrast_data' and hasattr(P, name)]
-    if not H.contrast_data and given:
-        raise ValueError('%s do%s nothing without --contrast_data FILE.npz' % (', '.join('--' + g for g in given), 'es' if len(given) == 1 else ''))
+# ---- the training scripts' hook ----
+def _refusals(H, P):
     if H.contrast_data:
         if H.contrast_n < 2:
             raise ValueError('--contrast_n must be at least 2, got %r' % (H.contrast_n,))
         if not (math.isfinite(H.contrast_t) and H.contrast_t >= 0):
             raise ValueError('--contrast_t must be finite and not negative, got %r' % (H.contrast_t,))
-    return H
+
+
+HOOK = Hook(
+    flags=(('contrast_data', None, dict(type=str, help='npz with x_train uint8 [n, H, W, 3] (no labels needed): rank 0 appends the NT-Xent value, the rank '
+                                                       'of the positive (Acc@1, Acc@5, mean rank), alignment and uniformity of D on two held-out views '
+                                                       'under the run\'s --aug and --temp to contrast_<seed>.csv at every evaluate_every; the training '
+                                                       'trajectory is unchanged')),
+           ('contrast_n', 2000, dict(type=int, help='with --contrast_data: the first N images of x_train (default: 2000)')),
+           ('contrast_t', 2.0, dict(type=float, help='with --contrast_data: t of the uniformity potential exp(-t |a - b|^2) (default: 2)'))),
+    switch='contrast_data', shown='D', refusals=_refusals,
+    # blocks of the training batch (all ranks' images)
+    build=lambda H, run: ContrastMonitor(*run.head, H.contrast_data, n=H.contrast_n, t=H.contrast_t, P=run.P, batch=run.batch),
+    log_lines=lambda monitor, step, out: [log_line(step, out)])
+add_hook_arguments, check_hook_arguments = HOOK.add_arguments, HOOK.check
 
 
 # ---- the command line ----

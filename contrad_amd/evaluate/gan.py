@@ -156,14 +156,79 @@ def own_network(which, architecture, image_size, device, P=None):
     return freeze(net.to(device))
 
 
-class Monitor(object):
-    """``--monitor`` on rank 0.  ``architecture`` / ``image_size`` / ``P``: what ``get_architecture`` built the training
-    generator from; ``device``: where it lives."""
+def load_x_train(path, image_size, who):
+    """``x_train`` of the npz at ``path`` (``features.load_images``), refused unless its images have the run's
+    ``image_size``.  ``who``: 'generator makes' or 'discriminator takes'."""
+    from .. import features
+    x = features.load_images(path, 'x_train')
+    if tuple(x.shape[1:]) != tuple(image_size):
+        raise ValueError('%s: x_train holds %s images, the %s %s' % (path, tuple(x.shape[1:]), who, tuple(image_size)))
+    return x
 
-    def __init__(self, logdir, architecture, image_size, device, seed, no_gif=False, P=None, delay_ms=500):
-        self.logdir, self.device, self.no_gif, self.delay_ms = logdir, device, bool(no_gif), delay_ms
-        self.eval_seed = eval_seed_of(seed)
-        self.G = own_network('G', architecture, image_size, device, P)
+
+def frozen_encoder(architecture, image_size, path, device):
+    """A monitor's yardstick: the discriminator of ``architecture`` (built inside ``preserved_rng``: the constructors draw
+    the initial weights) with the checkpoint at ``path``, loaded once and frozen."""
+    from .. import features
+    from ..models.gan import get_architecture
+    with preserved_rng(device):
+        E = get_architecture(architecture, image_size)[1]
+    return features.load_frozen(E, path, device)
+
+
+class WeightsMonitor(object):
+    """"Evaluate these weights, append a row": what every monitor of the training scripts is.  It owns the eval seed, a
+    frozen ``network`` of its own (``own_network``; also reachable as ``.G`` / ``.D`` when ``which`` says so) and its csv
+    ``files``: ``(name with %d for the eval seed, header, line_of(step, out))`` each, kept as ``(path, header, line_of)``;
+    a header is written only where the file does not exist yet, so a resumed run appends.  A subclass checks its arguments
+    and computes its fixed state BEFORE it calls this constructor (a refusal leaves no file behind) and gives ``evaluate()``.
+
+    ``update`` is the one place that upholds "monitoring never moves the training trajectory" (module docstring): the shown
+    module is only read (its mode, packed-weight caches and captured graphs are not touched) and the global random streams
+    come back as they were, whatever ``evaluate()`` draws or raises."""
+
+    def __init__(self, logdir, device, seed, network, files=(), which=None):
+        self.logdir, self.device, self.eval_seed = logdir, device, eval_seed_of(seed)
+        self.net = freeze(network)
+        if which is not None:
+            setattr(self, which, self.net)
+        self.files = [(os.path.join(logdir, name % self.eval_seed), head, line_of) for name, head, line_of in files]
+        for path, head, _ in self.files:
+            if not os.path.exists(path):
+                with open(path, 'w') as f:
+                    f.write(head + '\n')
+
+    @contextlib.contextmanager
+    def showing(self, shown):
+        """The body sees ``shown``'s weights in the owned network, in eval mode, under ``no_grad`` and ``preserved_rng``."""
+        with torch.no_grad(), preserved_rng(self.device):
+            self.net.load_state_dict(shown.state_dict())
+            self.net.eval()
+            yield
+
+    def evaluate(self):
+        raise NotImplementedError
+
+    def update(self, step, shown):
+        """One evaluation of ``shown``'s weights -> ``evaluate()``'s result, one line appended per file (``self.lines``;
+        none if ``evaluate()`` or a ``line_of`` raises)."""
+        with self.showing(shown):
+            out = self.evaluate()
+        self.lines = [line_of(step, out) for _, _, line_of in self.files]
+        for (path, _, _), line in zip(self.files, self.lines):
+            with open(path, 'a') as f:
+                f.write(line + '\n')
+        return out
+
+
+class Monitor(WeightsMonitor):
+    """``--monitor`` on rank 0: image grids, no csv.  ``architecture`` / ``image_size`` / ``P``: what ``get_architecture``
+    built the training generator from; ``device``: where it lives.  ``last_batch``: () -> the (images, labels) of the step
+    just finished (``LastBatch.last``), for an ``update`` that is not handed one."""
+
+    def __init__(self, logdir, architecture, image_size, device, seed, no_gif=False, P=None, delay_ms=500, last_batch=None):
+        super().__init__(logdir, device, seed, own_network('G', architecture, image_size, device, P), which='G')
+        self.no_gif, self.delay_ms, self.P, self.last_batch = bool(no_gif), delay_ms, P, last_batch
         self.fixed_gen = FixedSampleGeneration(self.G, volatile=self.no_gif, seed=self.eval_seed)
         self.image_grid = ImageGrid(volatile=self.no_gif)
         self._deflated = []                                        # apng_bytes: compressed frames so far
@@ -171,12 +236,13 @@ class Monitor(object):
     def _path(self, name):
         return os.path.join(self.logdir, name)
 
-    def update(self, step, generator, batch, augment_fn):
+    def update(self, step, generator, batch=None, augment_fn=None):
         """One evaluation: ``generator``: the module whose weights are shown (G, or g_ema in the StyleGAN2 loops);
-        ``batch``: the (images, labels) of the step just finished."""
-        with torch.no_grad(), preserved_rng(self.device):
-            self.G.load_state_dict(generator.state_dict())
-            self.G.eval()
+        ``batch``: the (images, labels) of the step just finished (default: ``last_batch()``); ``augment_fn``: the run's
+        (default: ``P.augment_fn``)."""
+        if batch is None and self.last_batch is not None:
+            batch = self.last_batch()
+        with self.showing(generator):
             torch.cuda.manual_seed(self.eval_seed)                 # StyleGAN2's per-layer noise: the same at every evaluation
             grid = self.fixed_gen.update(step)
             if self.no_gif:
@@ -189,5 +255,5 @@ class Monitor(object):
                     f.write(apng_bytes(self.fixed_gen.summary(), self.delay_ms, deflated=self._deflated))
             if batch is not None:
                 images = batch[0].clone()
-                aug_grid = self.image_grid.update(step, augment_fn(images))
+                aug_grid = self.image_grid.update(step, (augment_fn or self.P.augment_fn)(images))
                 write_png(self._path('real_augment_%d.png' % self.eval_seed), aug_grid)

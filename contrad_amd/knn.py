@@ -14,8 +14,8 @@ eval-mode trunk forward per image, one similarity GEMM, one select-and-vote laun
     query's own column out of its own bank by index (``self0``), so a set without a test split has
     a kNN accuracy too.
 
-``--knn_data`` of the training scripts runs ``knn_accuracy`` at every ``--evaluate_every`` through ``KNNMonitor``, which
-follows evaluate/gan.py's ``Monitor``: a discriminator of its own, so that the training trajectory does not move by a bit.
+``--knn_data`` of the training scripts runs ``knn_accuracy`` at every ``--evaluate_every`` through ``KNNMonitor``
+(evaluate/gan.py's ``WeightsMonitor``: a discriminator of its own, so that the training trajectory does not move by a bit).
 """
 import json
 import os
@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from . import features, ops
-from .evaluate.gan import eval_seed_of, own_network, preserved_rng
+from .evaluate.gan import WeightsMonitor, own_network
+from .hooks import Hook
 from .lineval import load_npz, synthetic_set
 from .models.gan import get_architecture
 
@@ -163,11 +164,10 @@ def loo_accuracy(D, x_u8, y, n_classes, k=200, temp=0.1, batch=500):
     return {'acc@1': 100.0 * int(hits.item()) / n, 'n': n, 'k': min(clf.k, n - 1)}      # the one device-to-host read
 
 
-class KNNMonitor(object):
+class KNNMonitor(WeightsMonitor):
     """``--knn_data`` on rank 0: the kNN accuracy of the training discriminator's weights at every evaluation, appended
-    as ``step,acc@1`` to ``knn_<eval_seed>.csv``.  Like evaluate/gan.py's ``Monitor`` it owns its module (built inside
-    ``preserved_rng``, always in eval mode, never requiring grad) and loads the training D's state dict at each
-    evaluation: D's mode, u / v, packed-weight caches and captured graphs are not touched, the random streams not read."""
+    as ``step,acc@1`` to ``knn_<eval_seed>.csv`` (evaluate/gan.py's ``WeightsMonitor``).  The uint8 sets go to the device
+    once, here."""
 
     def __init__(self, logdir, architecture, image_size, device, seed, data_path, n_classes=None, k=200, temp=0.1, batch=500,
                  P=None):
@@ -179,31 +179,24 @@ class KNNMonitor(object):
         if n_classes is None:
             n_classes = int(max(data['y_train'].max(), data['y_test'].max())) + 1
         self.n_classes, self.k, self.temp, self.batch = n_classes, k, temp, batch
-        self.data = to_device(data, n_classes, device)                     # the uint8 sets go to the device once
-        self.device = device
-        self.path = os.path.join(logdir, 'knn_%d.csv' % eval_seed_of(seed))
-        self.D = own_network('D', architecture, image_size, device, P)
-        if not os.path.exists(self.path):                                  # (a resumed run appends to its file)
-            with open(self.path, 'w') as f:
-                f.write('step,acc@1\n')
+        self.data = to_device(data, n_classes, device)
+        super().__init__(logdir, device, seed, own_network('D', architecture, image_size, device, P),
+                         [('knn_%d.csv', 'step,acc@1', lambda step, out: '%d,%.4f' % (step, out['acc@1']))], which='D')
 
-    def update(self, step, discriminator):
-        with torch.no_grad(), preserved_rng(self.device):
-            self.D.load_state_dict(discriminator.state_dict())
-            self.D.eval()
-            out = knn_accuracy(self.D, self.data, self.n_classes, self.k, self.temp, self.batch)
-        with open(self.path, 'a') as f:
-            f.write('%d,%.4f\n' % (step, out['acc@1']))
-        return out
+    def evaluate(self):
+        return knn_accuracy(self.D, self.data, self.n_classes, self.k, self.temp, self.batch)
 
 
-def add_hook_arguments(parser):
-    """The three flags of the training scripts."""
-    parser.add_argument('--knn_data', default=None, type=str,
-                        help='npz with x_train, y_train, x_test, y_test: rank 0 appends the weighted-kNN accuracy of D\'s '
-                             'penultimate features to knn_<seed>.csv at every evaluate_every; the training trajectory is unchanged')
-    parser.add_argument('--knn_k', default=200, type=int, help='with --knn_data: neighbours (default: 200)')
-    parser.add_argument('--knn_temp', default=0.1, type=float, help='with --knn_data: vote temperature (default: 0.1)')
+# ---- the training scripts' hook: ordinary defaults (the attributes are on every parsed namespace), --knn_k alone passes ----
+HOOK = Hook(
+    flags=(('knn_data', None, dict(type=str, help='npz with x_train, y_train, x_test, y_test: rank 0 appends the weighted-kNN accuracy of D\'s '
+                                                  'penultimate features to knn_<seed>.csv at every evaluate_every; the training trajectory is unchanged')),
+           ('knn_k', 200, dict(type=int, help='with --knn_data: neighbours (default: 200)')),
+           ('knn_temp', 0.1, dict(type=float, help='with --knn_data: vote temperature (default: 0.1)'))),
+    switch='knn_data', shown='D', suppressed=False,
+    build=lambda H, run: KNNMonitor(*run.head, H.knn_data, k=H.knn_k, temp=H.knn_temp, P=run.P),
+    log_lines=lambda monitor, step, out: ['[Steps %7d] [kNN Acc@1 %.3f]' % (step, out['acc@1'])])
+add_hook_arguments = HOOK.add_arguments
 
 
 def parse_args(argv=None):

@@ -32,7 +32,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .evaluate.gan import eval_seed_of, fixed_latent, own_network, preserved_rng
+from .evaluate.gan import WeightsMonitor, fixed_latent, frozen_encoder, own_network, preserved_rng
+from .hooks import Hook
 from .hostio import upload
 
 DEFAULT_EPS = 1e-4
@@ -239,73 +240,45 @@ def log_line(step, out):
                                                                            out['kept'], out['n'], out['eps'])
 
 
-class PPLMonitor(object):
+class PPLMonitor(WeightsMonitor):
     """``--ppl_encoder`` on rank 0: the path length of the training generator's weights at every evaluation, appended as
-    ``step,ppl,ppl_raw,kept`` to ``ppl_<eval_seed>.csv``.  Like ``SpectrumMonitor`` it owns a generator (built inside
-    ``preserved_rng``, always in eval mode) that loads the shown generator's state dict at each evaluation, and its encoder
-    (loaded once and frozen); latents, t and noise come from the eval seed, so two evaluations differ by the weights alone
-    and nothing is drawn from the global streams.  It needs no real data and none of the other hooks' flags.  It records
-    only: a non-finite distance is recorded as a row of nan (``summarise``), not raised into the training loop."""
+    ``step,ppl,ppl_raw,kept`` to ``ppl_<eval_seed>.csv`` (evaluate/gan.py's ``WeightsMonitor``).  Its encoder is loaded once
+    and frozen; latents, t and noise come from the eval seed, so two evaluations differ by the weights alone.  It needs no
+    real data and none of the other hooks' flags.  It records only: a non-finite distance is recorded as a row of nan
+    (``summarise``), not raised into the training loop."""
 
     def __init__(self, logdir, architecture, image_size, device, seed, encoder_path, encoder_arch=None, n=2000, space='z',
                  eps=DEFAULT_EPS, batch=64, P=None):
-        from . import features
-        from .models.gan import get_architecture
         check_space(architecture, space)
         check_ppl_arguments(n, float(eps), 'full', batch)
         self.n, self.space, self.eps, self.batch = int(n), space, float(eps), int(batch)
-        self.device, self.eval_seed = device, eval_seed_of(seed)
-        self.path = os.path.join(logdir, 'ppl_%d.csv' % self.eval_seed)
-        with preserved_rng(device):
-            E = get_architecture(encoder_arch or architecture, image_size)[1]
-        self.E = features.load_frozen(E, encoder_path, device)
-        self.G = own_network('G', architecture, image_size, device, P)
-        if not os.path.exists(self.path):                                      # (a resumed run appends to its file)
-            with open(self.path, 'w') as f:
-                f.write(CSV_HEAD + '\n')
+        self.E = frozen_encoder(encoder_arch or architecture, image_size, encoder_path, device)
+        super().__init__(logdir, device, seed, own_network('G', architecture, image_size, device, P),
+                         [('ppl_%d.csv', CSV_HEAD, csv_line)], which='G')
 
-    def update(self, step, generator):
-        with torch.no_grad(), preserved_rng(self.device):
-            self.G.load_state_dict(generator.state_dict())
-            self.G.eval()
-            out = ppl_of(self.G, self.E, self.n, self.eval_seed, self.space, 'full', self.eps, self.batch)
-        with open(self.path, 'a') as f:
-            f.write(csv_line(step, out) + '\n')
-        return out
+    def evaluate(self):
+        return ppl_of(self.G, self.E, self.n, self.eval_seed, self.space, 'full', self.eps, self.batch)
 
 
 # ---- the training scripts' hook ----
-HOOK_DEFAULTS = {'ppl_encoder': None, 'ppl_encoder_arch': None, 'ppl_n': 2000, 'ppl_space': 'z'}
+def _refusals(H, P):
+    if H.ppl_encoder:
+        if H.ppl_n < MIN_N:
+            raise ValueError('--ppl_n must be at least %d (the 1 %% rule), got %r' % (MIN_N, H.ppl_n))
+        check_space(P.architecture, H.ppl_space)
 
 
-def add_hook_arguments(parser):
-    """The four flags of the training scripts.  A flag that is not given leaves no attribute on the parsed namespace (its
-    default lives in ``HOOK_DEFAULTS``; read the flags through ``check_hook_arguments``)."""
-    from argparse import SUPPRESS
-    parser.add_argument('--ppl_encoder', type=str, default=SUPPRESS,
-                        help='discriminator checkpoint used as the frozen feature encoder: rank 0 appends the perceptual path length of '
-                             'the generator in its penultimate features (no real data) to ppl_<seed>.csv at every evaluate_every; '
-                             'comparable only under one encoder file, never with LPIPS-based PPL; the training trajectory is unchanged')
-    parser.add_argument('--ppl_encoder_arch', type=str, default=SUPPRESS,
-                        help="with --ppl_encoder: the encoder's architecture (default: the run's)")
-    parser.add_argument('--ppl_n', type=int, default=SUPPRESS, help='with --ppl_encoder: the number of pairs (default: 2000)')
-    parser.add_argument('--ppl_space', type=str, default=SUPPRESS,
-                        help="with --ppl_encoder: 'z' (default) or 'w' (StyleGAN2 only)")
-
-
-def check_hook_arguments(P):
-    """Refusals that need no device (called before the first CUDA call) -> the hook's flags, defaults filled in."""
-    from types import SimpleNamespace
-    H = SimpleNamespace(**{name: getattr(P, name, default) for name, default in HOOK_DEFAULTS.items()})
-    if not H.ppl_encoder:
-        for name in ('ppl_encoder_arch', 'ppl_n', 'ppl_space'):
-            if hasattr(P, name):
-                raise ValueError('--%s does nothing without --ppl_encoder FILE.pt' % name)
-        return H
-    if H.ppl_n < MIN_N:
-        raise ValueError('--ppl_n must be at least %d (the 1 %% rule), got %r' % (MIN_N, H.ppl_n))
-    check_space(P.architecture, H.ppl_space)
-    return H
+HOOK = Hook(
+    flags=(('ppl_encoder', None, dict(type=str, help='discriminator checkpoint used as the frozen feature encoder: rank 0 appends the perceptual path length of '
+                                                     'the generator in its penultimate features (no real data) to ppl_<seed>.csv at every evaluate_every; '
+                                                     'comparable only under one encoder file, never with LPIPS-based PPL; the training trajectory is unchanged')),
+           ('ppl_encoder_arch', None, dict(type=str, help="with --ppl_encoder: the encoder's architecture (default: the run's)")),
+           ('ppl_n', 2000, dict(type=int, help='with --ppl_encoder: the number of pairs (default: 2000)')),
+           ('ppl_space', 'z', dict(type=str, help="with --ppl_encoder: 'z' (default) or 'w' (StyleGAN2 only)"))),
+    switch='ppl_encoder', needs='FILE.pt', refusals=_refusals,
+    build=lambda H, run: PPLMonitor(*run.head, H.ppl_encoder, encoder_arch=H.ppl_encoder_arch, n=H.ppl_n, space=H.ppl_space, P=run.P),
+    log_lines=lambda monitor, step, out: [log_line(step, out)])
+add_hook_arguments, check_hook_arguments = HOOK.add_arguments, HOOK.check
 
 
 # ---- figures ----

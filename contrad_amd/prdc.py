@@ -22,26 +22,22 @@ fake rows, S_XY = X Y^T:
   * csrc/prdc.hip: ``prdc_kth`` per chunk of S_RR and S_FF (``self0`` = the chunk's first row), ``prdc_count`` per chunk of S_FR;
   * the four metrics are ratios of integers counted on the device; the host reads them once and divides in float64.
 
-``--prdc_data`` / ``--prdc_encoder`` of the training scripts run this at every ``--evaluate_every`` through ``PRDCMonitor``,
-which follows ``KNNMonitor``: modules of its own, so that the training trajectory does not move by a bit.  ``--prdc_best
+``--prdc_data`` / ``--prdc_encoder`` of the training scripts run this at every ``--evaluate_every`` through ``PRDCMonitor``
+(evaluate/gan.py's ``WeightsMonitor``: modules of its own, so that the training trajectory does not move by a bit).  ``--prdc_best
 METRIC`` keeps ``gen_best.pt`` / ``dis_best.pt`` (/ ``gen_ema_best.pt``), the names the reference gives its best-FID
 checkpoints, for the best value of that metric.  ``--prdc_kid`` adds the kernel distance of contrad_amd/kid.py to every
 evaluation (``kid_<seed>.csv``; ``--prdc_best kid`` selects its minimum); ``--prdc_kid_kernel rq`` makes that the
 rational-quadratic distance, in ``kid_rq_<seed>.csv``.  ``--prdc_fd`` adds the Frechet distance of contrad_amd/fd.py
 (``fd_<seed>.csv``; it records only).
 """
-import os
-from argparse import SUPPRESS
-from types import SimpleNamespace
-
 import torch
 
 from . import fd as fd_mod
 from . import features, ops
 from . import kid as kid_mod
 from . import nearest
-from .evaluate.gan import eval_seed_of, own_network, preserved_rng
-from .models.gan import get_architecture
+from .evaluate.gan import WeightsMonitor, frozen_encoder, load_x_train, own_network, preserved_rng
+from .hooks import Hook
 
 METRICS = ('precision', 'recall', 'density', 'coverage')
 CSV_HEAD = 'step,' + ','.join(METRICS)
@@ -145,16 +141,15 @@ def csv_line(step, out):
     return '%d,%s' % (step, ','.join('%.6f' % out[m] for m in METRICS))
 
 
-class PRDCMonitor(object):
+class PRDCMonitor(WeightsMonitor):
     """``--prdc_data`` on rank 0: precision / recall / density / coverage of the training generator's weights at every
-    evaluation, appended as ``step,precision,recall,density,coverage`` to ``prdc_<eval_seed>.csv``.  It owns its encoder
-    (``encoder_path``, loaded once and frozen: the yardstick must not move with the run) and, like evaluate/gan.py's
-    ``Monitor``, a generator of its own (built inside ``preserved_rng``, always in eval mode) that loads the shown
-    generator's state dict at each evaluation; the fakes come from fixed latents of the eval seed.  The real features and
-    t_R are computed once, here.  ``best``: one of METRICS; ``update`` then says whether the evaluation improved it (the
-    caller writes the ``*_best.pt`` files); a run resumed from the checkpoint of step ``resumed_step`` reads the best value
-    up to that step back from its csv (``best_in_csv``).  ``kid`` (``--prdc_kid``): each evaluation also appends
-    ``step,kid,kid_std`` to ``kid_<eval_seed>.csv`` (contrad_amd/kid.py); ``best`` may then be ``'kid'``, which is minimised.  ``kid_kernel``
+    evaluation, appended as ``step,precision,recall,density,coverage`` to ``prdc_<eval_seed>.csv`` (evaluate/gan.py's
+    ``WeightsMonitor``).  It owns its encoder (``encoder_path``, loaded once and frozen: the yardstick must not move with the
+    run); the fakes come from fixed latents of the eval seed.  The real features and t_R are computed once, here.
+    ``best``: one of BEST_CHOICES; ``update`` then says whether the evaluation improved it (the caller writes the
+    ``*_best.pt`` files); a run resumed from the checkpoint of step ``resumed_step`` reads the best value up to that step
+    back from its csv (``features.best_in_csv``).  ``kid`` (``--prdc_kid``): each evaluation also appends ``step,kid,kid_std``
+    to ``kid_<eval_seed>.csv`` (contrad_amd/kid.py); ``best`` may then be ``'kid'``, which is minimised.  ``kid_kernel``
     (``--prdc_kid_kernel``): 'rq' computes the rational-quadratic distance instead, into ``kid_rq_<eval_seed>.csv`` (never into
     ``kid_<eval_seed>.csv``: the two are different numbers), which ``best='kid'`` then tracks and reads back.  ``auth``
     (``--prdc_auth``): the real features are extracted once for both states -- ``real_state_of`` and ``nearest.real_state_of``
@@ -167,9 +162,7 @@ class PRDCMonitor(object):
     def __init__(self, logdir, architecture, image_size, device, seed, data_path, encoder_path, encoder_arch=None, k=5,
                  n_fake=10000, batch=500, best=None, resumed_step=0, P=None, kid=False, kid_kernel='poly3', auth=False, fd=False,
                  fd_iter=fd_mod.N_ITER):
-        real = features.load_images(data_path, 'x_train')
-        if tuple(real.shape[1:]) != tuple(image_size):
-            raise ValueError('%s: x_train holds %s images, the generator makes %s' % (data_path, tuple(real.shape[1:]), tuple(image_size)))
+        real = load_x_train(data_path, image_size, 'generator makes')
         check_k(k, len(real), n_fake)
         if best is not None and best not in BEST_CHOICES:
             raise ValueError('--prdc_best %r (one of %s)' % (best, ', '.join(BEST_CHOICES)))
@@ -184,20 +177,12 @@ class PRDCMonitor(object):
             raise ValueError('--prdc_auth needs at least 2 real images (%d)' % len(real))
         if fd:
             fd_mod.check_sizes(len(real), n_fake, fd_iter)
-        self.k, self.n_fake, self.batch, self.device, self.metric = int(k), int(n_fake), int(batch), device, best
-        self.eval_seed = eval_seed_of(seed)
-        self.path = os.path.join(logdir, 'prdc_%d.csv' % self.eval_seed)
-        self.kid_kernel = kid_kernel
-        self.kid_path = os.path.join(logdir, kid_csv_name(kid_kernel) % self.eval_seed) if kid else None
-        self.auth_path = os.path.join(logdir, 'auth_%d.csv' % self.eval_seed) if auth else None
-        self.auth_state = None
-        self.fd_path = os.path.join(logdir, 'fd_%d.csv' % self.eval_seed) if fd else None
-        self.fd_state, self.fd_iter = None, int(fd_iter)
-        self.n_real = len(real)
-        self.G = own_network('G', architecture, image_size, device, P)
-        with preserved_rng(device):                                        # the constructors draw the initial weights
-            E = get_architecture(encoder_arch or architecture, image_size)[1]
-        self.E = features.load_frozen(E, encoder_path, device)
+        self.k, self.n_fake, self.batch, self.metric = int(k), int(n_fake), int(batch), best
+        self.kid_kernel = kid_kernel if kid else None
+        self.auth_state = self.fd_state = None
+        self.fd_iter, self.n_real = int(fd_iter), len(real)
+        G = own_network('G', architecture, image_size, device, P)
+        self.E = frozen_encoder(encoder_arch or architecture, image_size, encoder_path, device)
         with torch.no_grad(), preserved_rng(device):
             if not auth:
                 self.real_state = real_state_of_images(self.E, torch.from_numpy(real).to(device), self.k, self.batch)
@@ -209,51 +194,45 @@ class PRDCMonitor(object):
                 self.auth_state = nearest.real_state_of(feats, normalize=False, bankT=self.real_state[0])
             if fd:                                                         # the same bank: centred once, here
                 self.fd_state = fd_mod.real_state_of(self.real_state[0], self.n_real)
-        self.files = [(self.path, CSV_HEAD, csv_line)] + ([(self.kid_path, kid_mod.CSV_HEAD, kid_mod.csv_line)] if kid else []) + \
-            ([(self.auth_path, nearest.CSV_HEAD, nearest.csv_line)] if auth else []) + \
-            ([(self.fd_path, fd_mod.CSV_HEAD, fd_mod.csv_line)] if fd else [])             # (after the files --prdc_best tracks)
+        super().__init__(logdir, device, seed, G,
+                         [('prdc_%d.csv', CSV_HEAD, csv_line)] + ([(kid_csv_name(kid_kernel), kid_mod.CSV_HEAD, kid_mod.csv_line)] if kid else []) +
+                         ([('auth_%d.csv', nearest.CSV_HEAD, nearest.csv_line)] if auth else []) +
+                         ([('fd_%d.csv', fd_mod.CSV_HEAD, fd_mod.csv_line)] if fd else []),     # (after the files --prdc_best tracks)
+                         which='G')
         self.best = None
-        for j, (path, head, _) in enumerate(self.files):
-            if not os.path.exists(path):                                   # (a resumed run appends to its file)
-                with open(path, 'w') as f:
-                    f.write(head + '\n')
-            elif best is not None and j == _tracked(best)[0]:
-                _, column, sign = _tracked(best)
-                self.best = features.best_in_csv(path, column, resumed_step, min if sign < 0 else max)
+        if best is not None:                                               # (a file made just now holds no row: None)
+            j, column, sign = _tracked(best)
+            self.best = features.best_in_csv(self.files[j][0], column, resumed_step, min if sign < 0 else max)
+
+    def evaluate(self):
+        fake = features.sample_u8(self.G, self.n_fake, self.batch, self.eval_seed)
+        features.check_u8(fake, 'fake', 'prdc')
+        feats = features.extract_features(self.E, fake, self.batch)
+        out = prdc(None, feats, self.k, real_state=self.real_state, normalize=False)
+        if self.kid_kernel is not None:                                    # the same fake features, the same real rows (bankT)
+            d = kid_mod.kid(None, feats, seed=self.eval_seed, normalize=False, real_bank=(self.real_state[0], self.n_real),
+                            kernel=self.kid_kernel)
+            out['kid'], out['kid_std'] = d['kid'], d['kid_std']
+        if self.auth_state is not None:                                    # the same fake features, the same real bank
+            a = nearest.authenticity(None, feats, real_state=self.auth_state, normalize=False)
+            out['authenticity'], out['nearest_mean'], out['real_nearest_mean'] = a['authenticity'], a['nearest_mean'], a['real_nearest_mean']
+        if self.fd_state is not None:                                      # the same fake features, the real state made once
+            f = fd_mod.fd(None, feats, self.fd_iter, normalize=False, real_state=self.fd_state)
+            out['fd'] = f['fd']
+            for name in ('mean_term', 'trace_fake', 'cross_term', 'tail'):
+                out['fd_' + name] = f[name]
+        return out
 
     def update(self, step, generator):
         """One evaluation of ``generator``'s weights (G, or g_ema in the StyleGAN2 loops) -> the metrics, with
         ``improved``: the tracked metric rose above (kid: fell below) the best so far (False without ``best``; a tie keeps
         the earlier).  With ``kid`` the kernel distance of the same fake features (contrad_amd/kid.py: the subsets of the
         eval seed, the same at every evaluation) comes as ``kid`` / ``kid_std`` and goes to ``kid_<eval_seed>.csv``."""
-        with torch.no_grad(), preserved_rng(self.device):
-            self.G.load_state_dict(generator.state_dict())
-            self.G.eval()
-            fake = features.sample_u8(self.G, self.n_fake, self.batch, self.eval_seed)
-            features.check_u8(fake, 'fake', 'prdc')
-            feats = features.extract_features(self.E, fake, self.batch)
-            out = prdc(None, feats, self.k, real_state=self.real_state, normalize=False)
-            if self.kid_path is not None:                                  # the same fake features, the same real rows (bankT)
-                d = kid_mod.kid(None, feats, seed=self.eval_seed, normalize=False, real_bank=(self.real_state[0], self.n_real),
-                                kernel=self.kid_kernel)
-                out['kid'], out['kid_std'] = d['kid'], d['kid_std']
-            if self.auth_path is not None:                                 # the same fake features, the same real bank
-                a = nearest.authenticity(None, feats, real_state=self.auth_state, normalize=False)
-                out['authenticity'], out['nearest_mean'], out['real_nearest_mean'] = a['authenticity'], a['nearest_mean'], a['real_nearest_mean']
-            if self.fd_path is not None:                                   # the same fake features, the real state made once
-                f = fd_mod.fd(None, feats, self.fd_iter, normalize=False, real_state=self.fd_state)
-                out['fd'] = f['fd']
-                for name in ('mean_term', 'trace_fake', 'cross_term', 'tail'):
-                    out['fd_' + name] = f[name]
-        lines = []
-        for path, _, line_of in self.files:
-            lines.append(line_of(step, out))
-            with open(path, 'a') as f:
-                f.write(lines[-1] + '\n')
+        out = super().update(step, generator)
         out['improved'] = False
         if self.metric is not None:
             j, column, sign = _tracked(self.metric)
-            value = float(lines[j].split(',')[column])                     # as the csv keeps it: a resumed run compares alike
+            value = float(self.lines[j].split(',')[column])                # as the csv keeps it: a resumed run compares alike
             if self.best is None or sign * value > sign * self.best:
                 self.best, out['improved'] = value, True
         return out
@@ -275,72 +254,16 @@ class PRDCMonitor(object):
         return lines
 
 
-HOOK_DEFAULTS = {'prdc_data': None, 'prdc_encoder': None, 'prdc_encoder_arch': None, 'prdc_k': 5, 'prdc_n': 10000, 'prdc_best': None,
-                 'prdc_kid': False, 'prdc_kid_kernel': 'poly3', 'prdc_auth': False, 'prdc_fd': False, 'prdc_fd_iter': fd_mod.N_ITER}
-
-
 def kid_csv_name(kid_kernel):
     """``kid_%d.csv`` for the cubic kernel, ``kid_rq_%d.csv`` for the rational-quadratic one."""
     return 'kid_%d.csv' if kid_kernel == 'poly3' else 'kid_' + kid_kernel + '_%d.csv'
 
 
-def add_hook_arguments(parser):
-    """The flags of the training scripts.  A flag that is not given leaves no attribute on the parsed namespace (its
-    default lives in ``HOOK_DEFAULTS``; read the flags through ``hook_options``): a run without the hook parses to what it
-    parsed to before the hook existed."""
-    off = dict(default=SUPPRESS)
-    parser.add_argument('--prdc_data', type=str, **off,
-                        help='npz with x_train uint8 [n, H, W, 3]: rank 0 appends precision / recall / density / coverage of the '
-                             'generator (g_ema where there is one) against it to prdc_<seed>.csv at every evaluate_every, in '
-                             'the features of --prdc_encoder; the training trajectory is unchanged')
-    parser.add_argument('--prdc_encoder', type=str, **off,
-                        help='with --prdc_data (required): discriminator checkpoint used as the frozen feature encoder')
-    parser.add_argument('--prdc_encoder_arch', type=str, **off,
-                        help="with --prdc_data: the encoder's architecture (default: the run's)")
-    parser.add_argument('--prdc_k', type=int, **off, help='with --prdc_data: neighbours (default: 5)')
-    parser.add_argument('--prdc_n', type=int, **off,
-                        help='with --prdc_data: generated images per evaluation (default: 10000; x_train is used whole)')
-    parser.add_argument('--prdc_best', type=str, choices=BEST_CHOICES, **off,
-                        help='with --prdc_data: keep gen_best.pt / dis_best.pt (and gen_ema_best.pt) of the evaluation with the '
-                             'best value of this metric (the reference keeps these names for its best FID); kid (needs '
-                             '--prdc_kid) is minimised')
-    parser.add_argument('--prdc_kid', action='store_true', **off,
-                        help='with --prdc_data: every evaluation also appends step,kid,kid_std to kid_<seed>.csv: the kernel '
-                             'distance (cubic kernel, gamma = coef0 = 1, 100 subsets of up to 1000) of the same fake features '
-                             'from the real set, comparable only under one --prdc_encoder file, never with Inception-based KID')
-    parser.add_argument('--prdc_kid_kernel', type=str, choices=kid_mod.KERNELS, **off,
-                        help='with --prdc_kid: poly3 (default), or rq: the rational-quadratic mixture (alpha = 1/2, 1, 2; a '
-                             'characteristic kernel) is computed instead and appended to kid_rq_<seed>.csv, never into '
-                             'kid_<seed>.csv; --prdc_best kid then tracks that file')
-    parser.add_argument('--prdc_auth', action='store_true', **off,
-                        help='with --prdc_data: every evaluation also appends step,authenticity,nearest_mean to auth_<seed>.csv: '
-                             'the memorisation check (contrad_amd/nearest.py), the share of the same fakes that is NOT closer to '
-                             'its nearest real image than that image is to its own nearest other real image, and the mean '
-                             'similarity of a fake to its nearest real.  It records only (no --prdc_best choice: not a quantity '
-                             'to maximise); read it against test_nearest.py --holdout, not against 1')
-    parser.add_argument('--prdc_fd', action='store_true', **off,
-                        help='with --prdc_data: every evaluation also appends step,fd,mean_term,trace_fake,cross_term,tail to '
-                             'fd_<seed>.csv: the Frechet distance (contrad_amd/fd.py) of the same fake features from the real set, '
-                             'comparable only under one --prdc_encoder file, never with Inception-based FID.  It records only: '
-                             '--prdc_best gains no choice for it')
-    parser.add_argument('--prdc_fd_iter', type=int, **off,
-                        help='with --prdc_fd: Newton-Schulz steps per evaluation, fixed (default: %d)' % fd_mod.N_ITER)
-
-
-def hook_options(P):
-    """The hook flags of a parsed command line, defaults filled in."""
-    return SimpleNamespace(**{name: getattr(P, name, default) for name, default in HOOK_DEFAULTS.items()})
-
-
-def check_hook_arguments(P):
-    """Refusals that need no device (called before the first CUDA call) -> ``hook_options(P)``."""
-    H = hook_options(P)
+# ---- the training scripts' hook ----
+def _refusals(H, P):
     if H.prdc_data and not H.prdc_encoder:
         raise ValueError('--prdc_data needs --prdc_encoder FILE.pt: the metrics are comparable between evaluations only in '
                          'the feature space of ONE frozen encoder, and the discriminator of this run changes at every step')
-    given = [name for name in HOOK_DEFAULTS if name != 'prdc_data' and hasattr(P, name)]
-    if not H.prdc_data and given:
-        raise ValueError('%s do%s nothing without --prdc_data FILE.npz' % (', '.join('--' + g for g in given), 'es' if len(given) == 1 else ''))
     if hasattr(P, 'prdc_kid_kernel') and not H.prdc_kid:
         raise ValueError('--prdc_kid_kernel needs --prdc_kid: without it no kernel distance is computed')
     if H.prdc_best == 'kid' and not H.prdc_kid:
@@ -349,7 +272,47 @@ def check_hook_arguments(P):
         raise ValueError('--prdc_fd_iter needs --prdc_fd: without it no Frechet distance is computed')
     if H.prdc_fd_iter < 1:
         raise ValueError('--prdc_fd_iter must be at least 1, got %r' % (H.prdc_fd_iter,))
-    return H
+
+
+HOOK = Hook(
+    flags=(('prdc_data', None, dict(type=str, help='npz with x_train uint8 [n, H, W, 3]: rank 0 appends precision / recall / density / coverage of the '
+                                                   'generator (g_ema where there is one) against it to prdc_<seed>.csv at every evaluate_every, in '
+                                                   'the features of --prdc_encoder; the training trajectory is unchanged')),
+           ('prdc_encoder', None, dict(type=str, help='with --prdc_data (required): discriminator checkpoint used as the frozen feature encoder')),
+           ('prdc_encoder_arch', None, dict(type=str, help="with --prdc_data: the encoder's architecture (default: the run's)")),
+           ('prdc_k', 5, dict(type=int, help='with --prdc_data: neighbours (default: 5)')),
+           ('prdc_n', 10000, dict(type=int, help='with --prdc_data: generated images per evaluation (default: 10000; x_train is used whole)')),
+           ('prdc_best', None, dict(type=str, choices=BEST_CHOICES,
+                                    help='with --prdc_data: keep gen_best.pt / dis_best.pt (and gen_ema_best.pt) of the evaluation with the '
+                                         'best value of this metric (the reference keeps these names for its best FID); kid (needs '
+                                         '--prdc_kid) is minimised')),
+           ('prdc_kid', False, dict(action='store_true',
+                                    help='with --prdc_data: every evaluation also appends step,kid,kid_std to kid_<seed>.csv: the kernel '
+                                         'distance (cubic kernel, gamma = coef0 = 1, 100 subsets of up to 1000) of the same fake features '
+                                         'from the real set, comparable only under one --prdc_encoder file, never with Inception-based KID')),
+           ('prdc_kid_kernel', 'poly3', dict(type=str, choices=kid_mod.KERNELS,
+                                             help='with --prdc_kid: poly3 (default), or rq: the rational-quadratic mixture (alpha = 1/2, 1, 2; a '
+                                                  'characteristic kernel) is computed instead and appended to kid_rq_<seed>.csv, never into '
+                                                  'kid_<seed>.csv; --prdc_best kid then tracks that file')),
+           ('prdc_auth', False, dict(action='store_true',
+                                     help='with --prdc_data: every evaluation also appends step,authenticity,nearest_mean to auth_<seed>.csv: '
+                                          'the memorisation check (contrad_amd/nearest.py), the share of the same fakes that is NOT closer to '
+                                          'its nearest real image than that image is to its own nearest other real image, and the mean '
+                                          'similarity of a fake to its nearest real.  It records only (no --prdc_best choice: not a quantity '
+                                          'to maximise); read it against test_nearest.py --holdout, not against 1')),
+           ('prdc_fd', False, dict(action='store_true',
+                                   help='with --prdc_data: every evaluation also appends step,fd,mean_term,trace_fake,cross_term,tail to '
+                                        'fd_<seed>.csv: the Frechet distance (contrad_amd/fd.py) of the same fake features from the real set, '
+                                        'comparable only under one --prdc_encoder file, never with Inception-based FID.  It records only: '
+                                        '--prdc_best gains no choice for it')),
+           ('prdc_fd_iter', fd_mod.N_ITER, dict(type=int, help='with --prdc_fd: Newton-Schulz steps per evaluation, fixed (default: %d)' % fd_mod.N_ITER))),
+    switch='prdc_data', refusals=_refusals,
+    build=lambda H, run: PRDCMonitor(*run.head, H.prdc_data, H.prdc_encoder, encoder_arch=H.prdc_encoder_arch, k=H.prdc_k, n_fake=H.prdc_n,
+                                     best=H.prdc_best, resumed_step=run.resumed_step, P=run.P, kid=H.prdc_kid, kid_kernel=H.prdc_kid_kernel,
+                                     auth=H.prdc_auth, fd=H.prdc_fd, fd_iter=H.prdc_fd_iter),
+    log_lines=lambda monitor, step, out: monitor.log_lines(step, out),
+    improved=lambda out: out['improved'])                              # the reference's best-checkpoint names: this step's networks
+add_hook_arguments, check_hook_arguments, hook_options, HOOK_DEFAULTS = HOOK.add_arguments, HOOK.check, HOOK.options, HOOK.defaults
 
 
 def parse_args(argv=None):

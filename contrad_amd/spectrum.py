@@ -43,7 +43,8 @@ import numpy as np
 import torch
 
 from . import features, ops
-from .evaluate.gan import eval_seed_of, own_network, preserved_rng
+from .evaluate.gan import WeightsMonitor, load_x_train, own_network
+from .hooks import Hook
 
 MIN_SIDE, MAX_SIDE = 16, 512
 MAX_N = 16384                               # the command line's default cap per set
@@ -209,76 +210,54 @@ def log_line(step, out):
         (step, out['lsd_db'], 'n/a' if out['floor_db'] is None else '%.3f' % out['floor_db'], out['hf_db']) + tuple(out['nyquist_db']))
 
 
-class SpectrumMonitor(object):
+class SpectrumMonitor(WeightsMonitor):
     """``--spectrum_data`` on rank 0: the radial power spectrum of the training generator's weights against the first ``n``
-    real images at every evaluation, appended as ``step,lsd_db,hf_db,nyq_h,nyq_v,nyq_d`` to ``spectrum_<eval_seed>.csv``.  No
-    encoder: it needs none of the ``--prdc_*`` flags.  Like ``SWDMonitor`` it owns a generator (built inside
-    ``preserved_rng``, always in eval mode) that loads the shown generator's state dict at each evaluation; the fakes come
-    from fixed latents of the eval seed (``features.sample_u8``), so two evaluations differ by the weights alone.  The real
+    real images at every evaluation, appended as ``step,lsd_db,hf_db,nyq_h,nyq_v,nyq_d`` to ``spectrum_<eval_seed>.csv``
+    (evaluate/gan.py's ``WeightsMonitor``).  No encoder: it needs none of the ``--prdc_*`` flags.  The fakes come from fixed
+    latents of the eval seed (``features.sample_u8``), so two evaluations differ by the weights alone.  The real
     side is one fixed curve: the real set is transformed once, here, and only its mean curve, its mean map and its noise
     floor are kept.  It records only: there is no ``*_best.pt`` choice, and an evaluation at which some bin or Nyquist point of
     the fakes has no power (``compare`` raises ValueError there) is recorded as a row of nan (``compare_or_nan``), not raised into
     the training loop.  A real set without power in some bin is refused here, in ``__init__``."""
 
     def __init__(self, logdir, architecture, image_size, device, seed, data_path, n=8192, batch=500, P=None):
-        real = features.load_images(data_path, 'x_train')
-        if tuple(real.shape[1:]) != tuple(image_size):
-            raise ValueError('%s: x_train holds %s images, the generator makes %s' % (data_path, tuple(real.shape[1:]), tuple(image_size)))
+        real = load_x_train(data_path, image_size, 'generator makes')
         if real.shape[1] != real.shape[2]:
             raise ValueError('spectrum: %s holds %d x %d images, square images expected' % (data_path, real.shape[1], real.shape[2]))
         check_side(real.shape[1])
         if int(n) < 1:
             raise ValueError('spectrum: n must be at least 1, got %r' % (n,))
-        self.n = min(int(n), len(real))
-        self.batch, self.device, self.eval_seed = int(batch), device, eval_seed_of(seed)
-        self.path = os.path.join(logdir, 'spectrum_%d.csv' % self.eval_seed)
+        self.n, self.batch = min(int(n), len(real)), int(batch)
         out = spectrum_of(torch.from_numpy(real[:self.n]).to(device))
         self.real = {'S': out['S'], 'n': out['n'], 'K': out['K'], 'mean': out['mean'], 'map': out['map'],
                      'floor_db': floor_of(out['profiles'])}
         log_ratio_db(self.real['mean'], self.real['mean'], 'a radial bin of the real set')     # (refused once, before the run)
         corners = [self.real['map'][p] for p in nyquist_points(out['S'])]
         log_ratio_db(corners, corners, 'a Nyquist point of the real set')
-        self.G = own_network('G', architecture, image_size, device, P)
-        if not os.path.exists(self.path):                                      # (a resumed run appends to its file)
-            with open(self.path, 'w') as f:
-                f.write(CSV_HEAD + '\n')
+        super().__init__(logdir, device, seed, own_network('G', architecture, image_size, device, P),
+                         [('spectrum_%d.csv', CSV_HEAD, csv_line)], which='G')
 
-    def update(self, step, generator):
-        with torch.no_grad(), preserved_rng(self.device):
-            self.G.load_state_dict(generator.state_dict())
-            self.G.eval()
-            fake = features.sample_u8(self.G, self.n, self.batch, self.eval_seed)
-            out = compare_or_nan(self.real, spectrum_of(fake))
-        with open(self.path, 'a') as f:
-            f.write(csv_line(step, out) + '\n')
-        return out
+    def evaluate(self):
+        fake = features.sample_u8(self.G, self.n, self.batch, self.eval_seed)
+        return compare_or_nan(self.real, spectrum_of(fake))
 
 
 # ---- the training scripts' hook ----
-HOOK_DEFAULTS = {'spectrum_data': None, 'spectrum_n': 8192}
-
-
-def add_hook_arguments(parser):
-    """The two flags of the training scripts.  A flag that is not given leaves no attribute on the parsed namespace (its
-    default lives in ``HOOK_DEFAULTS``; read the flags through ``check_hook_arguments``)."""
-    from argparse import SUPPRESS
-    parser.add_argument('--spectrum_data', type=str, default=SUPPRESS,
-                        help='npz with x_train uint8 [n, S, S, 3]: rank 0 appends the radial power spectrum of the generator against '
-                             'these images (log-spectral distance, high-band level and the three Nyquist points in dB; no encoder) '
-                             'to spectrum_<seed>.csv at every evaluate_every; the training trajectory is unchanged')
-    parser.add_argument('--spectrum_n', type=int, default=SUPPRESS,
-                        help='with --spectrum_data: the first N images of x_train against N samples (default: 8192)')
-
-
-def check_hook_arguments(P):
-    """Refusals that need no device (called before the first CUDA call) -> the hook's flags, defaults filled in."""
-    from types import SimpleNamespace
-    H = SimpleNamespace(**{name: getattr(P, name, default) for name, default in HOOK_DEFAULTS.items()})
-    if not H.spectrum_data and hasattr(P, 'spectrum_n'):
-        raise ValueError('--spectrum_n does nothing without --spectrum_data FILE.npz')
+def _refusals(H, P):
     if H.spectrum_data and H.spectrum_n < 1:
         raise ValueError('--spectrum_n must be at least 1, got %r' % (H.spectrum_n,))
-    return H
+
+
+HOOK = Hook(
+    flags=(('spectrum_data', None, dict(type=str, help='npz with x_train uint8 [n, S, S, 3]: rank 0 appends the radial power spectrum of the generator against '
+                                                       'these images (log-spectral distance, high-band level and the three Nyquist points in dB; no encoder) '
+                                                       'to spectrum_<seed>.csv at every evaluate_every; the training trajectory is unchanged')),
+           ('spectrum_n', 8192, dict(type=int, help='with --spectrum_data: the first N images of x_train against N samples (default: 8192)'))),
+    switch='spectrum_data', refusals=_refusals,
+    # (the real set is transformed once, in the constructor)
+    build=lambda H, run: SpectrumMonitor(*run.head, H.spectrum_data, n=H.spectrum_n, P=run.P),
+    log_lines=lambda monitor, step, out: [log_line(step, out)])
+add_hook_arguments, check_hook_arguments = HOOK.add_arguments, HOOK.check
 
 
 # ---- the command line (test_spectrum.py) ----

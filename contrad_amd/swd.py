@@ -33,7 +33,8 @@ import numpy as np
 import torch
 
 from . import features, ops
-from .evaluate.gan import eval_seed_of, own_network, preserved_rng
+from .evaluate.gan import WeightsMonitor, load_x_train, own_network
+from .hooks import Hook
 
 PATCH = 7
 HALF = PATCH // 2
@@ -209,69 +210,46 @@ def log_line(step, out):
                                                    out['avg'])
 
 
-class SWDMonitor(object):
+class SWDMonitor(WeightsMonitor):
     """``--swd_data`` on rank 0: the sliced Wasserstein distance of the training generator's weights from the first ``n``
-    real images at every evaluation, appended as ``step,swd_<res>...,swd_avg`` to ``swd_<eval_seed>.csv``.  No encoder: it
-    needs none of the ``--prdc_*`` flags.  Like ``PRDCMonitor`` it owns a generator (built inside ``preserved_rng``, always in
-    eval mode) that loads the shown generator's state dict at each evaluation; the fakes come from fixed latents of the eval
+    real images at every evaluation, appended as ``step,swd_<res>...,swd_avg`` to ``swd_<eval_seed>.csv`` (evaluate/gan.py's
+    ``WeightsMonitor``).  No encoder: it needs none of the ``--prdc_*`` flags.  The fakes come from fixed latents of the eval
     seed (``features.sample_u8``) and the draws from the same seed, so two evaluations differ by the weights alone.  The real
     set goes to the device once.  It records only: there is no ``*_best.pt`` choice."""
 
     def __init__(self, logdir, architecture, image_size, device, seed, data_path, n=8192, batch=500, P=None, nhoods=128,
                  dir_repeats=4, dirs_per_repeat=128):
-        real = features.load_images(data_path, 'x_train')
-        if tuple(real.shape[1:]) != tuple(image_size):
-            raise ValueError('%s: x_train holds %s images, the generator makes %s' % (data_path, tuple(real.shape[1:]), tuple(image_size)))
+        real = load_x_train(data_path, image_size, 'generator makes')
         if real.shape[1] != real.shape[2]:
             raise ValueError('swd: %s holds %d x %d images, square images expected' % (data_path, real.shape[1], real.shape[2]))
         self.levels = levels_of(real.shape[1])
-        self.n = min(int(n), len(real))
+        self.n, self.batch = min(int(n), len(real)), int(batch)
         check_settings(self.n, nhoods, dir_repeats, dirs_per_repeat)
         self.settings = dict(nhoods=int(nhoods), dir_repeats=int(dir_repeats), dirs_per_repeat=int(dirs_per_repeat))
-        self.batch, self.device, self.eval_seed = int(batch), device, eval_seed_of(seed)
-        self.path = os.path.join(logdir, 'swd_%d.csv' % self.eval_seed)
         self.real = torch.from_numpy(real[:self.n]).to(device)
-        self.G = own_network('G', architecture, image_size, device, P)
-        if not os.path.exists(self.path):                                      # (a resumed run appends to its file)
-            with open(self.path, 'w') as f:
-                f.write(csv_head(self.levels) + '\n')
+        super().__init__(logdir, device, seed, own_network('G', architecture, image_size, device, P),
+                         [('swd_%d.csv', csv_head(self.levels), csv_line)], which='G')
 
-    def update(self, step, generator):
-        with torch.no_grad(), preserved_rng(self.device):
-            self.G.load_state_dict(generator.state_dict())
-            self.G.eval()
-            fake = features.sample_u8(self.G, self.n, self.batch, self.eval_seed)
-            out = swd_of(self.real, fake, seed=self.eval_seed, **self.settings)
-        with open(self.path, 'a') as f:
-            f.write(csv_line(step, out) + '\n')
-        return out
+    def evaluate(self):
+        fake = features.sample_u8(self.G, self.n, self.batch, self.eval_seed)
+        return swd_of(self.real, fake, seed=self.eval_seed, **self.settings)
 
 
 # ---- the training scripts' hook ----
-HOOK_DEFAULTS = {'swd_data': None, 'swd_n': 8192}
-
-
-def add_hook_arguments(parser):
-    """The two flags of the training scripts.  A flag that is not given leaves no attribute on the parsed namespace (its
-    default lives in ``HOOK_DEFAULTS``; read the flags through ``check_hook_arguments``)."""
-    from argparse import SUPPRESS
-    parser.add_argument('--swd_data', type=str, default=SUPPRESS,
-                        help='npz with x_train uint8 [n, H, W, 3]: rank 0 appends the sliced Wasserstein distance (Laplacian-pyramid '
-                             'patches, no encoder) of the generator from these images, one value per resolution level and their '
-                             'average, to swd_<seed>.csv at every evaluate_every; the training trajectory is unchanged')
-    parser.add_argument('--swd_n', type=int, default=SUPPRESS,
-                        help='with --swd_data: the first N images of x_train against N samples (default: 8192)')
-
-
-def check_hook_arguments(P):
-    """Refusals that need no device (called before the first CUDA call) -> the hook's flags, defaults filled in."""
-    from types import SimpleNamespace
-    H = SimpleNamespace(**{name: getattr(P, name, default) for name, default in HOOK_DEFAULTS.items()})
-    if not H.swd_data and hasattr(P, 'swd_n'):
-        raise ValueError('--swd_n does nothing without --swd_data FILE.npz')
+def _refusals(H, P):
     if H.swd_data and H.swd_n < 1:
         raise ValueError('--swd_n must be at least 1, got %r' % (H.swd_n,))
-    return H
+
+
+HOOK = Hook(
+    flags=(('swd_data', None, dict(type=str, help='npz with x_train uint8 [n, H, W, 3]: rank 0 appends the sliced Wasserstein distance (Laplacian-pyramid '
+                                                  'patches, no encoder) of the generator from these images, one value per resolution level and their '
+                                                  'average, to swd_<seed>.csv at every evaluate_every; the training trajectory is unchanged')),
+           ('swd_n', 8192, dict(type=int, help='with --swd_data: the first N images of x_train against N samples (default: 8192)'))),
+    switch='swd_data', refusals=_refusals,
+    build=lambda H, run: SWDMonitor(*run.head, H.swd_data, n=H.swd_n, P=run.P),
+    log_lines=lambda monitor, step, out: [log_line(step, out)])
+add_hook_arguments, check_hook_arguments = HOOK.add_arguments, HOOK.check
 
 
 # ---- the command line (test_swd.py) ----

@@ -1,6 +1,7 @@
 """What the three training scripts share: the common flags, rank / process group, options, networks and optimizers, the
-rank-0 log, the gradient exchange, the loader choice, the monitoring hooks, the ``--graph`` gate and the loop with its
-log line and checkpoints.  ``train_gan`` and ``train_stylegan2`` keep what their reference counterparts do differently
+rank-0 log, the gradient exchange, the loader choice, the monitoring hooks (``HOOKS``: one list, in evaluation order, walked
+by four loops -- add the flags, check them, build the monitors on rank 0, evaluate), the ``--graph`` gate and the loop with
+its log line and checkpoints.  ``train_gan`` and ``train_stylegan2`` keep what their reference counterparts do differently
 and hand it over as a ``Script``; their ``main()`` is ``build_run`` + ``run_loop``."""
 import os
 import time
@@ -14,12 +15,12 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import config, contrast, latent, prdc, spectrum, swd
+from . import config, contrast, knn, latent, prdc, spectrum, swd
 from .augment import get_augment
 from .data import loader_for
 from .engine import GradAllReducer, setup_grad_exchange
 from .evaluate.gan import LastBatch, Monitor
-from .knn import KNNMonitor, add_hook_arguments
+from .hooks import Hook
 from .models.gan import get_architecture
 from .optim import FusedAdam
 from .training.gan import BASELINE_MODES, setup
@@ -71,21 +72,25 @@ def monitor_help(shows):
             'training_progress_<seed>.png (%s), real_augment_<seed>.png; the training trajectory is unchanged' % shows)
 
 
+# ``--monitor``: the image grids.  Its flag (and ``--no_gif``) is in the scripts' layouts, with their own help text.
+GRIDS = Hook(flags=(), switch='monitor',
+             build=lambda H, run: Monitor(*run.head, no_gif=run.P.no_gif, P=run.P, last_batch=lambda: run.loader.last),
+             log_lines=lambda monitor, step, out: ())
+
+# Every monitoring hook, in the order of one evaluation (and of its lines in log.txt).  PRDC is last: it decides ``_best``.
+HOOKS = (GRIDS, knn.HOOK, contrast.HOOK, swd.HOOK, spectrum.HOOK, latent.HOOK, prdc.HOOK)
+HELP_ORDER = (knn.HOOK, prdc.HOOK) + HOOKS[2:-1]        # --help keeps PRDC's flags where they have always been, behind kNN's
+
+
 def make_parser(description, layout):
     """``layout``: the script's flags in ``--help`` order -- the name of a common flag, or ``(name, kwargs)`` for a flag of
-    the script's own or for what it sets differently on a common one.  The monitoring hooks' flags
-    (knn.add_hook_arguments, then prdc.add_hook_arguments, contrast.add_hook_arguments, swd.add_hook_arguments,
-    spectrum.add_hook_arguments, latent.add_hook_arguments) come last."""
+    the script's own or for what it sets differently on a common one.  The flags of ``HOOKS`` come last."""
     parser = ArgumentParser(description=description)
     for item in layout:
         name, own = (item, {}) if isinstance(item, str) else item
         parser.add_argument(name, **dict(COMMON_FLAGS.get(name, {}), **own))
-    add_hook_arguments(parser)
-    prdc.add_hook_arguments(parser)
-    contrast.add_hook_arguments(parser)
-    swd.add_hook_arguments(parser)
-    spectrum.add_hook_arguments(parser)
-    latent.add_hook_arguments(parser)
+    for hook in HELP_ORDER:
+        hook.add_arguments(parser)
     return parser
 
 
@@ -188,12 +193,9 @@ def _loader(P, script, options, image_size, rank, world, dev, log):
 
 def build_run(P, script):
     """Everything between the parsed command line and the first iteration -> the run: P, options, G, D, g_ema (or None),
-    opt_G, opt_D, reducers, loader, graphed, and what ``run_loop`` needs around them."""
-    H = prdc.check_hook_arguments(P)                                # (refusals that need no device come first)
-    C = contrast.check_hook_arguments(P)
-    W = swd.check_hook_arguments(P)
-    F = spectrum.check_hook_arguments(P)
-    L = latent.check_hook_arguments(P)
+    opt_G, opt_D, reducers, loader, graphed, monitors (rank 0: ``(hook, monitor)`` of every hook that is on, in the order
+    of ``HOOKS``), and what ``run_loop`` needs around them."""
+    checked = [(hook, hook.check(P)) for hook in HOOKS]             # (refusals that need no device come first)
     if P.comment:
         P.comment = '_' + P.comment
     P.gin_stem = Path(P.gin_config).stem
@@ -250,40 +252,17 @@ def build_run(P, script):
     for line in (script.start_up_lines(P) if script.start_up_lines is not None else ()):
         log(line)
 
-    monitor = knn_monitor = prdc_monitor = contrast_monitor = None
     if P.monitor and rank == 0:
-        monitor = Monitor(logdir, P.architecture, image_size, dev, P.seed, no_gif=P.no_gif, P=P)
         loader = LastBatch(loader)                                  # the preview shows the batch the step drew
-    if P.knn_data and rank == 0:
-        knn_monitor = KNNMonitor(logdir, P.architecture, image_size, dev, P.seed, P.knn_data, k=P.knn_k, temp=P.knn_temp, P=P)
-    if C.contrast_data and rank == 0:                               # blocks of the training batch (all ranks' images)
-        contrast_monitor = contrast.ContrastMonitor(logdir, P.architecture, image_size, dev, P.seed, C.contrast_data,
-                                                    n=C.contrast_n, t=C.contrast_t, P=P, batch=options['batch_size'] * world)
-    if H.prdc_data and rank == 0:
-        prdc_monitor = prdc.PRDCMonitor(logdir, P.architecture, image_size, dev, P.seed, H.prdc_data, H.prdc_encoder,
-                                        encoder_arch=H.prdc_encoder_arch, k=H.prdc_k, n_fake=H.prdc_n, best=H.prdc_best,
-                                        resumed_step=starting_step - 1, P=P, kid=H.prdc_kid,
-                                        kid_kernel=H.prdc_kid_kernel, auth=H.prdc_auth, fd=H.prdc_fd,
-                                        fd_iter=H.prdc_fd_iter)
-    swd_monitor = None
-    if W.swd_data and rank == 0:                                    # (no encoder: none of the --prdc_* flags is needed)
-        swd_monitor = swd.SWDMonitor(logdir, P.architecture, image_size, dev, P.seed, W.swd_data, n=W.swd_n, P=P)
-    spectrum_monitor = None
-    if F.spectrum_data and rank == 0:                               # (no encoder either; the real set is transformed once, here)
-        spectrum_monitor = spectrum.SpectrumMonitor(logdir, P.architecture, image_size, dev, P.seed, F.spectrum_data,
-                                                    n=F.spectrum_n, P=P)
-    ppl_monitor = None
-    if L.ppl_encoder and rank == 0:                                 # (no real data: an encoder file alone)
-        ppl_monitor = latent.PPLMonitor(logdir, P.architecture, image_size, dev, P.seed, L.ppl_encoder,
-                                        encoder_arch=L.ppl_encoder_arch, n=L.ppl_n, space=L.ppl_space, P=P)
+    monitor_run = SimpleNamespace(head=(logdir, P.architecture, image_size, dev, P.seed), P=P, loader=loader,
+                                  batch=options['batch_size'] * world, resumed_step=starting_step - 1)
+    monitors = [(hook, hook.build(H, monitor_run)) for hook, H in checked if rank == 0 and hook.on(P)]
     graphed, why_not = graph_gate(P, script)
     if why_not:
         log(why_not)
     return SimpleNamespace(P=P, options=options, G=G, D=D, g_ema=g_ema, opt_G=opt_G, opt_D=opt_D, reducers=reducers,
                            loader=loader, graphed=graphed, nets=nets, rank=rank, world=world, logdir=logdir, log=log,
-                           starting_step=starting_step, monitor=monitor, knn_monitor=knn_monitor,
-                           prdc_monitor=prdc_monitor, contrast_monitor=contrast_monitor, swd_monitor=swd_monitor,
-                           spectrum_monitor=spectrum_monitor, ppl_monitor=ppl_monitor)
+                           starting_step=starting_step, monitors=monitors)
 
 
 def run_loop(run, iteration):
@@ -305,24 +284,12 @@ def run_loop(run, iteration):
                  P.print_every * images_per_step / max(time.time() - t0, 1e-9)))
             t0 = time.time()
         if step % P.evaluate_every == 0 and run.rank == 0:
-            if run.monitor is not None:
-                run.monitor.update(step, run.g_ema if run.g_ema is not None else run.G, run.loader.last, P.augment_fn)
-            if run.knn_monitor is not None:
-                log('[Steps %7d] [kNN Acc@1 %.3f]' % (step, run.knn_monitor.update(step, run.D)['acc@1']))
-            if run.contrast_monitor is not None:
-                log(contrast.log_line(step, run.contrast_monitor.update(step, run.D)))
-            if run.swd_monitor is not None:
-                log(swd.log_line(step, run.swd_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)))
-            if run.spectrum_monitor is not None:
-                log(spectrum.log_line(step, run.spectrum_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)))
-            if run.ppl_monitor is not None:
-                log(latent.log_line(step, run.ppl_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)))
             tags = ('', f'_{step}') if step % P.save_every == 0 else ('',)
-            if run.prdc_monitor is not None:
-                m = run.prdc_monitor.update(step, run.g_ema if run.g_ema is not None else run.G)
-                for line in run.prdc_monitor.log_lines(step, m):
+            for hook, monitor in run.monitors:
+                out = monitor.update(step, run.D if hook.shown == 'D' else run.g_ema if run.g_ema is not None else run.G)
+                for line in hook.log_lines(monitor, step, out):
                     log(line)
-                if m['improved']:                                   # the reference's best-checkpoint names: this step's networks
+                if hook.improved is not None and hook.improved(out):
                     tags += ('_best',)
             for tag in tags:
                 for name, net in run.nets.items():

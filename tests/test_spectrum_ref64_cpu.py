@@ -177,6 +177,16 @@ def test_hook_flag_checks():
 
 
 def test_the_training_scripts_take_the_flags():
+    """The parsers of the training scripts accept the spectrum hook's flags and its check hands them back -- and so for
+    every hook the driver registers."""
+    import hook_flags
     from contrad_amd import train_driver
-    src = open(train_driver.__file__).read()
-    assert 'spectrum.add_hook_arguments(parser)' in src and 'spectrum.check_hook_arguments(P)' in src
+    assert spectrum.HOOK in train_driver.HOOKS
+    assert [hook.switch for hook in train_driver.HOOKS] == list(hook_flags.GIVEN)        # every registered hook is walked
+    for name, parse in hook_flags.script_parsers().items():
+        H = spectrum.check_hook_arguments(parse(hook_flags.MINIMAL + ['--spectrum_data', 'x.npz', '--spectrum_n', '9']))
+        assert (H.spectrum_data, H.spectrum_n) == ('x.npz', 9), name
+        for hook in train_driver.HOOKS:
+            flags, want = hook_flags.GIVEN[hook.switch]
+            P = parse(hook_flags.MINIMAL + flags)
+            assert hook.on(P) and vars(hook.check(P)) == want, (name, hook.switch)
